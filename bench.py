@@ -2,7 +2,7 @@
 """bench.py -- BASELINE.json's metric on MI355X: Mcells/s per Jacobi iteration
 and ms per simulation step of the Stable-Fluids vel_step + dens_step.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
 
 With N > 1 and no WORLD_SIZE in the environment the command starts its own N ranks as child processes
 (python -m torch.distributed.run ... bench.py, before anything here touches the GPU) and relays rank 0's line;
@@ -15,7 +15,11 @@ started under torch.distributed.run (as the driver does) it is one of those rank
 A "step" is one loop body of the reference's main (FluidSequential.c:298-306):
 sources zeroed, vel_step, dens_step, 40 Jacobi sweeps per solve = 200 sweeps,
 3 advects, 2 projections.  Fields are resident in HBM when the timed region
-starts.  One JSON line on rank 0.
+starts.  One JSON line on rank 0.  With --dump-outputs DIR, rank 0 also writes u, v and dens as the last timed
+step of the headline grid left them (DIR/u.npy, v.npy, dens.npy) and, on 1 GPU, as the ordinary-data leg's last
+timed step left them (DIR/ordinary_u.npy, ...): float32, a fixed sample of cells on large grids (output_cells).
+The headline's fields have decayed to zeros after a dozen steps at 4096^2; the ordinary-data leg's keep their
+magnitude.  The inputs depend only on the arguments, so two builds can be compared output for output.
 
 Workload: N=1 -> 4096^2 (the grid BASELINE.json's metric is quoted on, config
 2); N>1 -> 8192^2 split into row slabs (config 3), strong scaling, with the
@@ -50,6 +54,9 @@ VALU_PEAK_PER_SIMD_US = 570.0
 SIMDS = 1024
 BYTES_PER_CELL_SWEEP = 12      # read x + read x0 + write x_new, fp32 (6 with fp16 storage)
 BYTES_PER_CELL_STEP = 2548     # SURVEY.md 8(d), 40 sweeps/solve
+DUMP_FIELDS = ("u", "v", "dens")        # what step(N, dt, diff, visc, u, v, dens) hands back to its caller
+DUMP_CELLS = 1 << 21                    # per field: two legs x 3 fields x 8 MiB stay under the 64 MB a dump may take
+DUMP_SEED = 20261015
 
 
 def parse():
@@ -84,7 +91,12 @@ def parse():
                     help="multi-GPU halo exchange: the library's own RCCL exchange (C++, no host wait) or "
                          "torch.distributed (auto: rccl with --backend nccl)")
     ap.add_argument("--check", action="store_true", help="multi-GPU: also verify bit equality with a 1-context run (small grids)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write u, v and dens as the last timed step "
+                                                           "left them to DIR/[ordinary_]<field>.npy (float32; see output_cells)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def timed_steps(solver, dist, world, steps, iters, before_step=None):
@@ -165,6 +177,16 @@ def measure_ordinary(solver, fields, steps, warmup, iters):
     torch.cuda.synchronize()
     copy_ms = (time.perf_counter() - t0) * 1e3 / steps
     return timed_steps(solver, None, 1, steps, iters, before_step=inject) + (copy_ms,)
+
+
+def output_cells(grid):
+    """Flat indices of the cells --dump-outputs writes of a grid x grid field: None (every cell, as a 2-D array) up to
+    DUMP_CELLS cells, else DUMP_CELLS draws from PCG64 seed DUMP_SEED, sorted and without repeats (a 1-D array) -- the
+    same cells for every field and every run at this grid."""
+    import numpy as np
+    if grid * grid <= DUMP_CELLS:
+        return None
+    return np.unique(np.random.default_rng(DUMP_SEED).integers(0, grid * grid, size=DUMP_CELLS))
 
 
 def pmc_summary(grid):
@@ -380,7 +402,24 @@ def main():
         overlap_trials[n_] = {"overlap_ms_per_step": ms[1], "in_line_ms_per_step": ms[0], "chosen": overlap_choice[n_],
                               "note": "FLUID_PARAM_XCHG_OVERLAP measured both ways over 4 untimed steps before the warm-up"}
 
-    def run(n_, steps, warmup, fuse_divergence=True):
+    outputs = {} if a.dump_outputs else None
+
+    def keep_outputs(s, n_, prefix):
+        """--dump-outputs: DUMP_FIELDS as the last timed step left them (every rank takes part in the gathers).  Taken
+        after the leg's stand-alone pressure solves, which write only u_prev, v_prev and scratch: the host work here
+        would otherwise idle the GPU just before they are timed (measured: `value` 5 % lower)."""
+        pick = output_cells(n_ + 2)
+        for k in DUMP_FIELDS:
+            f = s.gather_global(k)
+            outputs[prefix + k] = f if pick is None else f.reshape(-1)[pick]
+
+    def write_outputs():
+        if outputs and rank == 0:
+            os.makedirs(a.dump_outputs, exist_ok=True)
+            for k, v in outputs.items():
+                np.save(os.path.join(a.dump_outputs, k + ".npy"), v.astype(np.float32, copy=False))
+
+    def run(n_, steps, warmup, fuse_divergence=True, dump=False):
         choose_overlap(n_)
         tune(n_)
         fields = initialize_parameters(n_, seed=a.seed)     # same seed on every rank
@@ -390,6 +429,8 @@ def main():
         solve = pressure_solve_rate(s, a.iters, max(steps // 2, 4)) if world == 1 else None
         calls = s.exchange_calls()
         native[0] = s.native_exchange
+        if dump and outputs is not None:
+            keep_outputs(s, n_, "")
         s.close()
         return out + (solve,), fields, calls
 
@@ -418,7 +459,7 @@ def main():
         tuning[(n_, "ordinary")] = {"untimed_steps": steps, "shapes_still_open": s.autotune_pending()}
         s.close()
 
-    def run_ordinary(n_, steps, warmup):
+    def run_ordinary(n_, steps, warmup, dump=False):
         tune(n_)
         tune_ordinary(n_)
         fields = initialize_parameters(n_, seed=a.seed)
@@ -426,6 +467,8 @@ def main():
         s.load_global(**fields)
         out = measure_ordinary(s, fields, steps, warmup, a.iters)
         solve = pressure_solve_rate(s, a.iters, max(steps // 2, 4))
+        if dump and outputs is not None:
+            keep_outputs(s, n_, "ordinary_")
         s.close()
         return out + (solve,)
 
@@ -440,8 +483,9 @@ def main():
                 "in_step_pressure_us_per_sweep": t_instep * 1e6}
 
     if a.only_ordinary:
-        e, j, p, t, copy_ms, solve = run_ordinary(n, a.steps, a.warmup)
+        e, j, p, t, copy_ms, solve = run_ordinary(n, a.steps, a.warmup, dump=True)
         r = rates(e, j, p, t, a.steps, cells, solve)
+        write_outputs()
         emit({"value_ordinary_data": r, "copy_ms_per_step": copy_ms})
         return
 
@@ -465,10 +509,10 @@ def main():
                     sys.exit("rank %d: %s differs between %d slabs and one context" % (rank, k, world))
         if rank == 0:
             print("check ok: %d slabs bit-identical to one context at %dx%d" % (world, grid, grid), file=sys.stderr)
-    def measure_grid(grid_, steps, warmup):
+    def measure_grid(grid_, steps, warmup, dump=False):
         """One grid on this job's ranks: the timed steps, the rates and the roofline objects."""
         n_, cells_ = grid_ - 2, grid_ * grid_
-        (elapsed, jac_ms, prs_ms, t, solve), fields, calls = run(n_, steps, warmup)
+        (elapsed, jac_ms, prs_ms, t, solve), fields, calls = run(n_, steps, warmup, dump=dump)
         r = rates(elapsed, jac_ms, prs_ms, t, steps, cells_, solve)
         ms_step, t_sweep = r["ms_per_step"], r["t_sweep"]
         sweeps, field_launches = t["sweeps"], t["jacobi_field_launches"]
@@ -578,7 +622,7 @@ def main():
         finally:
             world = keep
 
-    m, fields, _raw = measure_grid(grid, a.steps, a.warmup)
+    m, fields, _raw = measure_grid(grid, a.steps, a.warmup, dump=True)
     arith = "fp32" if a.dtype == "f32" else "fp16 storage, fp32 arithmetic"
     native_exchange = native[0]
     line = {
@@ -629,7 +673,7 @@ def main():
             "note": "FLUID_PARAM_FUSE_DIVERGENCE = 0: the same K steps with k_divergence as a separate pass, so that the "
                     "pressure solves inside the steps are sweeps alone (how round 1 measured `value`)"}
     if world == 1 and not a.no_ordinary:
-        e2, j2, p2, t2, copy_ms, solve2 = run_ordinary(n, a.steps, a.warmup)
+        e2, j2, p2, t2, copy_ms, solve2 = run_ordinary(n, a.steps, a.warmup, dump=True)
         r2 = rates(e2, j2, p2, t2, a.steps, cells, solve2)
         line["value_ordinary_data"] = {
             "value": r2["value"], "unit": "Mcells/s", "us_per_jacobi_sweep": r2["us_per_jacobi_sweep"],
@@ -657,6 +701,7 @@ def main():
                                                      "source_copies_ms_per_step": copy_o}
     if rank == 0 and world == 1 and not a.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(n, fields, a.iters)
+    write_outputs()
     if rank == 0:
         emit(line)
     if world > 1:

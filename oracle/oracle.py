@@ -134,10 +134,6 @@ def have_ref(n, iters=ITERS):
     return os.path.exists(ref_path(n, iters))
 
 
-def can_build_ref():
-    return os.path.exists("/root/reference/project/sequential/FluidSequential.c")
-
-
 class Reference:
     """project/sequential/FluidSequential.c itself, compiled by build_ref.sh
     for one (N, sweeps).  dt/visc/diff are the reference's macros; they are

@@ -213,7 +213,28 @@ def trajectory_checksums(only=None):
         json.dump(rows, f, indent=1)
 
 
+def oracle_vs_ref():
+    """CRC-32 of what the reference computes in tests/test_oracle_vs_ref.py's recipes (seeded operator inputs, steps
+    from its own initializeParameters): the test replays the same recipes on the restatement against these."""
+    import json
+    sys.path.insert(0, os.path.dirname(OUT))
+    from oracle.oracle import Oracle
+    from test_oracle_vs_ref import CHECKSUMS, OPERATOR_SIZES, STEP_CASES, each_operator, steps_from_reference_init
+    build_ref(["%d:40" % n for n in OPERATOR_SIZES] + ["%d:%d" % c for c in STEP_CASES])
+    coefficients = Oracle().coefficients
+    rows = {"each_operator": {}, "steps": {}}
+    for n in OPERATOR_SIZES:
+        rows["each_operator"][str(n)] = dict(each_operator(Reference(n, 40), n, coefficients, stale=0))
+    for n, iters in STEP_CASES:
+        rows["steps"]["%d:%d" % (n, iters)] = dict(steps_from_reference_init(Reference(n, iters)))
+    with open(CHECKSUMS, "w") as f:
+        json.dump(rows, f, indent=1)
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["oracle_vs_ref"]:
+        oracle_vs_ref()
+        sys.exit(0)
     if sys.argv[1:] == ["checksums"]:
         checksums()
         sys.exit(0)
@@ -231,4 +252,5 @@ if __name__ == "__main__":
     state_grid()
     checksums()
     trajectory_checksums()
+    oracle_vs_ref()
     print("golden vectors written to", OUT)

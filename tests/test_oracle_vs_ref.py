@@ -1,81 +1,126 @@
-"""CPU, build container only: the restatement against the reference itself
-(oracle/_ref/*.so, built from /root/reference by oracle/build_ref.sh) on fresh
-random inputs.  Skipped where neither the reference tree nor a prebuilt
-oracle/_ref is present."""
+"""CPU: the restatement against the reference itself on seeded random inputs --
+every operator on its own, and whole steps from the reference's own
+initializeParameters.  The reference's outputs are pinned by the CRC-32 of
+their bytes in tests/golden/oracle_vs_ref.json, which tests/golden/make_golden.py
+records by running the recipes below on the compiled reference
+(oracle/_ref/*.so); here the restatement runs the same recipes and must
+reproduce every checksum, so neither the reference nor its build is needed."""
+import json
+import os
+import zlib
+
 import numpy as np
 import pytest
 
-from conftest import assert_bit_equal, rnd
-from oracle.oracle import DIFF, DT, VISC, Reference, can_build_ref, have_ref
+from conftest import GOLDEN, rnd
+from oracle.oracle import DIFF, DT, VISC
+
+CHECKSUMS = os.path.join(GOLDEN, "oracle_vs_ref.json")
+OPERATOR_SIZES = [14, 30, 61, 126]
+STEP_CASES = [(30, 40), (61, 40), (126, 40), (126, 20), (254, 40)]
+FIELDS = ("dens", "dens_prev", "u", "u_prev", "v", "v_prev")      # initializeParameters' order
 
 
-def _ref(n, iters=40):
-    if not (have_ref(n, iters) or can_build_ref()):
-        pytest.skip("reference build for N=%d not available here" % n)
-    return Reference(n, iters)
+def crc(a):
+    return zlib.crc32(np.ascontiguousarray(a, dtype=np.float32).view(np.uint8).reshape(-1))
 
 
-@pytest.mark.parametrize("n", [14, 30, 61, 126])
-def test_each_operator(oracle, n):
-    r = _ref(n)
+def each_operator(eng, n, coefficients, stale):
+    """(label, CRC-32) of every operator's output on inputs drawn from PCG64 seed n, then ("inputs", CRC-32 of every
+    array drawn, as drawn).  `eng` is the reference or the restatement (same method names and argument order).  Each
+    advect writes into one of a freshly drawn pair -- the first for `stale` 0, the second for 1 -- so the recorded run
+    and the checked one start from different stale contents."""
     rng = np.random.default_rng(n)
+    drawn = [0]
+
+    def draw(lo=-1.0, hi=1.0):
+        a = rnd(rng, n, lo, hi)
+        drawn[0] = zlib.crc32(a.view(np.uint8).reshape(-1), drawn[0])
+        return a
+
     for b in (0, 1, 2):
-        x = rnd(rng, n)
-        y = x.copy()
-        r.set_bnd(b, x)
-        oracle.set_bnd(b, y)
-        assert_bit_equal(y, x, "set_bnd")
-    x, s = rnd(rng, n), rnd(rng, n)
-    y = x.copy()
-    r.add_source(x, s)
-    oracle.add_source(y, s)
-    assert_bit_equal(y, x, "add_source")
+        x = draw()
+        eng.set_bnd(b, x)
+        yield "set_bnd b=%d" % b, crc(x)
+    x, s = draw(), draw()
+    eng.add_source(x, s)
+    yield "add_source", crc(x)
     for b, coef in ((1, VISC), (2, VISC), (0, DIFF), (0, None)):
-        a, be = (1.0, 4.0) if coef is None else oracle.coefficients(n, DT, coef)
-        x, x0 = rnd(rng, n), rnd(rng, n)
-        y = x.copy()
-        r.diffuse(b, x, x0.copy(), a, be)
-        oracle.diffuse(b, y, x0, a, be, 40)
-        assert_bit_equal(y, x, "diffuse b=%d" % b)
-    u, v = rnd(rng, n), rnd(rng, n)
-    p, d = rnd(rng, n), rnd(rng, n)
-    p2, d2 = p.copy(), d.copy()
-    r.divergence(u, v, p, d)
-    oracle.divergence(u, v, p2, d2)
-    assert_bit_equal(p2, p, "p")
-    assert_bit_equal(d2, d, "div")
-    u2, v2 = u.copy(), v.copy()
-    pr = rnd(rng, n)
-    r.subtract_gradient(u, v, pr)
-    oracle.subtract_gradient(u2, v2, pr)
-    assert_bit_equal(u2, u, "grad u")
-    assert_bit_equal(v2, v, "grad v")
+        a, be = (1.0, 4.0) if coef is None else coefficients(n, DT, coef)
+        x, x0 = draw(), draw()
+        eng.diffuse(b, x, x0.copy(), a, be)
+        yield "diffuse b=%d %s" % (b, "pressure" if coef is None else "coef=%g" % coef), crc(x)
+    u, v = draw(), draw()
+    p, d = draw(), draw()
+    eng.divergence(u, v, p, d)
+    yield "p", crc(p)
+    yield "div", crc(d)
+    pr = draw()
+    eng.subtract_gradient(u, v, pr)
+    yield "grad u", crc(u)
+    yield "grad v", crc(v)
     for amp in (0.01, 1.0, 4.0 / DT):
-        u, v, d0 = rnd(rng, n, -amp, amp), rnd(rng, n, -amp, amp), rnd(rng, n)
+        u, v, d0 = draw(-amp, amp), draw(-amp, amp), draw()
         for b in (0, 1, 2):
-            d, e = rnd(rng, n), rnd(rng, n)
-            r.advect(b, d, d0, u, v)
-            oracle.advect(b, e, d0, u, v)
-            assert_bit_equal(e, d, "advect amp=%g b=%d" % (amp, b))
+            d = (draw(), draw())[stale]
+            eng.advect(b, d, d0, u, v)
+            yield "advect amp=%g b=%d" % (amp, b), crc(d)
+    yield "inputs", drawn[0]
 
 
-@pytest.mark.parametrize("n,iters", [(30, 40), (61, 40), (126, 40), (126, 20), (254, 40)])
-def test_steps_from_reference_init(oracle, n, iters):
-    r = _ref(n, iters)
-    a = r.initialize()
-    b = oracle.initialize_glibc(n)
-    for x, y in zip(a, b):
-        assert_bit_equal(y, x, "initializeParameters")
-    dens, dens0, u, u0, v, v0 = a
-    d2, d02, u2, u02, v2, v02 = b
-    r.step_src(u, v, dens, u0, v0, dens0)
-    oracle.step_src(u2, v2, d2, u02, v02, d02, iters=iters)
-    for z in range(3):
-        for x, y, w in ((u, u2, "u"), (v, v2, "v"), (dens, d2, "dens"), (u0, u02, "u_prev"), (v0, v02, "v_prev"),
-                        (dens0, d02, "dens_prev")):
-            assert_bit_equal(y, x, "%s after step %d" % (w, z + 1))
-        r.step(u, v, dens, u0, v0, dens0)
-        oracle.step(u2, v2, d2, u02, v02, d02, iters=iters)
+def steps_from_reference_init(eng, steps=3):
+    """(label, CRC-32) of the six fields initializeParameters draws (glibc rand, seed 1), then of all six after each of
+    `steps` steps of the reference's loop, the first with the sources.  `eng`: initialize(), step_src(), step() as the
+    oracle.Reference class has them."""
+    fs = eng.initialize()
+    for name, f in zip(FIELDS, fs):
+        yield "initializeParameters %s" % name, crc(f)
+    dens, dens0, u, u0, v, v0 = fs
+    for z in range(1, steps + 1):
+        (eng.step_src if z == 1 else eng.step)(u, v, dens, u0, v0, dens0)
+        for name, f in zip(FIELDS, fs):
+            yield "%s after step %d" % (name, z), crc(f)
+
+
+class Restatement:
+    """The oracle behind the interface of oracle.Reference for one sweep count."""
+
+    def __init__(self, oracle, n, iters):
+        self.oracle, self.n, self.iters = oracle, n, iters
+
+    def initialize(self):
+        return self.oracle.initialize_glibc(self.n)
+
+    def step_src(self, *fields):
+        self.oracle.step_src(*fields, iters=self.iters)
+
+    def step(self, *fields):
+        self.oracle.step(*fields, iters=self.iters)
+
+
+@pytest.fixture(scope="module")
+def recorded():
+    with open(CHECKSUMS) as f:
+        return json.load(f)
+
+
+def check(got, want, what):
+    got = dict(got)
+    assert list(got) == list(want), "%s: the recipe's outputs are not the recorded ones" % what
+    assert got.get("inputs") == want.get("inputs"), "%s: the inputs drawn are not those the checksums were recorded on" % what
+    bad = [k for k in want if got[k] != want[k]]
+    assert not bad, "%s: the restatement's bytes differ from the reference's in %s" % (what, ", ".join(bad))
+
+
+@pytest.mark.parametrize("n", OPERATOR_SIZES)
+def test_each_operator(oracle, recorded, n):
+    check(each_operator(oracle, n, oracle.coefficients, stale=1), recorded["each_operator"][str(n)], "N=%d" % n)
+
+
+@pytest.mark.parametrize("n,iters", STEP_CASES)
+def test_steps_from_reference_init(oracle, recorded, n, iters):
+    check(steps_from_reference_init(Restatement(oracle, n, iters)), recorded["steps"]["%d:%d" % (n, iters)],
+          "N=%d, %d sweeps" % (n, iters))
 
 
 def test_portable_init_shape(oracle):
