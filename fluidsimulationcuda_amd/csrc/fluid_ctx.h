@@ -11,6 +11,7 @@
 
 namespace fluid_detail {
 int fail(int code, const char* fmt, ...);      // records the calling thread's error string, returns `code`
+int materialize_zero(fluid_ctx* c, int f);      // a field zero by definition gets its zeros in memory (fluid_solver.hip)
 struct RcclExchange;                            // fluid_exchange_rccl.hip
 void rccl_release(RcclExchange* x);
 }  // namespace fluid_detail
@@ -29,6 +30,23 @@ void rccl_release(RcclExchange* x);
         if (rc_ != FLUID_OK) return rc_; \
     } while (0)
 
+// What one field's buffer holds beyond its memory (fluid_solver.hip: "row-slab bookkeeping", "fields that are zero by
+// definition").  Two fields trade buffers by trading the whole record; only wrote() and mark_zero() reset one.
+struct FieldState {
+    void* ptr = nullptr;
+    int reach = 0;            // rows past each inner slab edge that hold their owner's values (see "row-slab bookkeeping")
+    bool zero = false;        // all +0 by definition; the memory is NOT (yet) zeroed
+    bool pend = false;        // owes itself `+ pend_inc` in every cell (deferred add_source of a zero source)
+    float pend_inc = 0.0f;
+    // add_source of a real source, deferred into the next diffusion's first launch (fluid_solver.hip: op_add_source)
+    int src_of = 0;           // 0: nothing owed; else 1 + the id of the source field s: owes itself + src_dt * s
+    float src_dt = 0.0f;
+    // fp16 storage: a projection's pressure is of the order h * |velocity| -- 1e-5 at 16384^2, fp16 subnormals -- so in a
+    // step the divergence and the pressure are kept multiplied by a power of two (fluid_solver.hip: project): fscale (1:
+    // plain values), undone exactly when the field is downloaded and by a pass over it for any reader that does not know
+    float fscale = 1.0f;
+};
+
 struct fluid_ctx {
     int n = 0, w = 0, pitch = 0;
     size_t field_floats = 0;
@@ -45,15 +63,15 @@ struct fluid_ctx {
     // collectives in one order), ordered against the compute stream(s) by events.  An exchange issued `async` is not waited
     // for at once: the first launch of the solve it feeds runs its interior strips -- rows that depend on this slab's own rows
     // only -- while the halo rows travel, and its edge strips behind the exchange's event (fluid_solver.hip: call_exchange,
-    // op_diffuse_batch).  FLUID_PARAM_XCHG_OVERLAP.
+    // launch_fused).  FLUID_PARAM_XCHG_OVERLAP.
     hipStream_t xstream = nullptr;
     hipEvent_t ev_xbegin = nullptr, ev_xdone = nullptr;
     bool xchg_overlap = true;
-    bool xpend = false;                    // an async exchange is in flight: whoever consumes its rows waits on ev_xdone first
+    unsigned xowed = 0;                    // compute streams that owe a wait on ev_xdone: bit 0 main, bit 1 stream2 (xchg_join)
     long long split_launches = 0;          // first launches that ran as interior + edge strips around an exchange
     bool early_advect = true;                      // FLUID_PARAM_EARLY_ADVECT
     float vmax_prev[2] = {-1.0f, -1.0f};           // the last global bounds of the velocity / density advection (-1: none yet)
-    void* f[FLUID_NFIELDS] = {};
+    FieldState field[FLUID_NFIELDS];
     size_t field_bytes = 0;
     unsigned int* d_scalar = nullptr;     // device word for the reductions
     float* d_partials = nullptr;          // slabs: per-block maxima of the gradient subtraction (launch_subtract_gradient)
@@ -79,21 +97,8 @@ struct fluid_ctx {
                                                    // allows it.  Every (mode, beta) is proven on the device first
     // slab decomposition
     int rank = 0, nranks = 1, own0 = 1, own1 = 1, min_slab = 0, halo = 1;
-    int reach[FLUID_NFIELDS] = {};            // see "row-slab bookkeeping" below
-    bool zero[FLUID_NFIELDS] = {};            // field is all +0 by definition; its memory is NOT (yet) zeroed
-    bool pend[FLUID_NFIELDS] = {};            // field owes itself `+ pend_inc[f]` in every cell (deferred add_source of a zero source)
-    float pend_inc[FLUID_NFIELDS] = {};
-    // add_source of a real source field, deferred into the first launch of the diffusion that consumes the sum
-    // (fluid_solver.hip: op_add_source / op_diffuse_batch): field f owes itself + src_dt[f] * (field src_of[f] - 1)
-    int src_of[FLUID_NFIELDS] = {};           // 0: nothing owed; else 1 + the id of the source field
-    float src_dt[FLUID_NFIELDS] = {};
     bool fuse_add_source = true;              // FLUID_PARAM_FUSE_ADD_SOURCE
-    // fp16 storage: the pressure of a projection is of the order h * |velocity| -- 1e-5 at 16384^2, inside fp16's subnormal
-    // range -- so inside a step the divergence and the pressure are kept multiplied by a power of two (fluid_solver.hip:
-    // project); fscale[f] is that factor for field f (1: plain values), undone exactly when the field is downloaded and by a
-    // pass over it for any reader that does not know
-    float pscale = 1.0f;
-    float fscale[FLUID_NFIELDS];
+    float pscale = 1.0f;                      // fp16 storage: the factor of a projection's scaled fields (FieldState::fscale)
     fluid_exchange_fn xchg = nullptr;
     void* xchg_user = nullptr;
     fluid_detail::RcclExchange* rccl = nullptr;   // the library's own exchange, when attached (fluid_exchange_rccl_attach)
@@ -110,7 +115,8 @@ struct fluid_ctx {
     bool in_pressure_solve = false;
 
     bool valid_field(int id) const { return id >= 0 && id < FLUID_NFIELDS; }
-    void* row(int id, int r) const { return static_cast<char*>(f[id]) + (size_t)r * pitch * esz; }
+    void* ptr(int id) const { return field[id].ptr; }
+    void* row(int id, int r) const { return static_cast<char*>(ptr(id)) + (size_t)r * pitch * esz; }
     int lo_all() const { return own0 - (rank == 0 ? 1 : 0); }          // owned rows incl. ghost row
     int hi_all() const { return own1 + (rank == nranks - 1 ? 1 : 0); }
 };

@@ -103,16 +103,6 @@ static void slab_rows(int n, int r, int P, int* lo, int* hi)
     *hi = *lo + base + (r < rem ? 1 : 0);
 }
 
-static int zero_if_marked(fluid_ctx* c, int f)
-{
-    // rows travel as they are in memory: a field that is zero only by definition gets its zeros now; a pending
-    // add_source increment stays pending on every rank alike (fluid_solver.hip: need_list)
-    if (!c->zero[f]) return FLUID_OK;
-    HIP_TRY(hipMemsetAsync(c->f[f], 0, c->field_bytes, c->stream));
-    c->zero[f] = false;
-    return FLUID_OK;
-}
-
 static int rccl_exchange(void* user, int kind, const int* fields, int nfields, int depth, float* scalar)
 {
     RcclExchange* x = static_cast<RcclExchange*>(user);
@@ -125,7 +115,9 @@ static int rccl_exchange(void* user, int kind, const int* fields, int nfields, i
         // every rank, or the tall ranks enter the group while the short ones return
         if (depth < 1 || depth > c->min_slab) return fail(FLUID_E_COMM, "halo depth %d does not fit the slabs (shortest: %d rows)", depth, c->min_slab);
         x->calls[0] += 1;
-        for (int k = 0; k < nfields; ++k) TRY(zero_if_marked(c, fields[k]));
+        // rows travel as they are in memory: a field that is zero only by definition gets its zeros now; a pending
+        // add_source increment stays pending on every rank alike (fluid_solver.hip: need_list)
+        for (int k = 0; k < nfields; ++k) TRY(materialize_zero(c, fields[k]));
         NCCL_TRY(api, api->GroupStart());
         for (int k = 0; k < nfields; ++k) {              // same order on every rank: sends and receives pair up
             const int f = fields[k];
@@ -144,7 +136,7 @@ static int rccl_exchange(void* user, int kind, const int* fields, int nfields, i
     }
     case FLUID_XCHG_GATHER: {
         x->calls[1] += 1;
-        for (int k = 0; k < nfields; ++k) TRY(zero_if_marked(c, fields[k]));
+        for (int k = 0; k < nfields; ++k) TRY(materialize_zero(c, fields[k]));
         NCCL_TRY(api, api->GroupStart());
         for (int k = 0; k < nfields; ++k)
             for (int r = 0; r < c->nranks; ++r) {

@@ -34,12 +34,22 @@ int fail(int code, const char* fmt, ...)
     return code;
 }
 
+// see "fields that are zero by definition" (the RCCL exchange's too: rows travel as they are in memory)
+int materialize_zero(fluid_ctx* c, int f)
+{
+    if (!c->field[f].zero) return FLUID_OK;
+    HIP_TRY(hipMemsetAsync(c->ptr(f), 0, c->field_bytes, c->stream));
+    c->field[f].zero = false;
+    return FLUID_OK;
+}
+
 }  // namespace fluid_detail
 
 namespace {
 
 using fluid_detail::fail;
 using fluid_detail::g_err;
+using fluid_detail::materialize_zero;
 
 constexpr size_t kControlBytes = 256;   // tail of the arena: reduction scalar (+0), division-proof counter (+8)
 constexpr int kMaxN = 65533;     // one grid row per blockIdx.y in the pointwise kernels (HIP: gridDim.y <= 65535 = N + 2);
@@ -64,17 +74,27 @@ int check_fields(const fluid_ctx* c, std::initializer_list<int> ids)
     return FLUID_OK;
 }
 
+// the bit of fluid_ctx::xowed of the compute stream work is enqueued on now
+unsigned stream_bit(const fluid_ctx* c) { return c->stream2 && c->stream == c->stream2 ? 2u : 1u; }
+
+// the current compute stream waits for the exchange in flight, if it still owes that wait; another stream's debt stays
+int xchg_join(fluid_ctx* c)
+{
+    if (!(c->xowed & stream_bit(c))) return FLUID_OK;
+    HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_xdone, 0));
+    c->xowed &= ~stream_bit(c);
+    return FLUID_OK;
+}
+
 // Every exchange goes through here.  One issued `async` (slabs, FLUID_PARAM_XCHG_OVERLAP) runs with the exchange stream as
-// "the context's stream": behind everything enqueued on the compute stream so far (event), and the compute stream behind it
-// again only when xchg_join() is called by whoever consumes the rows.  A callback that enqueues elsewhere or waits on the
-// host (the tests' in-process fabric) is merely not overlapped.  The ranks issue their collectives in one order whichever
-// stream each goes to (RCCL serialises a communicator's operations in issue order across streams).
+// "the context's stream": behind everything enqueued on the compute stream so far (event), and every compute stream behind
+// it again only when that stream calls xchg_join() before it consumes the rows.  A callback that enqueues elsewhere or waits
+// on the host (the tests' in-process fabric) is merely not overlapped.  The ranks issue their collectives in one order
+// whichever stream each goes to (RCCL serialises a communicator's operations in issue order across streams).
 int call_exchange(fluid_ctx* c, int kind, const int* ids, int count, int depth, float* scalar, bool async = false)
 {
-    if (c->xpend) {                                      // one exchange in flight at a time: the earlier one is joined first
-        HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_xdone, 0));
-        c->xpend = false;
-    }
+    // one exchange in flight at a time: this stream joins the earlier one (a debt left on the other waits on the later record)
+    TRY(xchg_join(c));
     // An exchange the caller waits for at once stays in line on the compute stream: a hop to another stream and back
     // costs ~10 us each way on this platform (measured: a no-op exchange routed through the second stream leaves the GPU
     // idle for 20 us), which only an exchange that runs beside a launch can pay for.
@@ -87,17 +107,8 @@ int call_exchange(fluid_ctx* c, int kind, const int* ids, int count, int depth, 
     c->stream = compute;
     if (rc != 0) return rc;
     HIP_TRY(hipEventRecord(c->ev_xdone, c->xstream));
-    c->xpend = true;
+    c->xowed = 3u;                                       // every compute stream: main and stream2
     return 0;
-}
-
-// the current compute stream waits for the exchange in flight (if any); `keep`: another stream still has to join it too
-int xchg_join(fluid_ctx* c, bool keep = false)
-{
-    if (!c->xpend) return FLUID_OK;
-    HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_xdone, 0));
-    if (!keep) c->xpend = false;
-    return FLUID_OK;
 }
 
 int exchange(fluid_ctx* c, int kind, std::initializer_list<int> fields, int depth, float* scalar = nullptr)
@@ -274,8 +285,8 @@ DivPlan division_mode(fluid_ctx* c, float beta, float alpha)
 }
 
 // ---- row-slab bookkeeping ------------------------------------------------------
-// reach[f] = how many rows beyond each INNER edge of this slab currently hold the
-// same values as their owner's copy (kEverywhere: the field is known identical
+// FieldState::reach = how many rows beyond each INNER edge of this slab currently hold
+// the same values as their owner's copy (kEverywhere: the field is known identical
 // on all ranks, e.g. freshly zeroed).  Writers set it (an operator that computes
 // `r` rows past the slab leaves reach r), need() raises it with ONE exchange for
 // all the fields that fall short.  With one slab everything is a no-op.
@@ -285,11 +296,15 @@ int exchange_cap(const fluid_ctx* c) { return c->min_slab - 1; }     // rows a n
 
 void wrote(fluid_ctx* c, int f, int reach)
 {
-    c->reach[f] = c->nranks > 1 ? reach : kEverywhere;
-    c->pend[f] = false;                        // overwritten: whatever the old contents still owed is moot
-    c->src_of[f] = 0;
-    c->fscale[f] = 1.0f;                       // (a writer that keeps a scale sets it again afterwards)
+    c->field[f].reach = c->nranks > 1 ? reach : kEverywhere;
+    c->field[f].zero = false;
+    c->field[f].pend = false;                        // overwritten: whatever the old contents still owed is moot
+    c->field[f].src_of = 0;
+    c->field[f].fscale = 1.0f;                       // (a writer that keeps a scale sets it again afterwards)
 }
+
+// fields a and b trade buffers -- and with them everything recorded about the buffers' contents
+void trade(fluid_ctx* c, int a, int b) { std::swap(c->field[a], c->field[b]); }
 
 // `async`: the compute stream does not wait for the rows (call_exchange); the caller's next solve joins them (xchg_join)
 int need_list(fluid_ctx* c, const std::vector<int>& fields, int reach, bool async = false)
@@ -298,7 +313,7 @@ int need_list(fluid_ctx* c, const std::vector<int>& fields, int reach, bool asyn
     if (reach > exchange_cap(c)) return fail(FLUID_E_COMM, "halo of %d rows exceeds the slab height", reach);
     std::vector<int> ids;
     for (int f : fields)
-        if (c->reach[f] < reach) ids.push_back(f);
+        if (c->field[f].reach < reach) ids.push_back(f);
     if (ids.empty()) return FLUID_OK;
     if (!c->xchg) return fail(FLUID_E_COMM, "multi-GPU context without an exchange callback");
     std::sort(ids.begin(), ids.end());
@@ -307,7 +322,7 @@ int need_list(fluid_ctx* c, const std::vector<int>& fields, int reach, bool asyn
     const int rc = call_exchange(c, FLUID_XCHG_HALO, ids.data(), (int)ids.size(), reach, nullptr, async);
     c->in_halo_exchange = false;
     if (rc != 0) return fail(FLUID_E_COMM, "halo exchange failed (rc %d)", rc);
-    for (int f : ids) c->reach[f] = reach;
+    for (int f : ids) c->field[f].reach = reach;
     return FLUID_OK;
 }
 
@@ -323,44 +338,47 @@ void rows(const fluid_ctx* c, int reach, int* lo, int* hi)
     *hi = std::min(c->n + 1, c->own1 + reach);
 }
 
+// rows(), plus the wall rows where the range reaches them (pointwise kernels treat them as cells, FluidSequential.c:78-82)
+void rows_with_walls(const fluid_ctx* c, int reach, int* lo, int* hi)
+{
+    rows(c, reach, lo, hi);
+    if (*lo == 1) *lo = 0;
+    if (*hi == c->n + 1) *hi = c->n + 2;
+}
+
 // ---- fields that are zero by definition ---------------------------------------------
-// The sources of every step after the first and the pressure's first guess are
-// all +0.  Writing those zeros and reading them back is pure traffic, so such a
-// field is only MARKED zero; the three consumers that matter take the mark
-// (add_source adds the constant dt*0, the fused Jacobi kernel reads nothing, the
-// divergence kernel skips its p stores) and everything else materialises the
-// zeros first.
-// add_source with a source that is zero by definition adds the constant dt*0 to every cell: it
-// changes nothing but the sign of -0 (and NaN/inf rules for a non-finite dt), yet costs a read and a
-// write of the whole field.  With the fused Jacobi kernel the increment stays PENDING instead: the
-// solve that consumes the field as its right-hand side adds it to each row as it loads it, any other
-// reader settles it with the real kernel first (here), and a writer that replaces the field drops it.
+// The sources of every step after the first and the pressure's first guess are all +0.  Writing those zeros and reading
+// them back is pure traffic, so such a field is only MARKED zero (FieldState::zero, mark_zero); the three consumers that
+// matter take the mark (add_source adds the constant dt*0, the fused Jacobi kernel reads nothing, the divergence kernel
+// skips its p stores) and everything else materialises the zeros first.
+// add_source of such a source adds dt*0 to every cell: nothing but the sign of -0 (and NaN/inf rules for a non-finite
+// dt), for a read and a write of the whole field.  With the fused Jacobi kernel the increment stays PENDING instead
+// (FieldState::pend): the solve that consumes the field as its right-hand side adds it to each row as it loads it, any
+// other reader settles it with the real kernel first (here), and a writer that replaces the field drops it (wrote).
 int settle_source(fluid_ctx* c, int f);
 
 // a field kept scaled (fscale) goes back to plain values: every row of it, one multiplication by a power of two
 int unscale(fluid_ctx* c, int f)
 {
-    if (c->fscale[f] == 1.0f) return FLUID_OK;
-    const float inv = 1.0f / c->fscale[f];
-    c->fscale[f] = 1.0f;
-    if (c->zero[f]) return FLUID_OK;
-    fluid::launch_scale(c->stream, c->st, c->f[f], c->pitch, 0, c->n + 2, inv);
+    if (c->field[f].fscale == 1.0f) return FLUID_OK;
+    const float inv = 1.0f / c->field[f].fscale;
+    c->field[f].fscale = 1.0f;
+    if (c->field[f].zero) return FLUID_OK;
+    fluid::launch_scale(c->stream, c->st, c->ptr(f), c->pitch, 0, c->n + 2, inv);
     return FLUID_OK;
 }
 
 int settle(fluid_ctx* c, int f, bool keep_scale = false)
 {
     if (!keep_scale) TRY(unscale(c, f));
-    if (c->src_of[f]) return settle_source(c, f);
-    if (!c->pend[f]) return FLUID_OK;
-    const int reach = c->nranks > 1 ? std::min(c->reach[f], exchange_cap(c)) : 0;
+    if (c->field[f].src_of) return settle_source(c, f);
+    if (!c->field[f].pend) return FLUID_OK;
+    const int reach = c->nranks > 1 ? std::min(c->field[f].reach, exchange_cap(c)) : 0;
     int lo, hi;
-    rows(c, reach, &lo, &hi);
-    if (lo == 1) lo = 0;
-    if (hi == c->n + 1) hi = c->n + 2;
-    const float inc = c->pend_inc[f];
-    c->pend[f] = false;
-    TIMED(c, FLUID_TIME_SOURCE, fluid::launch_add_source(c->stream, c->st, c->f[f], nullptr, c->pitch, lo, hi, inc));
+    rows_with_walls(c, reach, &lo, &hi);
+    const float inc = c->field[f].pend_inc;
+    c->field[f].pend = false;
+    TIMED(c, FLUID_TIME_SOURCE, fluid::launch_add_source(c->stream, c->st, c->ptr(f), nullptr, c->pitch, lo, hi, inc));
     return FLUID_OK;
 }
 
@@ -368,26 +386,15 @@ int settle(fluid_ctx* c, int f, bool keep_scale = false)
 // applies it on load)
 int settle_source(fluid_ctx* c, int f)
 {
-    if (c->src_of[f]) {
-        // an add_source of a real source field that no diffusion launch took over (see op_add_source): the kernel of its own
-        const int s = c->src_of[f] - 1;
-        const int reach = c->nranks > 1 ? std::min({c->reach[f], c->reach[s], exchange_cap(c)}) : 0;
-        int lo, hi;
-        rows(c, reach, &lo, &hi);
-        if (lo == 1) lo = 0;
-        if (hi == c->n + 1) hi = c->n + 2;
-        c->src_of[f] = 0;
-        TIMED(c, FLUID_TIME_SOURCE, fluid::launch_add_source(c->stream, c->st, c->f[f], c->f[s], c->pitch, lo, hi, c->src_dt[f]));
-        wrote(c, f, reach);
-    }
-    return FLUID_OK;
-}
-
-int materialize_zero(fluid_ctx* c, int f)
-{
-    if (!c->zero[f]) return FLUID_OK;
-    HIP_TRY(hipMemsetAsync(c->f[f], 0, c->field_bytes, c->stream));
-    c->zero[f] = false;
+    if (!c->field[f].src_of) return FLUID_OK;
+    // an add_source of a real source field that no diffusion launch took over (see op_add_source): the kernel of its own
+    const int s = c->field[f].src_of - 1;
+    const int reach = c->nranks > 1 ? std::min({c->field[f].reach, c->field[s].reach, exchange_cap(c)}) : 0;
+    int lo, hi;
+    rows_with_walls(c, reach, &lo, &hi);
+    c->field[f].src_of = 0;
+    TIMED(c, FLUID_TIME_SOURCE, fluid::launch_add_source(c->stream, c->st, c->ptr(f), c->ptr(s), c->pitch, lo, hi, c->field[f].src_dt));
+    wrote(c, f, reach);
     return FLUID_OK;
 }
 
@@ -403,14 +410,7 @@ int materialize(fluid_ctx* c, std::initializer_list<int> fs)
     return FLUID_OK;
 }
 
-void mark_zero(fluid_ctx* c, int f)
-{
-    c->zero[f] = true;
-    c->pend[f] = false;
-    c->src_of[f] = 0;
-    c->fscale[f] = 1.0f;
-    c->reach[f] = kEverywhere;
-}
+void mark_zero(fluid_ctx* c, int f) { wrote(c, f, kEverywhere); c->field[f].zero = true; }
 
 // ---- operators -------------------------------------------------------------------
 // `defer` (only the step functions pass it: nothing can touch x or s between this call and the diffusion that follows it
@@ -420,29 +420,27 @@ void mark_zero(fluid_ctx* c, int f)
 int op_add_source(fluid_ctx* c, int x, int s, float dt, bool defer = false)
 {
     // pointwise: valid as far out as both operands are
-    const int reach = c->nranks > 1 ? std::min({c->reach[x], c->reach[s], exchange_cap(c)}) : 0;
+    const int reach = c->nranks > 1 ? std::min({c->field[x].reach, c->field[s].reach, exchange_cap(c)}) : 0;
     int lo, hi;
-    rows(c, reach, &lo, &hi);
-    if (lo == 1) lo = 0;                     // wall rows are cells like any other here (FluidSequential.c:78-82)
-    if (hi == c->n + 1) hi = c->n + 2;
+    rows_with_walls(c, reach, &lo, &hi);
     TRY(materialize(c, x));
-    if (c->zero[s]) {
+    if (c->field[s].zero) {
         volatile float z = 0.0f;
         const float inc = dt * z;          // the reference's dt * s[i] with s[i] = +0 (sign and NaN rules included)
         if (c->variant == fluid::JACOBI_TB && c->defer_zero_source) {
-            c->pend[x] = true;             // (x was settled just above: one pending increment at a time)
-            c->pend_inc[x] = inc;
-            return FLUID_OK;               // reach[x] unchanged: nothing was written
+            c->field[x].pend = true;             // (x was settled just above: one pending increment at a time)
+            c->field[x].pend_inc = inc;
+            return FLUID_OK;               // x's reach unchanged: nothing was written
         }
-        TIMED(c, FLUID_TIME_SOURCE, fluid::launch_add_source(c->stream, c->st, c->f[x], nullptr, c->pitch, lo, hi, inc));
+        TIMED(c, FLUID_TIME_SOURCE, fluid::launch_add_source(c->stream, c->st, c->ptr(x), nullptr, c->pitch, lo, hi, inc));
     } else {
         TRY(settle(c, s));                 // (a source that is itself owed something: never inside a step)
         if (defer && c->fuse_add_source && c->variant == fluid::JACOBI_TB && c->tb_nv == 2) {
-            c->src_of[x] = 1 + s;
-            c->src_dt[x] = dt;
-            return FLUID_OK;               // reach[x] unchanged: nothing was written
+            c->field[x].src_of = 1 + s;
+            c->field[x].src_dt = dt;
+            return FLUID_OK;               // x's reach unchanged: nothing was written
         }
-        TIMED(c, FLUID_TIME_SOURCE, fluid::launch_add_source(c->stream, c->st, c->f[x], c->f[s], c->pitch, lo, hi, dt));
+        TIMED(c, FLUID_TIME_SOURCE, fluid::launch_add_source(c->stream, c->st, c->ptr(x), c->ptr(s), c->pitch, lo, hi, dt));
     }
     wrote(c, x, reach);
     return FLUID_OK;
@@ -583,6 +581,24 @@ int tune_end(fluid_ctx* c)
     return FLUID_OK;
 }
 
+// what pick_sweeps() needs to know of the problem, the same on every rank: `canonical` (fp16 storage: the schedule is part
+// of the result, so it derives from the global problem alone and a short reach exchanges early instead of shortening a
+// launch; fp32 results do not depend on it), `small` (below FLUID_PARAM_TB_MIN_CELLS: one launch per sweep; default 0,
+// the fused kernel wins at every size measured) and `slab_cells` (what a rank sweeps: from the base slab height, not this
+// rank's own, so that ranks of an uneven split take the same size-dependent decisions)
+struct SweepShape {
+    bool canonical, small;
+    long long slab_cells;
+};
+
+// for `count` solves per launch: fp32 weighs a batch's cells against TB_MIN_CELLS (plans made ahead of a batch pass 1)
+SweepShape sweep_shape(const fluid_ctx* c, int count)
+{
+    const bool canonical = c->st == fluid::STORAGE_F16;
+    const long long slab_cells = (long long)(c->nranks > 1 ? c->min_slab : c->n) * c->n;
+    return {canonical, (canonical ? (long long)c->n * c->n : slab_cells * count) < c->tb_min_cells, slab_cells};
+}
+
 // Sweeps fused into the next launch of a solve with `remaining` sweeps to go, of which `room` can run before rows must be
 // exchanged (slabs; = remaining on one GPU).  Depths 16 / 12 / 8 / 4 / 2 exist (2-column lanes, fp32 storage for 16 and
 // 12).  Per sweep the deep launches are the cheap ones where they pay at all, and a shallow remainder is dear (measured,
@@ -595,14 +611,15 @@ int tune_end(fluid_ctx* c)
 //   - FLUID_PARAM_TB_T16_MIN_CELLS replaces the size rules by one floor (0: always), so that tests can run the deep
 //     kernels of either form on grids the oracle finishes in milliseconds.
 //   - fp16 storage rounds once per launch, so its schedule is part of the result and stays the greedy 8 / 4 / 2 one.
-int pick_sweeps(const fluid_ctx* c, int remaining, int room, bool canonical, bool small, long long slab_cells, bool all_mode4)
+int pick_sweeps(const fluid_ctx* c, int remaining, int room, const SweepShape& shape, bool all_mode4)
 {
+    const long long slab_cells = shape.slab_cells;
     // the fused kernel addresses a field through 32-bit buffer offsets: fields of 2 GiB and more
     // (beyond ~23000^2 in fp32) take single-sweep launches
-    if (c->variant != fluid::JACOBI_TB || small || c->field_bytes >= 0x7F000000ull) return 1;
+    if (c->variant != fluid::JACOBI_TB || shape.small || c->field_bytes >= 0x7F000000ull) return 1;
     room = std::min(room, remaining);
     const int greedy = (room >= 8 && c->tb_max_t >= 8) ? 8 : (room >= 4 && c->tb_max_t >= 4) ? 4 : room >= 2 ? 2 : 1;
-    if (canonical || c->tb_nv != 2 || c->tb_max_t < 12 || room < 12 || (remaining & 1)) return greedy;
+    if (shape.canonical || c->tb_nv != 2 || c->tb_max_t < 12 || room < 12 || (remaining & 1)) return greedy;
     const bool forced = c->tb_t16_min_cells >= 0;
     const bool big = forced ? slab_cells >= c->tb_t16_min_cells : slab_cells >= (8ll << 20);
     if (!big) return greedy;
@@ -652,8 +669,8 @@ struct Solve {
 // caller would like valid afterwards (the gradient wants 1).  The temporally
 // blocked kernel runs T of the sweeps per launch, all solves of the batch in the
 // same launch.  Sweeps ping-pong between x's buffer and a scratch field's; if a
-// result ends in the scratch buffer the two fields trade buffers (pointer swap,
-// no copy) -- field ids, not addresses, are stable.
+// result ends in the scratch buffer the two fields trade buffers (trade(): the
+// records swap, no copy) -- field ids, not addresses, are stable.
 // `ds` (one GPU, a single pressure solve): the right-hand side sv[0].x0 is the divergence of (ds->u, ds->v), not yet
 // computed -- the first launch computes it row by row as it goes and stores it (fluid_kernels.hip, DIVSRC).
 struct DivSource {
@@ -661,19 +678,36 @@ struct DivSource {
     float scale;          // -0.5f * h
 };
 
-// `keep_pending`: an exchange the caller issued async feeds another batch on another stream too -- this batch joins it on
-// its own stream but leaves it marked as in flight (full_step: the density diffusion beside the velocity path)
-int op_diffuse_batch(fluid_ctx* c, const Solve* sv, int count, int iters, int final_reach = 0, const DivSource* ds = nullptr,
-                     int scratch_base = 0, bool keep_pending = false)
+// One op_diffuse_batch call: its solves, and what its steps -- prepare, plan, the sweep loop, commit -- hand on
+struct Batch {
+    const Solve* sv;
+    int count, iters, final_reach;
+    const DivSource* ds;
+    int scratch_base;          // a batch beside another on the second stream (full_step) takes the last slots
+    const int* scratch;        // each solve's ping-pong partner
+    const int* sum;            // where x0 + dt*s of a deferred add_source lands
+    int cur[3], nxt[3];        // the fields each solve's next launch reads its guess from / writes to
+    DivPlan plan[3];
+    bool same_mode, all_mode4, add_src;   // add_src: the right-hand sides' deferred add_source rides in the first launch
+    float out_scale[3];
+    SweepShape shape;
+};
+
+// a solve's |x0| minima per tile (division mode 3) go with its scratch field: a batch on the second stream has slots of its own
+unsigned* solve_tiles(const fluid_ctx* c, int slot) { return c->tiles + (size_t)slot * fluid::tile_rows(c->n) * fluid::tile_pitch(c->n); }
+
+// argument checks, the scales of the solves reconciled, right-hand sides that are zero by definition materialised
+int batch_prepare(fluid_ctx* c, Batch& B)
 {
-    static const int kScratchAll[3] = {FLUID_TMP0, FLUID_TMP1, FLUID_TMP2};
-    static const int kSumAll[3] = {FLUID_TMP3, FLUID_TMP4, FLUID_TMP5};      // x0 + dt*s of a deferred add_source lands here
-    if (scratch_base < 0 || scratch_base + count > 3) return fail(FLUID_E_INVALID, "a batch holds 1 to 3 solves");
-    const int* kScratch = kScratchAll + scratch_base;      // (a solve that runs beside another batch on a second stream takes the last one)
-    const int* kSum = kSumAll + scratch_base;
-    if (iters < 0 || (iters & 1)) return fail(FLUID_E_INVALID, "sweep count must be even and >= 0 (got %d)", iters);
-    if (count < 1 || count > 3) return fail(FLUID_E_INVALID, "a batch holds 1 to 3 solves");
-    for (int k = 0; k < count; ++k) {
+    static const int kScratch[3] = {FLUID_TMP0, FLUID_TMP1, FLUID_TMP2};
+    static const int kSum[3] = {FLUID_TMP3, FLUID_TMP4, FLUID_TMP5};
+    const Solve* sv = B.sv;
+    if (B.scratch_base < 0 || B.scratch_base + B.count > 3) return fail(FLUID_E_INVALID, "a batch holds 1 to 3 solves");
+    B.scratch = kScratch + B.scratch_base;
+    B.sum = kSum + B.scratch_base;
+    if (B.iters < 0 || (B.iters & 1)) return fail(FLUID_E_INVALID, "sweep count must be even and >= 0 (got %d)", B.iters);
+    if (B.count < 1 || B.count > 3) return fail(FLUID_E_INVALID, "a batch holds 1 to 3 solves");
+    for (int k = 0; k < B.count; ++k) {
         if (sv[k].x == sv[k].x0 || sv[k].x >= FLUID_TMP0 || sv[k].x0 >= FLUID_TMP0)
             return fail(FLUID_E_INVALID, "diffuse: x and x0 must be distinct non-scratch fields");
         for (int j = 0; j < k; ++j)
@@ -682,285 +716,276 @@ int op_diffuse_batch(fluid_ctx* c, const Solve* sv, int count, int iters, int fi
     }
     // The solve is linear in (x, x0): a right-hand side kept scaled (fp16 storage: the divergence, project()) gives a
     // solution with the same factor, provided the first guess carries it too (a guess that is zero by definition does)
-    float out_scale[3] = {1.0f, 1.0f, 1.0f};
-    for (int k = 0; k < count; ++k) {
-        const float sx = c->zero[sv[k].x] ? c->fscale[sv[k].x0] : c->fscale[sv[k].x];
-        if (sx != c->fscale[sv[k].x0] || c->src_of[sv[k].x0]) {
-            if (c->fscale[sv[k].x] != 1.0f || c->fscale[sv[k].x0] != 1.0f) TRY(xchg_join(c, keep_pending));
+    for (int k = 0; k < B.count; ++k) {
+        const FieldState &x = c->field[sv[k].x], &x0 = c->field[sv[k].x0];
+        if ((x.zero ? x0.fscale : x.fscale) != x0.fscale || x0.src_of) {
+            if (x.fscale != 1.0f || x0.fscale != 1.0f) TRY(xchg_join(c));
             TRY(unscale(c, sv[k].x));
             TRY(unscale(c, sv[k].x0));
         }
-        out_scale[k] = c->fscale[sv[k].x0];
+        B.out_scale[k] = x0.fscale;
     }
-    if (iters == 0) {
-        TRY(xchg_join(c, keep_pending));
-        for (int k = 0; k < count; ++k) TRY(settle_source(c, sv[k].x0));    // (no launch to take a deferred source over)
+    if (B.iters == 0) {
+        TRY(xchg_join(c));
+        for (int k = 0; k < B.count; ++k) TRY(settle_source(c, sv[k].x0));    // (no launch to take a deferred source over)
         return FLUID_OK;
     }
-    for (int k = 0; k < count; ++k) TRY(materialize_zero(c, sv[k].x0));     // a pending increment rides along (TbBatch::x0_inc)
+    for (int k = 0; k < B.count; ++k) TRY(materialize_zero(c, sv[k].x0));     // a pending increment rides along (TbBatch::x0_inc)
+    return FLUID_OK;
+}
+
+// division modes, whether a deferred add_source rides in the first launch (else it is settled now), mode 3's tile minima
+int batch_plan(fluid_ctx* c, Batch& B)
+{
+    const Solve* sv = B.sv;
+    B.same_mode = B.all_mode4 = true;
+    for (int k = 0; k < B.count; ++k) {
+        B.cur[k] = sv[k].x;
+        B.nxt[k] = B.scratch[k];
+        B.plan[k].arg = sv[k].beta;
+        if (c->variant == fluid::JACOBI_TB) B.plan[k] = division_mode(c, sv[k].beta, sv[k].alpha);
+        B.same_mode = B.same_mode && B.plan[k].mode == B.plan[0].mode;
+        B.all_mode4 = B.all_mode4 && B.plan[k].mode == 4;
+    }
+    B.shape = sweep_shape(c, B.count);
     // a deferred add_source (op_add_source) rides in the first launch if that is a fused one of a shape that exists with the
-    // second store, the source is this solve's first guess and all solves of the launch agree; else it is settled now
-    bool add_src = c->src_of[sv[0].x0] != 0;
-    for (int k = 0; k < count; ++k)
-        add_src = add_src && c->src_of[sv[k].x0] == 1 + sv[k].x && c->src_dt[sv[k].x0] == c->src_dt[sv[0].x0] && !c->zero[sv[k].x] &&
-                  !c->pend[sv[k].x] && !c->src_of[sv[k].x] && ds == nullptr;
-    hipEvent_t stop;
-    TRY(timing_begin(c, FLUID_TIME_DIFFUSION, &stop));
-    const bool multi = c->nranks > 1;
-    int cur[3], nxt[3], divmode[3];
-    DivPlan plan[3];
-    bool same_mode = true, all_mode4 = true;
-    for (int k = 0; k < count; ++k) {
-        cur[k] = sv[k].x;
-        nxt[k] = kScratch[k];
-        plan[k].arg = sv[k].beta;
-        if (c->variant == fluid::JACOBI_TB) plan[k] = division_mode(c, sv[k].beta, sv[k].alpha);
-        divmode[k] = plan[k].mode;
-        same_mode = same_mode && divmode[k] == divmode[0];
-        all_mode4 = all_mode4 && divmode[k] == 4;
+    // second store, the source is this solve's first guess and all solves agree.  That depth: what the loop picks when
+    // nothing is short (a short reach there exchanges first, or shortens the launch and the source is settled there)
+    const FieldState& x00 = c->field[sv[0].x0];
+    bool add_src = x00.src_of != 0 && B.ds == nullptr && B.same_mode;
+    for (int k = 0; k < B.count; ++k) {
+        const FieldState &x = c->field[sv[k].x], &x0 = c->field[sv[k].x0];
+        add_src = add_src && x0.src_of == 1 + sv[k].x && x0.src_dt == x00.src_dt && !x.zero && !x.pend && !x.src_of;
     }
-    {
-        const bool canonical0 = c->st == fluid::STORAGE_F16;
-        const long long cells0 = (long long)(c->nranks > 1 ? c->min_slab : c->n) * c->n;
-        const bool small0 = (canonical0 ? (long long)c->n * c->n : cells0 * count) < c->tb_min_cells;
-        // the depth of the first launch: what the loop below will pick when nothing is short (a short reach there exchanges
-        // first, or shortens the launch -- in which case the source is settled there, before that launch)
-        const int T0 = pick_sweeps(c, iters, iters, canonical0, small0, cells0, all_mode4);
-        add_src = add_src && same_mode && fluid::jacobi_tb_addsrc_exists(T0, divmode[0], c->tb_nv);
-        if (!add_src)
-            for (int k = 0; k < count; ++k)
-                if (c->src_of[sv[k].x0]) {
-                    TRY(xchg_join(c, keep_pending));                        // (its kernel touches rows that may be on their way)
-                    TRY(settle_source(c, sv[k].x0));
-                }
-    }
+    B.add_src = add_src && fluid::jacobi_tb_addsrc_exists(pick_sweeps(c, B.iters, B.iters, B.shape, B.all_mode4), B.plan[0].mode, c->tb_nv);
+    if (!B.add_src)
+        for (int k = 0; k < B.count; ++k)
+            if (c->field[sv[k].x0].src_of) {
+                TRY(xchg_join(c));                        // (its kernel touches rows that may be on their way)
+                TRY(settle_source(c, sv[k].x0));
+            }
     // division mode 3 needs |x0| >= beta * 2^-72 wherever it is used: minima of |x0| per tile, once per solve (x0 does not
     // change during it), over the rows of x0 that are valid here; tiles beyond them read 0 = "divide the long way"
-    const size_t tile_words = (size_t)fluid::tile_rows(c->n) * fluid::tile_pitch(c->n);
-    {
-        fluid::TileBatch tb{};
-        int m = 0, valid = kEverywhere;
-        for (int k = 0; k < count; ++k)
-            if (divmode[k] == 3) {
-                tb.field[m] = c->f[sv[k].x0];
-                tb.tiles[m] = c->tiles + (size_t)(scratch_base + k) * tile_words;      // a solve's tiles go with its scratch field: a
-                                                                                        // batch on the second stream has slots of its own
-                valid = std::min(valid, c->nranks > 1 ? c->reach[sv[k].x0] : kEverywhere);
-                ++m;
-            }
-        if (m > 0) {
-            TRY(xchg_join(c, keep_pending));
-            if (c->nranks > 1)
-                HIP_TRY(hipMemsetAsync(c->tiles + (size_t)scratch_base * tile_words, 0, (size_t)count * tile_words * sizeof(unsigned), c->stream));
-            int lo, hi;
-            rows(c, std::min(valid, c->n), &lo, &hi);
-            fluid::launch_tile_min_abs(c->stream, c->st, tb, m, c->pitch, c->n, lo, hi, fluid::tile_pitch(c->n));
+    fluid::TileBatch tb{};
+    int m = 0, valid = kEverywhere;
+    for (int k = 0; k < B.count; ++k)
+        if (B.plan[k].mode == 3) {
+            tb.field[m] = c->ptr(sv[k].x0);
+            tb.tiles[m] = solve_tiles(c, B.scratch_base + k);
+            valid = std::min(valid, c->nranks > 1 ? c->field[sv[k].x0].reach : kEverywhere);
+            ++m;
         }
+    if (m == 0) return FLUID_OK;
+    TRY(xchg_join(c));
+    if (c->nranks > 1)
+        HIP_TRY(hipMemsetAsync(solve_tiles(c, B.scratch_base), 0,
+                               (size_t)B.count * fluid::tile_rows(c->n) * fluid::tile_pitch(c->n) * sizeof(unsigned), c->stream));
+    int lo, hi;
+    rows(c, std::min(valid, c->n), &lo, &hi);
+    fluid::launch_tile_min_abs(c->stream, c->st, tb, m, c->pitch, c->n, lo, hi, fluid::tile_pitch(c->n));
+    return FLUID_OK;
+}
+
+// sweeps the batch can run right now: x is read one row further out than x0
+int batch_reach(const fluid_ctx* c, const Batch& B)
+{
+    int r = kEverywhere;
+    for (int k = 0; k < B.count; ++k) r = std::min(r, std::min(c->field[B.cur[k]].reach, c->field[B.sv[k].x0].reach + 1));
+    return r;
+}
+
+// the fused kernel's arguments for solves [first, last); divsrc / addsrc: the launch forms (and stores) the right-hand sides
+fluid::TbBatch fill_batch(const fluid_ctx* c, const Batch& B, int first, int last, bool divsrc, bool addsrc)
+{
+    fluid::TbBatch bt{};
+    for (int j = first; j < last; ++j) {
+        const int q = j - first;
+        const DivPlan& p = B.plan[j];
+        const FieldState& x0 = c->field[B.sv[j].x0];
+        bt.x[q] = c->ptr(B.cur[j]);
+        bt.x0[q] = x0.ptr;
+        bt.out[q] = c->ptr(B.nxt[j]);
+        bt.alpha[q] = B.sv[j].alpha;
+        bt.beta[q] = p.arg;
+        bt.yd[q] = p.yd;
+        bt.hi[q] = p.hi;
+        bt.lo[q] = p.lo;
+        bt.tiles[q] = p.mode == 3 ? solve_tiles(c, B.scratch_base + j) : nullptr;
+        bt.tile_thr[q] = p.tile_thr;
+        bt.b[q] = B.sv[j].b;
+        bt.x_zero[q] = c->field[B.cur[j]].zero ? 1 : 0;
+        bt.x0_inc[q] = x0.pend && !addsrc && !divsrc ? x0.pend_inc : -0.0f;     // x + (-0) is x for every x
+        if (addsrc) bt.div[q] = c->ptr(B.sum[j]);
     }
-    auto reach_now = [&]() {
-        int r = kEverywhere;
-        for (int k = 0; k < count; ++k) r = std::min(r, std::min(c->reach[cur[k]], c->reach[sv[k].x0] + 1));
-        return r;
-    };
-    int r = multi ? reach_now() : kEverywhere;            // sweeps possible right now
-    // FLUID_PARAM_TB_MIN_CELLS: slabs below it run one launch per sweep.  Default 0: with 2-column
-    // lanes the fused kernel wins at every size measured (32^2 .. 16384^2) -- tiny grids are bound by
-    // launch latency and it needs 5 launches per solve instead of 40.
-    // fp16 storage rounds once per launch, so there the launch schedule is part of the result: it
-    // must not depend on how the grid is split, how deep the ghost zones are or how solves are
-    // batched.  It is derived from the global problem alone and a short reach triggers an early
-    // exchange instead of a shorter launch.  (fp32 results do not depend on the schedule.)
-    const bool canonical = c->st == fluid::STORAGE_F16;
-    // what a rank sweeps (the whole grid on one GPU).  From the base slab height, not this rank's own (ranks differ by a
-    // row when N does not divide evenly), so that every rank takes the same size-dependent decisions.  (Exchanges are
-    // driven by `reach`, which every sweep consumes alike whatever the launch depth, so they would pair up regardless.)
-    const long long slab_cells = (long long)(c->nranks > 1 ? c->min_slab : c->n) * c->n;
-    const bool small = (canonical ? (long long)c->n * c->n : slab_cells * count) < c->tb_min_cells;
-    bool joined = false;                  // this batch's stream has waited for the exchange in flight (if any)
-    for (int k = 0; k < iters;) {
-        const int remaining = iters - k;
-        auto pick = [&](int room) { return pick_sweeps(c, remaining, room, canonical, small, slab_cells, all_mode4); };
-        const int wantT = canonical ? pick(remaining) : 1;     // slabs with fp16 storage keep halo >= 8 (fluid_create_ex)
-        if (r < wantT) {
-            const int depth = std::max(wantT, std::min(c->halo, remaining + final_reach));
-            std::vector<int> ids;
-            for (int j = 0; j < count; ++j) {
-                ids.push_back(cur[j]);
-                if (c->reach[sv[j].x0] < depth - 1) ids.push_back(sv[j].x0);
-            }
-            TRY(xchg_join(c, keep_pending));                                  // (the caller's exchange first, if it is still out)
-            TRY(need_list(c, ids, depth, /*async=*/true));                    // the launch below is split around it
-            keep_pending = false;                                             // (this one is this batch's own)
-            joined = false;
-            r = reach_now();
+    bt.count = last - first;
+    bt.tile_pitch = fluid::tile_pitch(c->n);
+    if (addsrc) bt.div_scale = c->field[B.sv[first].x0].src_dt;
+    if (divsrc) {
+        bt.x[0] = c->ptr(B.ds->u);
+        bt.x0[0] = c->ptr(B.ds->v);
+        bt.div[0] = c->ptr(B.sv[0].x0);
+        bt.div_scale = B.ds->scale;
+    }
+    return bt;
+}
+
+// strip height of the two edge windows (ghost columns cost ~1.6x per row: shorter strips there keep the launch balanced)
+int edge_rows(const fluid_ctx* c, int T, int rb) { return std::max(2 * T, rb * (c->tb_edge_pct > 0 ? c->tb_edge_pct : 100) / 100); }
+
+// Closed-form strip height of a fused launch of m solves, T sweeps, rows_n output rows (tools/tb_sweep.py on MI355X): the
+// kernel hides its latencies only behind other waves, so every block should be resident at once (a 256-thread block is one
+// wave per SIMD), in the tallest strips that allow (each pays 2T rows of pipeline fill): the smallest height whose blocks
+// fit 92 % of one round; grids too large for one round stop at 80 rows (160 for a batch; 192 at T = 16).
+int strip_rows(const fluid_ctx* c, int T, int m, long long rows_n)
+{
+    const int nv = c->tb_nv;
+    const int HL = (T + nv - 1) / nv, VS = 64 - 2 * HL;
+    const long long windows = ((c->n + nv - 1) / nv + VS - 1) / VS;
+    const long long inner = windows > 2 ? windows - 2 : 0, outer = windows - inner;
+    const int resident = nv == 2 ? (T >= 16 ? 2 : 4) : (T >= 8 ? 2 : 3);
+    const long long room = (long long)c->num_cu * resident * 92 / 100;
+    const int cap = T >= 16 ? 192 : (T >= 8 ? 80 : 96) * (m > 1 ? 2 : 1);
+    int rb = 2 * T;
+    for (; rb < cap; rb += 2) {
+        const long long si = (rows_n + rb - 1) / rb, se = (rows_n + edge_rows(c, T, rb) - 1) / edge_rows(c, T, rb);
+        if ((inner * ((si + 3) / 4) + outer * ((se + 3) / 4)) * m <= room) break;
+    }
+    // small grids: a launch lasts as long as one wave's march of rb + 2T rows, and the best height
+    // measured is about rows / 64 (2 at 128^2, 4 at 256^2, 8 at 512^2, 16 and more from 1024^2)
+    if (rows_n <= 1100) rb = std::max(2, std::min(rb, (int)(rows_n / 64) & ~1));
+    return rb;
+}
+
+// A fused launch of the sweep loop; strip height TB_ROWS, else the closed form as the run-time tuner's first candidate
+// (RbTuner).  While this stream owes the wait on an exchange in flight, the strips whose inputs are this slab's own rows --
+// output rows [own0 + T, own1 - T): T sweeps reach T rows -- go first and run while the halo rows travel; the strips next to
+// the inner edges wait for the exchange's event, in one launch.  Same arithmetic per cell whichever launch it falls into.
+int launch_fused(fluid_ctx* c, const fluid::TbBatch& bt, int T, int divmode, bool divsrc, bool addsrc, int lo, int hi)
+{
+    const bool owed = c->nranks > 1 && (c->xowed & stream_bit(c));
+    const int in_lo = owed && c->rank > 0 ? std::max(lo, c->own0 + T) : lo;
+    const int in_hi = owed && c->rank < c->nranks - 1 ? std::min(hi, c->own1 - T) : hi;
+    const bool split = owed && in_hi - in_lo >= 2 * T && (in_lo > lo || in_hi < hi);
+    for (int part = split ? 0 : 1; part < 2; ++part) {     // 0: the interior of a split launch; 1: the rest (or all)
+        const int plo = part ? lo : in_lo, phi = part ? hi : in_hi;
+        const int hole_lo = part && split ? in_lo : 0, hole_hi = part && split ? in_hi : 0;
+        if (part) TRY(xchg_join(c));
+        const long long rows_n = (phi - plo) - std::max(0, hole_hi - hole_lo);
+        int rb = c->tb_rows > 0 ? c->tb_rows : strip_rows(c, T, bt.count, rows_n);
+        int trial = -1;
+        unsigned long long key = 0;
+        if (c->tb_rows <= 0 && c->autotune) {
+            // (the two edge parts of a split launch: keyed by their rows, and as a shape of their own)
+            key = tune_key(c, T, bt.count + (divsrc ? 8 : 0) + (addsrc ? 16 : 0) + (hole_hi > hole_lo ? 32 : 0), divmode, rows_n);
+            rb = tune_pick(c, key, rb, T, rows_n, &trial);
         }
-        const int T = canonical ? wantT : pick(std::min(r, remaining));
-        if (add_src && k == 0 && !fluid::jacobi_tb_addsrc_exists(T, divmode[0], c->tb_nv)) {
-            add_src = false;                   // a shallower first launch than planned (short reach): the kernel of its own after all
-            if (!joined) TRY(xchg_join(c, keep_pending));
-            joined = true;
-            for (int j = 0; j < count; ++j) TRY(settle_source(c, sv[j].x0));
+        if (trial >= 0) TRY(tune_begin(c, key, trial));
+        fluid::launch_jacobi_tb(c->stream, c->st, T, divmode, c->tb_nv, bt, c->pitch, c->n, plo, phi, rb, std::min(rb, edge_rows(c, T, rb)),
+                                divsrc, addsrc, hole_lo, hole_hi);
+        if (trial >= 0) TRY(tune_end(c));
+    }
+    if (split) c->split_launches += 1;
+    return FLUID_OK;
+}
+
+// the state a launch of the sweep loop leaves: `r` rows past the slab valid (kEverywhere: one GPU); `first`: the solves' first
+void commit_launch(fluid_ctx* c, Batch& B, bool first, int r)
+{
+    if (B.ds && first && c->nranks > 1)             // the divergence exists where this launch stored it
+        c->field[B.sv[0].x0].reach = std::max(0, std::min(c->field[B.sv[0].x0].reach, r));
+    if (B.add_src && first) {
+        // the sums were stored out of place, on the rows this launch computed (+ the wall rows next to them): the
+        // right-hand side takes that buffer, the sum field the old one
+        for (int j = 0; j < B.count; ++j) {
+            trade(c, B.sv[j].x0, B.sum[j]);
+            wrote(c, B.sum[j], 0);
+            wrote(c, B.sv[j].x0, std::max(0, r));
+        }
+        B.add_src = false;
+    }
+    for (int j = 0; j < B.count; ++j) {
+        c->field[B.cur[j]].zero = false;             // from now on this buffer is just the other half of the ping-pong
+        wrote(c, B.nxt[j], r);
+        std::swap(B.cur[j], B.nxt[j]);
+    }
+}
+
+// the sweep loop: launches of T sweeps each, an exchange first whenever the valid rows run short
+int batch_sweep(fluid_ctx* c, Batch& B)
+{
+    const Solve* sv = B.sv;
+    const bool multi = c->nranks > 1, canonical = B.shape.canonical;
+    int r = multi ? batch_reach(c, B) : kEverywhere;
+    for (int k = 0; k < B.iters;) {
+        const int remaining = B.iters - k;
+        const int wantT = canonical ? pick_sweeps(c, remaining, remaining, B.shape, B.all_mode4) : 1;   // slabs with fp16 storage keep halo >= 8 (fluid_create_ex)
+        if (r < wantT) {
+            const int depth = std::max(wantT, std::min(c->halo, remaining + B.final_reach));
+            std::vector<int> ids;
+            for (int j = 0; j < B.count; ++j) {
+                ids.push_back(B.cur[j]);
+                if (c->field[sv[j].x0].reach < depth - 1) ids.push_back(sv[j].x0);
+            }
+            TRY(xchg_join(c));                                // (the caller's exchange first, if it is still out)
+            TRY(need_list(c, ids, depth, /*async=*/true));    // the launch below is split around it
+            r = batch_reach(c, B);
+        }
+        const int T = canonical ? wantT : pick_sweeps(c, remaining, std::min(r, remaining), B.shape, B.all_mode4);
+        if (B.add_src && k == 0 && !fluid::jacobi_tb_addsrc_exists(T, B.plan[0].mode, c->tb_nv)) {
+            B.add_src = false;                   // a shallower first launch than planned (short reach): the kernel of its own after all
+            TRY(xchg_join(c));
+            for (int j = 0; j < B.count; ++j) TRY(settle_source(c, sv[j].x0));
         }
         int lo, hi;
         rows(c, multi ? std::min(r - T, exchange_cap(c)) : 0, &lo, &hi);
         if (T == 1) {
-            const int v = c->variant == fluid::JACOBI_TB ? (small ? fluid::JACOBI_NAIVE : fluid::JACOBI_STREAM) : c->variant;
-            if (!joined) TRY(xchg_join(c, keep_pending));
-            joined = true;
-            for (int j = 0; j < count; ++j) TRY(materialize(c, cur[j], /*keep_scale=*/true));      // single-sweep kernels read x
-            for (int j = 0; j < count; ++j) TRY(settle(c, sv[j].x0, /*keep_scale=*/true));         // ... and x0 as it is in memory
-            for (int j = 0; j < count; ++j)
-                fluid::launch_jacobi(c->stream, c->st, v, c->f[cur[j]], c->f[sv[j].x0], c->f[nxt[j]], c->pitch, c->n, lo, hi,
+            // the single-sweep kernels, one launch per solve, read x and x0 as they are in memory
+            const int v = c->variant == fluid::JACOBI_TB ? (B.shape.small ? fluid::JACOBI_NAIVE : fluid::JACOBI_STREAM) : c->variant;
+            TRY(xchg_join(c));
+            for (int j = 0; j < B.count; ++j) TRY(materialize(c, B.cur[j], /*keep_scale=*/true));
+            for (int j = 0; j < B.count; ++j) TRY(settle(c, sv[j].x0, /*keep_scale=*/true));
+            for (int j = 0; j < B.count; ++j)
+                fluid::launch_jacobi(c->stream, c->st, v, c->ptr(B.cur[j]), c->ptr(sv[j].x0), c->ptr(B.nxt[j]), c->pitch, c->n, lo, hi,
                                      sv[j].alpha, sv[j].beta, sv[j].b);
             if (c->timing) {
-                c->launches += count;
-                c->field_launches += count;
+                c->launches += B.count;
+                c->field_launches += B.count;
             }
         } else {
             // one launch per group of solves that share a division mode (normally: all of them)
-            for (int first = 0; first < count;) {
-                fluid::TbBatch bt{};
-                int m = 0;
-                int last = first;
-                for (int j = first; j < count && (same_mode || j == first); ++j, ++last) {
-                    bt.x[m] = c->f[cur[j]];
-                    bt.x0[m] = c->f[sv[j].x0];
-                    bt.out[m] = c->f[nxt[j]];
-                    bt.alpha[m] = sv[j].alpha;
-                    bt.beta[m] = plan[j].arg;
-                    bt.yd[m] = plan[j].yd;
-                    bt.hi[m] = plan[j].hi;
-                    bt.lo[m] = plan[j].lo;
-                    bt.tiles[m] = divmode[j] == 3 ? c->tiles + (size_t)(scratch_base + j) * tile_words : nullptr;
-                    bt.tile_thr[m] = plan[j].tile_thr;
-                    bt.b[m] = sv[j].b;
-                    bt.x_zero[m] = c->zero[cur[j]] ? 1 : 0;
-                    bt.x0_inc[m] = c->pend[sv[j].x0] ? c->pend_inc[sv[j].x0] : -0.0f;     // x + (-0) is x for every x
-                    ++m;
-                }
-                bt.count = m;
-                bt.tile_pitch = fluid::tile_pitch(c->n);
-                const bool divsrc = ds != nullptr && k == 0;
-                const bool addsrc = add_src && k == 0;
-                if (addsrc) {
-                    for (int j = first, q = 0; j < last; ++j, ++q) {
-                        bt.div[q] = c->f[kSum[j]];
-                        bt.x0_inc[q] = -0.0f;
-                    }
-                    bt.div_scale = c->src_dt[sv[first].x0];
-                }
-                if (divsrc) {
-                    bt.x[0] = c->f[ds->u];
-                    bt.x0[0] = c->f[ds->v];
-                    bt.div[0] = c->f[sv[0].x0];
-                    bt.div_scale = ds->scale;
-                    bt.x0_inc[0] = -0.0f;
-                }
-                const int edge_pct = c->tb_edge_pct > 0 ? c->tb_edge_pct : 100;
-                auto edge_rows = [&](int r) { return std::max(2 * T, r * edge_pct / 100); };
-                // this launch on output rows [lo_, hi_) (the whole launch, or one part of a launch split around an exchange)
-                auto launch_rows = [&](int lo_, int hi_, int hole_lo = 0, int hole_hi = 0) -> int {
-                    int rb = c->tb_rows;
-                    if (rb <= 0) {
-                        // auto (tools/tb_sweep.py on MI355X): the kernel hides its latencies only behind other
-                        // waves, so it wants every block resident at once -- a 256-thread block is one wave per
-                        // SIMD, tb_waves_per_simd blocks fit a CU -- and then the tallest strips that still
-                        // allow (each strip pays 2T rows of pipeline fill).  Smallest strip height whose
-                        // non-empty blocks fit 92 % of one round; grids too large for one round stop at 80
-                        // rows (160 for a batch; 192 at T = 16), past which more strips win again.
-                        const int nv = c->tb_nv;
-                        const int HL = (T + nv - 1) / nv, VS = 64 - 2 * HL;
-                        const long long windows = ((c->n + nv - 1) / nv + VS - 1) / VS;
-                        const int resident = nv == 2 ? (T >= 16 ? 2 : 4) : (T >= 8 ? 2 : 3);
-                        const long long room = (long long)c->num_cu * resident * 92 / 100;
-                        const long long rows_n = (hi_ - lo_) - std::max(0, hole_hi - hole_lo);
-                        auto blocks = [&](int r) {
-                            const long long si = (rows_n + r - 1) / r, se = (rows_n + edge_rows(r) - 1) / edge_rows(r);
-                            const long long inner = windows > 2 ? windows - 2 : 0, outer = windows - inner;
-                            return (inner * ((si + 3) / 4) + outer * ((se + 3) / 4)) * m;
-                        };
-                        const int cap = T >= 16 ? 192 : (T >= 8 ? 80 : 96) * (m > 1 ? 2 : 1);
-                        rb = 2 * T;
-                        while (rb < cap && blocks(rb) > room) rb += 2;
-                        // small grids: a launch lasts as long as one wave's march of rb + 2T rows, and the best height
-                        // measured is about rows / 64 (2 at 128^2, 4 at 256^2, 8 at 512^2, 16 and more from 1024^2)
-                        if (rows_n <= 1100) rb = std::max(2, std::min(rb, (int)(rows_n / 64) & ~1));
-                    }
-                    // ... and that closed form is only the first candidate of the run-time tuner (see RbTuner)
-                    int trial = -1;
-                    unsigned long long key = 0;
-                    if (c->tb_rows <= 0 && c->autotune) {
-                        // (the two edge parts of a split launch: keyed by their rows, and as a shape of their own)
-                        const long long rows_k = (hi_ - lo_) - std::max(0, hole_hi - hole_lo);
-                        key = tune_key(c, T, m + (divsrc ? 8 : 0) + (addsrc ? 16 : 0) + (hole_hi > hole_lo ? 32 : 0), divmode[first], rows_k);
-                        rb = tune_pick(c, key, rb, T, rows_k, &trial);
-                    }
-                    // edge windows (ghost columns) cost ~1.6x per row: shorter strips there keep the launch balanced
-                    const int rb_edge = std::min(rb, edge_rows(rb));
-                    if (trial >= 0) TRY(tune_begin(c, key, trial));
-                    fluid::launch_jacobi_tb(c->stream, c->st, T, divmode[first], c->tb_nv, bt, c->pitch, c->n, lo_, hi_, rb, rb_edge, divsrc, addsrc,
-                                            hole_lo, hole_hi);
-                    if (trial >= 0) TRY(tune_end(c));
-                    return FLUID_OK;
-                };
-                // An exchange is still in flight (issued async just above, or by the caller): the strips whose inputs are this
-                // slab's own rows -- output rows [own0 + T, own1 - T): T sweeps reach T rows -- go first and run while the halo
-                // rows travel; the strips next to the slab's inner edges wait for the exchange's event.  Same arithmetic per
-                // cell whichever launch it falls into.
-                int in_lo = lo, in_hi = hi;
-                if (c->xpend && !joined && multi) {
-                    if (c->rank > 0) in_lo = std::max(lo, c->own0 + T);
-                    if (c->rank < c->nranks - 1) in_hi = std::min(hi, c->own1 - T);
-                }
-                if (c->xpend && !joined && in_hi - in_lo >= 2 * T && (in_lo > lo || in_hi < hi)) {
-                    TRY(launch_rows(in_lo, in_hi));
-                    TRY(xchg_join(c, keep_pending));
-                    TRY(launch_rows(lo, hi, in_lo, in_hi));              // both edge parts in one launch
-                    c->split_launches += 1;
-                } else {
-                    if (!joined) TRY(xchg_join(c, keep_pending));
-                    TRY(launch_rows(lo, hi));
-                }
-                joined = true;
+            for (int first = 0, last; first < B.count; first = last) {
+                last = B.same_mode ? B.count : first + 1;
+                const bool divsrc = B.ds != nullptr && k == 0, addsrc = B.add_src && k == 0;
+                TRY(launch_fused(c, fill_batch(c, B, first, last, divsrc, addsrc), T, B.plan[first].mode, divsrc, addsrc, lo, hi));
                 if (c->timing) {
                     c->launches += 1;
-                    c->field_launches += m;
+                    c->field_launches += last - first;
                 }
-                first = last;
             }
         }
         r = multi ? std::min(r - T, exchange_cap(c)) : kEverywhere;
-        if (ds && k == 0 && multi) c->reach[sv[0].x0] = std::max(0, std::min(c->reach[sv[0].x0], r));   // the divergence exists where this launch stored it
-        if (add_src && k == 0) {
-            // the sums were stored out of place, on the rows this launch computed (+ the wall rows next to them): the
-            // right-hand side takes that buffer, the scratch field the old one
-            for (int j = 0; j < count; ++j) {
-                const int x0 = sv[j].x0;
-                std::swap(c->f[x0], c->f[kSum[j]]);
-                c->zero[kSum[j]] = false;
-                wrote(c, kSum[j], 0);
-                wrote(c, x0, std::max(0, r));
-            }
-            add_src = false;
-        }
-        for (int j = 0; j < count; ++j) {
-            c->zero[cur[j]] = false;       // from now on this buffer is just the other half of the ping-pong
-            c->zero[nxt[j]] = false;
-            wrote(c, nxt[j], r);
-            std::swap(cur[j], nxt[j]);
-        }
+        commit_launch(c, B, k == 0, r);
         k += T;
     }
+    return FLUID_OK;
+}
+
+int op_diffuse_batch(fluid_ctx* c, const Solve* sv, int count, int iters, int final_reach = 0, const DivSource* ds = nullptr,
+                     int scratch_base = 0)
+{
+    Batch B{sv, count, iters, final_reach, ds, scratch_base};
+    TRY(batch_prepare(c, B));
+    if (iters == 0) return FLUID_OK;
+    hipEvent_t stop;
+    TRY(timing_begin(c, FLUID_TIME_DIFFUSION, &stop));
+    TRY(batch_plan(c, B));
+    TRY(batch_sweep(c, B));
     HIP_TRY(hipGetLastError());
+    // commit: a result that ended in the scratch buffer takes it over (its record with it)
     for (int j = 0; j < count; ++j) {
-        if (cur[j] != sv[j].x) {
-            std::swap(c->f[sv[j].x], c->f[kScratch[j]]);
-            std::swap(c->reach[sv[j].x], c->reach[kScratch[j]]);
-            std::swap(c->pend[sv[j].x], c->pend[kScratch[j]]);
-            std::swap(c->pend_inc[sv[j].x], c->pend_inc[kScratch[j]]);
-        }
-        wrote(c, kScratch[j], 0);
-        c->fscale[sv[j].x] = out_scale[j];
+        if (B.cur[j] != sv[j].x) trade(c, sv[j].x, B.scratch[j]);
+        wrote(c, B.scratch[j], 0);
+        c->field[sv[j].x].fscale = B.out_scale[j];
     }
     return timing_end(c, stop, iters * count);
 }
@@ -977,7 +1002,7 @@ int op_diffuse(fluid_ctx* c, int b, int x, int x0, float alpha, float beta, int 
 // when the reach exceeds what a neighbour can supply it gathers whole fields.
 // The bound is a host decision, i.e. a pipeline drain: vmax_begin() only
 // enqueues (reduction kernel, device-side all-reduce, copy to pinned memory),
-// so the caller can put independent work behind it before advect_halo() waits.
+// so the caller can put independent work behind it before advect_rows() waits.
 // `have_max`: the gradient subtraction that has just produced (u, v) left their maximum in the device word already
 // (op_subtract_gradient with_max)
 int vmax_begin(fluid_ctx* c, int u, int v, bool have_max = false)
@@ -986,7 +1011,7 @@ int vmax_begin(fluid_ctx* c, int u, int v, bool have_max = false)
     if (!have_max) {
         TRY(materialize(c, {u, v}));
         HIP_TRY(hipMemsetAsync(c->d_scalar, 0, sizeof(unsigned), c->stream));
-        fluid::launch_absmax2(c->stream, c->st, c->f[u], c->f[v], c->pitch, c->n, c->own0, c->own1, c->d_scalar);
+        fluid::launch_absmax2(c->stream, c->st, c->ptr(u), c->ptr(v), c->pitch, c->n, c->own0, c->own1, c->d_scalar);
     }
     TRY(exchange(c, FLUID_XCHG_MAX_BEGIN, {}, 0));       // in-place MAX over ranks on the device scalar
     HIP_TRY(hipMemcpyAsync(c->h_scalar, c->d_scalar, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
@@ -994,20 +1019,20 @@ int vmax_begin(fluid_ctx* c, int u, int v, bool have_max = false)
     return FLUID_OK;
 }
 
-int advect_halo(fluid_ctx* c, std::initializer_list<int> sources, float dt0)
+// slabs: waits for the bound vmax_begin() enqueued (*vmax) and brings in the rows of `sources` an advection along it reads
+// (whole fields beyond a neighbour's reach) unless the `have` rows already there cover them -- *fetched: rows came in here
+int advect_rows(fluid_ctx* c, std::initializer_list<int> sources, float dt0, int have, float* vmax, bool* fetched)
 {
-    if (c->nranks == 1) return FLUID_OK;
     HIP_TRY(hipEventSynchronize(c->scalar_ready));
-    float vmax = 0.f;
-    std::memcpy(&vmax, c->h_scalar, sizeof vmax);
-    TRY(exchange(c, FLUID_XCHG_MAX_END, {}, 0, &vmax));  // transports that reduce on the host finish here
-    const double reach = std::ceil((double)std::fabs(dt0) * (double)vmax) + 2.0;
-    if (!(reach <= (double)exchange_cap(c))) {     // also catches NaN/inf
-        TRY(exchange(c, FLUID_XCHG_GATHER, sources, 0));
-        for (int f : sources) c->reach[f] = kEverywhere;
-        return FLUID_OK;
-    }
-    return need(c, sources, (int)reach);
+    std::memcpy(vmax, c->h_scalar, sizeof *vmax);
+    TRY(exchange(c, FLUID_XCHG_MAX_END, {}, 0, vmax));  // transports that reduce on the host finish here
+    const double reach = std::ceil((double)std::fabs(dt0) * (double)*vmax) + 2.0;
+    *fetched = !(have > 0 && reach <= (double)have);
+    if (!*fetched) return FLUID_OK;
+    if (reach <= (double)exchange_cap(c)) return need(c, sources, (int)reach);
+    TRY(exchange(c, FLUID_XCHG_GATHER, sources, 0));     // (also NaN / inf)
+    for (int f : sources) c->field[f].reach = kEverywhere;
+    return FLUID_OK;
 }
 
 // vmax_begin() has been enqueued; `run` enqueues the advection of `sources` (FluidSequential.c:107-141) along that velocity.
@@ -1030,26 +1055,11 @@ int advect_bounded(fluid_ctx* c, int slot, std::initializer_list<int> sources, f
             TRY(run());
         }
     }
-    HIP_TRY(hipEventSynchronize(c->scalar_ready));
     float vmax = 0.f;
-    std::memcpy(&vmax, c->h_scalar, sizeof vmax);
-    TRY(exchange(c, FLUID_XCHG_MAX_END, {}, 0, &vmax));  // transports that reduce on the host finish here
-    const double reach = std::ceil((double)std::fabs(dt0) * (double)vmax) + 2.0;
+    bool fetched = false;
+    TRY(advect_rows(c, sources, dt0, guess, &vmax, &fetched));
     c->vmax_prev[slot] = std::isfinite(vmax) ? vmax : -1.0f;
-    if (guess > 0 && reach <= (double)guess) return FLUID_OK;
-    if (!(reach <= (double)exchange_cap(c))) {     // also catches NaN/inf
-        TRY(exchange(c, FLUID_XCHG_GATHER, sources, 0));
-        for (int f : sources) c->reach[f] = kEverywhere;
-    } else {
-        TRY(need(c, sources, (int)reach));
-    }
-    return run();
-}
-
-int advect_prepare(fluid_ctx* c, std::initializer_list<int> sources, int u, int v, float dt0)
-{
-    TRY(vmax_begin(c, u, v));
-    return advect_halo(c, sources, dt0);
+    return fetched ? run() : FLUID_OK;
 }
 
 int op_advect(fluid_ctx* c, int b, int d, int d0, int u, int v, float dt)
@@ -1057,9 +1067,8 @@ int op_advect(fluid_ctx* c, int b, int d, int d0, int u, int v, float dt)
     if (d == d0 || d == u || d == v) return fail(FLUID_E_INVALID, "advect: output must not alias an input");
     const float dt0 = dt * (float)c->n;
     TRY(materialize(c, {d0, u, v}));
-    c->zero[d] = false;
     TIMED(c, FLUID_TIME_ADVECTION,
-          fluid::launch_advect(c->stream, c->st, c->f[d], c->f[d0], c->f[u], c->f[v], c->pitch, c->n, c->own0, c->own1, dt0, b));
+          fluid::launch_advect(c->stream, c->st, c->ptr(d), c->ptr(d0), c->ptr(u), c->ptr(v), c->pitch, c->n, c->own0, c->own1, dt0, b));
     wrote(c, d, 0);
     return FLUID_OK;
 }
@@ -1072,10 +1081,8 @@ int op_advect2(fluid_ctx* c, int ba, int da, int d0a, int bb, int db, int d0b, i
     if (da == db) return fail(FLUID_E_INVALID, "advect: outputs must be distinct");
     const float dt0 = dt * (float)c->n;
     TRY(materialize(c, {d0a, d0b, u, v}));
-    c->zero[da] = false;
-    c->zero[db] = false;
     TIMED(c, FLUID_TIME_ADVECTION,
-          fluid::launch_advect2(c->stream, c->st, c->f[da], c->f[d0a], ba, c->f[db], c->f[d0b], bb, c->f[u], c->f[v], c->pitch,
+          fluid::launch_advect2(c->stream, c->st, c->ptr(da), c->ptr(d0a), ba, c->ptr(db), c->ptr(d0b), bb, c->ptr(u), c->ptr(v), c->pitch,
                                 c->n, c->own0, c->own1, dt0));
     wrote(c, da, 0);
     wrote(c, db, 0);
@@ -1101,11 +1108,10 @@ int op_divergence(fluid_ctx* c, int u, int v, int p, int div, int want = 0, floa
     rows(c, reach, &lo, &hi);
     // p = 0 everywhere (FluidSequential.c:153 + set_bnd(0,p)): marked, not written
     TIMED(c, FLUID_TIME_DIVERGENCE,
-          fluid::launch_divergence(c->stream, c->st, c->f[u], c->f[v], c->f[p], c->f[div], c->pitch, c->n, lo, hi, h,
+          fluid::launch_divergence(c->stream, c->st, c->ptr(u), c->ptr(v), c->ptr(p), c->ptr(div), c->pitch, c->n, lo, hi, h,
                                    /*write_p=*/0, pscale));
-    c->zero[div] = false;
     wrote(c, div, reach);
-    c->fscale[div] = pscale;
+    c->field[div].fscale = pscale;
     mark_zero(c, p);
     return FLUID_OK;
 }
@@ -1121,8 +1127,8 @@ int op_subtract_gradient(fluid_ctx* c, int u, int v, int p, bool with_max = fals
     TRY(need(c, {p}, 1));
     with_max = with_max && c->nranks > 1 && c->d_partials;
     TIMED(c, FLUID_TIME_PROJECTION,
-          fluid::launch_subtract_gradient(c->stream, c->st, c->f[u], c->f[v], c->f[p], c->pitch, c->n, c->own0, c->own1, h,
-                                          c->d_partials, with_max ? c->d_scalar : nullptr, 1.0f / c->fscale[p]));
+          fluid::launch_subtract_gradient(c->stream, c->st, c->ptr(u), c->ptr(v), c->ptr(p), c->pitch, c->n, c->own0, c->own1, h,
+                                          c->d_partials, with_max ? c->d_scalar : nullptr, 1.0f / c->field[p].fscale));
     wrote(c, u, 0);
     wrote(c, v, 0);
     return FLUID_OK;
@@ -1140,10 +1146,9 @@ int op_gradient_advect(fluid_ctx* c, int u, int v, int p, int b, int d, int d0, 
     const float h = 1.0f / (float)c->n;
     TRY(materialize(c, {u, v, d0}));
     TRY(materialize(c, p, /*keep_scale=*/true));
-    c->zero[d] = false;
     TIMED(c, FLUID_TIME_PROJECTION,
-          fluid::launch_gradient_advect(c->stream, c->st, c->f[u], c->f[v], c->f[p], c->f[d], c->f[d0], c->pitch, c->n, c->own0,
-                                        c->own1, h, dt * (float)c->n, b, 1.0f / c->fscale[p]));
+          fluid::launch_gradient_advect(c->stream, c->st, c->ptr(u), c->ptr(v), c->ptr(p), c->ptr(d), c->ptr(d0), c->pitch, c->n, c->own0,
+                                        c->own1, h, dt * (float)c->n, b, 1.0f / c->field[p].fscale));
     wrote(c, u, 0);
     wrote(c, v, 0);
     wrote(c, d, 0);
@@ -1175,11 +1180,10 @@ struct AdvectAfter {
 bool divergence_fuses(fluid_ctx* c, int iters, int reach)
 {
     if (c->variant != fluid::JACOBI_TB || c->tb_nv != 2 || !c->fuse_divergence || iters < 8) return false;
-    const bool canonical = c->st == fluid::STORAGE_F16;
-    const long long slab_cells = (long long)(c->nranks > 1 ? c->min_slab : c->n) * c->n;
-    if ((canonical ? (long long)c->n * c->n : slab_cells) < c->tb_min_cells) return false;
+    const SweepShape shape = sweep_shape(c, 1);
+    if (shape.small) return false;
     const int room = c->nranks > 1 ? std::min(reach + 1, iters) : iters;        // sweeps the first launch may fuse (op_diffuse_batch)
-    if (room < 8 || pick_sweeps(c, iters, room, canonical, false, slab_cells, true) < 8) return false;
+    if (room < 8 || pick_sweeps(c, iters, room, shape, true) < 8) return false;
     return division_mode(c, 4.0f, 1.0f).mode == 4;
 }
 
@@ -1188,34 +1192,30 @@ int project(fluid_ctx* c, int u, int v, int p, int div, int iters, const AdvectA
 {
     // rows past the slab on which the divergence is wanted (so that the solve needs no exchange of its own), as op_divergence
     const int reach = c->nranks > 1 ? std::max(0, std::min(std::min(iters, c->halo - 1), exchange_cap(c) - 1)) : 0;
-    if (divergence_fuses(c, iters, reach)) {
-        // computeDivergenceAndPressure (FluidSequential.c:143-158) inside the solve's first launch: p = 0 is a mark, the
-        // divergence is produced row by row as that launch's right-hand side and stored, ghost cells included
+    // fused: computeDivergenceAndPressure (FluidSequential.c:143-158) inside the solve's first launch: p = 0 is a mark, the
+    // divergence is produced row by row as that launch's right-hand side and stored, ghost cells included
+    const bool fused = divergence_fuses(c, iters, reach);
+    const DivSource ds{u, v, (-0.5f * (1.0f / (float)c->n)) * c->pscale};
+    if (fused) {
         if (p == u || p == v || div == u || div == v || p == div)
             return fail(FLUID_E_INVALID, "divergence: outputs must not alias inputs");
         TRY(materialize(c, {u, v}));
         if (c->nranks > 1) TRY(need(c, {u, v}, reach + 1, /*async=*/true));      // joined by the solve's first launch
         mark_zero(c, p);
-        c->zero[div] = false;               // about to be overwritten entirely
-        c->pend[div] = false;
-        c->reach[div] = c->nranks > 1 ? reach : kEverywhere;   // what the first launch can form from (u, v); it records what it stored
-        const DivSource ds{u, v, (-0.5f * (1.0f / (float)c->n)) * c->pscale};
-        c->fscale[div] = c->pscale;         // (what the first launch stores; the solve is linear: p comes out with the same factor)
-        c->in_pressure_solve = true;
-        const int rc = op_diffuse(c, 0, p, div, 1.0f, 4.0f, iters, /*final_reach=*/1, &ds);
-        c->in_pressure_solve = false;
-        TRY(rc);
-        TRY(xchg_join(c));
-        wrote(c, div, 0);
-        c->fscale[div] = c->pscale;
-        if (then_advect) return op_gradient_advect(c, u, v, p, then_advect->b, then_advect->d, then_advect->d0, then_advect->dt);
-        return op_subtract_gradient(c, u, v, p, with_max);
+        wrote(c, div, reach);                 // about to be overwritten: as far as the first launch can form it from (u, v)
+        c->field[div].fscale = c->pscale;     // (what the first launch stores; the solve is linear: p comes out with the same factor)
+    } else {
+        TRY(op_divergence(c, u, v, p, div, std::min(iters, c->halo - 1), c->pscale));
     }
-    TRY(op_divergence(c, u, v, p, div, std::min(iters, c->halo - 1), c->pscale));
     c->in_pressure_solve = true;            // timing only: reported separately (fluid_timing::pressure_ms)
-    const int rc_solve = op_diffuse(c, 0, p, div, 1.0f, 4.0f, iters, /*final_reach=*/1);
+    const int rc_solve = op_diffuse(c, 0, p, div, 1.0f, 4.0f, iters, /*final_reach=*/1, fused ? &ds : nullptr);
     c->in_pressure_solve = false;
     TRY(rc_solve);
+    if (fused) {                            // (the first launch recorded the rows it stored)
+        TRY(xchg_join(c));
+        wrote(c, div, 0);
+        c->field[div].fscale = c->pscale;
+    }
     if (then_advect) return op_gradient_advect(c, u, v, p, then_advect->b, then_advect->d, then_advect->d0, then_advect->dt);
     return op_subtract_gradient(c, u, v, p, with_max);
 }
@@ -1290,12 +1290,10 @@ int full_step(fluid_ctx* c, float dt, float diff, float visc, int iters)
     // result (iters = 20 runs as 8 + 8 + 4 on one GPU and must do so here).
     int fill1 = 0, fill2 = 0;
     {
-        const bool canonical = c->st == fluid::STORAGE_F16;
-        const long long slab_cells = (long long)c->min_slab * c->n;
-        const bool small = (canonical ? (long long)c->n * c->n : slab_cells) < c->tb_min_cells;
+        const SweepShape shape = sweep_shape(c, 1);
         std::vector<int> launches;
         for (int left = iters; left > 0;) {
-            launches.push_back(pick_sweeps(c, left, left, canonical, small, slab_cells, /*all_mode4=*/false));
+            launches.push_back(pick_sweeps(c, left, left, shape, /*all_mode4=*/false));
             left -= launches.back();
         }
         // about eight sweeps behind each reduction (whole launches; single-sweep kernels: eight launches)
@@ -1315,9 +1313,10 @@ int full_step(fluid_ctx* c, float dt, float diff, float visc, int iters)
         // could not agree on.  It ping-pongs with TMP2, the velocity path with TMP0 / TMP1.
         HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
         HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
+        c->xowed = (c->xowed & 1u) ? 3u : 0u;       // stream2 now runs behind every wait of the main stream: it owes what that owes
         hipStream_t main_stream = c->stream;
         c->stream = c->stream2;
-        const int rc_dens = op_diffuse_batch(c, all + 2, 1, iters, 0, nullptr, /*scratch_base=*/2, /*keep_pending=*/true);
+        const int rc_dens = op_diffuse_batch(c, all + 2, 1, iters, 0, nullptr, /*scratch_base=*/2);
         hipError_t e_join = rc_dens == FLUID_OK ? hipEventRecord(c->ev_join, c->stream2) : hipSuccess;
         c->stream = main_stream;
         TRY(rc_dens);
@@ -1359,12 +1358,12 @@ int copy_rows(fluid_ctx* c, int field, float* host, const float* chost, int row_
     if (row_lo == row_hi) return FLUID_OK;
     // a download of a field kept scaled (fp16 storage: pressure, divergence) divides on the host, in float: exact, where a
     // pass over the fp16 field would round the plain values into fp16's subnormals again
-    const float host_scale = (!to_device && c->st != fluid::STORAGE_F32) ? 1.0f / c->fscale[field] : 1.0f;
+    const float host_scale = (!to_device && c->st != fluid::STORAGE_F32) ? 1.0f / c->field[field].fscale : 1.0f;
     TRY(materialize(c, field, /*keep_scale=*/host_scale != 1.0f));
     char* dev = static_cast<char*>(c->row(field, row_lo)) + (size_t)XOFF * c->esz;
     const size_t rows = (size_t)(row_hi - row_lo), w = (size_t)c->w;
     const size_t dp = (size_t)c->pitch * c->esz;
-    if (to_device) c->reach[field] = 0;     // the caller vouches only for its own rows
+    if (to_device) c->field[field].reach = 0;     // the caller vouches only for its own rows
     if (c->st == fluid::STORAGE_F32) {
         const size_t hp = w * sizeof(float);
         if (to_device)
@@ -1460,7 +1459,6 @@ int fluid_create_ex(const fluid_config* cfg, fluid_ctx** out)
     c->esz = fluid::storage_bytes(c->st);
     c->field_bytes = c->field_floats * c->esz;
     c->variant = cfg->jacobi_variant;
-    for (float& f : c->fscale) f = 1.0f;
     if (c->st == fluid::STORAGE_F16 && n >= 16) {
         // 2^(floor(log2 N) - 2): h * pscale lies in (1/8, 1/4], so a scaled divergence is at most a quarter of the velocity
         // differences it is formed from -- no fp16 overflow that the plain field would not have had 2^12 earlier -- and the
@@ -1509,7 +1507,7 @@ int fluid_create_ex(const fluid_config* cfg, fluid_ctx** out)
         if (e != hipSuccess) return bail(fail(FLUID_E_HIP, "hipStreamCreate: %s", hipGetErrorString(e)));
         c->own_stream = true;
     }
-    for (int k = 0; k < FLUID_NFIELDS; ++k) c->f[k] = c->arena + (size_t)k * c->field_bytes;
+    for (int k = 0; k < FLUID_NFIELDS; ++k) c->field[k].ptr = c->arena + (size_t)k * c->field_bytes;
     auto hip_ok = [&](hipError_t e, const char* what) {
         if (e == hipSuccess) return true;
         rc = fail(e == hipErrorOutOfMemory ? FLUID_E_NOMEM : FLUID_E_HIP, "%s: %s", what, hipGetErrorString(e));
@@ -1632,7 +1630,7 @@ int fluid_field_ptr(fluid_ctx* c, int field, void** dev_ptr)
     if (!dev_ptr) return fail(FLUID_E_INVALID, "null pointer");
     if (c->in_halo_exchange) TRY(materialize_zero(c, field));
     else TRY(materialize(c, field));       // whoever asks for the address may read the memory
-    *dev_ptr = c->f[field];
+    *dev_ptr = c->ptr(field);
     return FLUID_OK;
 }
 
@@ -1677,8 +1675,7 @@ int fluid_fill(fluid_ctx* c, int field, float value)
     TRY(check_ctx(c));
     TRY(check_fields(c, {field}));
     if (value == 0.0f && !std::signbit(value)) {
-        HIP_TRY(hipMemsetAsync(c->f[field], 0, c->field_bytes, c->stream));
-        c->zero[field] = false;
+        HIP_TRY(hipMemsetAsync(c->ptr(field), 0, c->field_bytes, c->stream));
         wrote(c, field, kEverywhere);
         return FLUID_OK;
     }
@@ -1778,9 +1775,10 @@ int fluid_plan_sweeps(int N, int rows, int storage, int pressure_form, int iters
     c.field_bytes = (size_t)(N + 2) * fluid::pitch_for(N) * c.esz;
     c.tb_max_t = max_sweeps;
     c.tb_t16_min_cells = t16_min_cells;
+    const SweepShape shape{storage == FLUID_STORAGE_F16, false, (long long)rows * N};
     int k = 0;
     for (int left = iters; left > 0;) {
-        const int t = pick_sweeps(&c, left, left, storage == FLUID_STORAGE_F16, false, (long long)rows * N, pressure_form != 0);
+        const int t = pick_sweeps(&c, left, left, shape, pressure_form != 0);
         if (k < capacity) depths[k] = t;
         ++k;
         left -= t;
@@ -1838,7 +1836,7 @@ int fluid_exchange_now(fluid_ctx* c, int kind, const int* fields, int nfields, i
     c->in_halo_exchange = false;
     if (rc != 0) return fail(FLUID_E_COMM, "exchange failed (kind %d, rc %d)", kind, rc);
     for (int k = 0; k < nfields; ++k)
-        c->reach[fields[k]] = kind == FLUID_XCHG_GATHER ? kEverywhere : std::max(c->reach[fields[k]], depth);
+        c->field[fields[k]].reach = kind == FLUID_XCHG_GATHER ? kEverywhere : std::max(c->field[fields[k]].reach, depth);
     return FLUID_OK;
 }
 
@@ -1881,7 +1879,7 @@ int fluid_op_set_bnd(fluid_ctx* c, int b, int x)
     if (b < 0 || b > 2) return fail(FLUID_E_INVALID, "b must be 0, 1 or 2");
     if (c->nranks != 1) return fail(FLUID_E_INVALID, "fluid_op_set_bnd is a whole-grid operator (1 GPU)");
     TRY(materialize(c, x));
-    fluid::launch_set_bnd(c->stream, c->st, c->f[x], c->pitch, c->n, b);
+    fluid::launch_set_bnd(c->stream, c->st, c->ptr(x), c->pitch, c->n, b);
     HIP_TRY(hipGetLastError());
     return FLUID_OK;
 }
@@ -1903,10 +1901,9 @@ int fluid_op_jacobi_sweep(fluid_ctx* c, int b, int x, int x0, int out, float alp
     if (b < 0 || b > 2) return fail(FLUID_E_INVALID, "b must be 0, 1 or 2");
     if (out == x || out == x0) return fail(FLUID_E_INVALID, "jacobi_sweep: out must not alias an input");
     TRY(materialize(c, {x, x0}));
-    c->zero[out] = false;
     TRY(need(c, {x}, 1));
     const int v1 = c->variant == fluid::JACOBI_TB ? fluid::JACOBI_STREAM : c->variant;   // one sweep: nothing to block
-    fluid::launch_jacobi(c->stream, c->st, v1, c->f[x], c->f[x0], c->f[out], c->pitch, c->n, c->own0, c->own1, alpha, beta, b);
+    fluid::launch_jacobi(c->stream, c->st, v1, c->ptr(x), c->ptr(x0), c->ptr(out), c->pitch, c->n, c->own0, c->own1, alpha, beta, b);
     wrote(c, out, 0);
     HIP_TRY(hipGetLastError());
     return FLUID_OK;
@@ -1926,7 +1923,12 @@ int fluid_op_advect(fluid_ctx* c, int b, int d, int d0, int u, int v, float dt)
     TRY(check_fields(c, {d, d0, u, v}));
     if (b < 0 || b > 2) return fail(FLUID_E_INVALID, "b must be 0, 1 or 2");
     if (d == d0 || d == u || d == v) return fail(FLUID_E_INVALID, "advect: output must not alias an input");
-    TRY(advect_prepare(c, {d0}, u, v, dt * (float)c->n));
+    if (c->nranks > 1) {                  // on this call's bound alone (no early guess: it would change the exchanges issued)
+        float vmax = 0.f;
+        bool fetched = false;
+        TRY(vmax_begin(c, u, v));
+        TRY(advect_rows(c, {d0}, dt * (float)c->n, 0, &vmax, &fetched));
+    }
     TRY(op_advect(c, b, d, d0, u, v, dt));
     HIP_TRY(hipGetLastError());
     return FLUID_OK;
@@ -1959,7 +1961,7 @@ int fluid_residual(fluid_ctx* c, int x, int x0, float alpha, float beta, float* 
     TRY(materialize(c, {x, x0}));
     TRY(need(c, {x}, 1));
     HIP_TRY(hipMemsetAsync(c->d_scalar, 0, sizeof(unsigned), c->stream));
-    fluid::launch_residual(c->stream, c->st, c->f[x], c->f[x0], c->pitch, c->n, c->own0, c->own1, alpha, beta, c->d_scalar);
+    fluid::launch_residual(c->stream, c->st, c->ptr(x), c->ptr(x0), c->pitch, c->n, c->own0, c->own1, alpha, beta, c->d_scalar);
     TRY(reduce_to_host(c, out));
     return exchange(c, FLUID_XCHG_MAX, {}, 0, out);
 }
@@ -1971,7 +1973,7 @@ int fluid_absmax_velocity(fluid_ctx* c, int u, int v, float* out)
     if (!out) return fail(FLUID_E_INVALID, "null pointer");
     TRY(materialize(c, {u, v}));
     HIP_TRY(hipMemsetAsync(c->d_scalar, 0, sizeof(unsigned), c->stream));
-    fluid::launch_absmax2(c->stream, c->st, c->f[u], c->f[v], c->pitch, c->n, c->own0, c->own1, c->d_scalar);
+    fluid::launch_absmax2(c->stream, c->st, c->ptr(u), c->ptr(v), c->pitch, c->n, c->own0, c->own1, c->d_scalar);
     TRY(reduce_to_host(c, out));
     return exchange(c, FLUID_XCHG_MAX, {}, 0, out);
 }
