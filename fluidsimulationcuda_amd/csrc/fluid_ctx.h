@@ -84,6 +84,7 @@ struct fluid_ctx {
     long long tb_t16_min_cells = -1;               // >= 0: 16-sweep launches on every slab of at least this many cells (tests, tuning);
                                                    // -1: the measured rule of pick_sweeps()
     bool fuse_divergence = true;                   // a projection's divergence is computed inside its solve's first launch
+    bool tb_fill = true;                           // FLUID_PARAM_TB_FILL: the fused kernel skips the fill evaluations nothing reads
     bool autotune = true;                          // strip heights of the fused kernel measured at run time (fluid_solver.hip: RbTuner)
     struct Trial { unsigned long long key; int cand; hipEvent_t a, b; };
     std::vector<Trial> trials;                     // launches being timed for the tuner

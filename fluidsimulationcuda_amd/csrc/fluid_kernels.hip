@@ -547,6 +547,7 @@ struct TbArgs {
     unsigned sx, sy;      // sign masks: flip across vertical / horizontal walls
     float x0_inc;         // pending add_source increment of the right-hand side (-0.0f: none)
     bool st_rg_lane, is_lg;
+    bool fill;            // skip the stage evaluations of the pipeline fill and drain that nothing reads (tb_march)
 };
 
 __device__ __forceinline__ float fxor(float v, unsigned m) { return __uint_as_float(__float_as_uint(v) ^ m); }
@@ -787,10 +788,14 @@ __device__ __forceinline__ void tb_sticky(const Vec<NV>& G, v2f& nf)
 // GEN = false: every row any stage touches at this step is interior -- a
 // branch-free body.  GEN = true (the few steps of a wall strip that sit on rows
 // 0 / n+1): per-stage checks, ghost rows of each stage regenerated from its rows 1 / n.
-template <int T, int DIVMODE, bool EDGE, bool WALL, bool GEN, int PH, typename S, int NV, bool DIVSRC = false, bool ADDSRC = false>
+// PART (interior body only): stages 1 .. smax run and the rest are skipped -- a wave-uniform branch per stage.  A skipped
+// stage stores nothing and leaves its ring slot undefined: only evaluations that are skipped as well read it (tb_march).
+template <int T, int DIVMODE, bool EDGE, bool WALL, bool GEN, int PH, typename S, int NV, bool DIVSRC = false, bool ADDSRC = false,
+          bool PART = false>
 __device__ __forceinline__ void tb_step(int t, Vec<NV> (&W)[T][3], Vec<NV> (&Q)[T + 1], Vec<NV> (&PX)[3], Vec<NV> (&PQ)[3],
-                                        const TbArgs<S, NV>& a, Vec<NV> (&UR)[3], Vec<NV> (&VR)[3], v2f& nf)
+                                        const TbArgs<S, NV>& a, Vec<NV> (&UR)[3], Vec<NV> (&VR)[3], v2f& nf, int smax = T)
 {
+    static_assert(!(PART && GEN), "the general body runs every stage");
     constexpr int UP = PH % 3, ME = (PH + 1) % 3, FR = (PH + 2) % 3;
     // stage 0: row t of x and x0, loaded three steps ago.  The hand-over is an opaque register move on
     // purpose: a plain assignment lets the allocator rename the prefetch slot into the ring and pay
@@ -852,15 +857,24 @@ __device__ __forceinline__ void tb_step(int t, Vec<NV> (&W)[T][3], Vec<NV> (&Q)[
     if constexpr (!GEN) {
 #pragma unroll
         for (int s = 1; s <= T; ++s) {
+            // PART: the stage's arithmetic behind a scalar branch; its ring write and store are not (a skipped stage writes
+            // an undefined row, which costs nothing, and stores through a disabled offset), so that every step issues the
+            // same memory operations outside any branch and the loop after the partial steps keeps waiting for each row
+            // three steps after its load (hipcc counts the operations in flight per path: see the prologue of tb_march)
+            const bool run = !PART || s <= smax;
             const int q = t - s;                         // row this stage produces now (wave-uniform)
-            Vec<NV> G = tb_stencil<DIVMODE, NV>(W[s - 1][UP], W[s - 1][ME], W[s - 1][FR], Q[s], a.alpha, a.k);
+            Vec<NV> G;
             float v1 = 0.f, vn = 0.f;
-            if (EDGE) tb_fix_columns<S, NV>(G, a, v1, vn, WALL && s == T);
-            if (s < T) W[s][FR] = G;
-            else {
-                tb_sticky<DIVMODE, NV>(G, nf);
-                tb_store<EDGE, WALL, S, NV>(G, q, (q >= a.q_lo) & (q < a.q_hi), a, v1, vn);
+            if (run) {
+                G = tb_stencil<DIVMODE, NV>(W[s - 1][UP], W[s - 1][ME], W[s - 1][FR], Q[s], a.alpha, a.k);
+                if (EDGE) tb_fix_columns<S, NV>(G, a, v1, vn, WALL && s == T);
+                if (s == T) tb_sticky<DIVMODE, NV>(G, nf);
+            } else {
+#pragma unroll
+                for (int c = 0; c < NV; ++c) G.c[c] = __builtin_nondeterministic_value(W[s - 1][FR].c[c]);
             }
+            if (s < T) W[s][FR] = G;
+            else tb_store<EDGE, WALL, S, NV>(G, q, run & (q >= a.q_lo) & (q < a.q_hi), a, v1, vn);
         }
     } else {
         // ring writes stay unconditional (selected values), so the rings stay in registers
@@ -924,6 +938,12 @@ __device__ __forceinline__ bool tb_march(int t0, int t1, const TbArgs<S, NV>& a)
     // T+1 <= t <= n+1.  Wall strips run the general body only for the triples that contain another
     // kind of step -- about T/3 of them per wall -- as three loops, so neither body pays for the
     // other's registers.
+    // Pipeline fill (a.fill): stage s at step t produces row t-s from rows t-s-1 .. t-s+1 of stage s-1.  When the strip's
+    // top is not the wall (t0 = q_lo-T), stage 0 holds rows t0 .. only, so stage s is right from row t0+s on, which it
+    // produces at step t0+2s; what it produces before that feeds only earlier evaluations of the later stages, and
+    // through them rows of stage T above q_lo, which are not stored.  So the first ceil(2T/3) triples run stages
+    // 1 .. (t-t0)/2 only: T(T+1) of a strip's T(rb+2T) stage evaluations.  The same way the steps of the last triple
+    // past t1 run none.  Both are partial steps of the interior body; the general one always runs every stage.
     int t = t0;
     if constexpr (WALL) {
         for (; t <= t1 && t < T + 1; t += 3) {
@@ -932,10 +952,23 @@ __device__ __forceinline__ bool tb_march(int t0, int t1, const TbArgs<S, NV>& a)
             tb_step<T, DIVMODE, EDGE, WALL, true, 2, S, NV, DIVSRC, ADDSRC>(t + 2, W, Q, PX, PQ, a, UR, VR, nf);
         }
     }
-    for (; t <= t1 && (!WALL || t + 1 <= a.n); t += 3) {
+    const int fill_end = (a.fill && t0 == a.q_lo - T) ? t0 + 3 * ((2 * T + 2) / 3) : t0;   // partial steps before it
+    const int full_end = a.fill ? t1 - 2 : t1;           // ... and in triples that start after it
+    auto stages = [&](int u) { return u > t1 ? 0 : u < fill_end ? (u - t0) >> 1 : T; };
+    for (; t <= t1 && t < fill_end && (!WALL || t + 1 <= a.n); t += 3) {
+        tb_step<T, DIVMODE, EDGE, WALL, false, 0, S, NV, DIVSRC, ADDSRC, true>(t, W, Q, PX, PQ, a, UR, VR, nf, stages(t));
+        tb_step<T, DIVMODE, EDGE, WALL, false, 1, S, NV, DIVSRC, ADDSRC, true>(t + 1, W, Q, PX, PQ, a, UR, VR, nf, stages(t + 1));
+        tb_step<T, DIVMODE, EDGE, WALL, false, 2, S, NV, DIVSRC, ADDSRC, true>(t + 2, W, Q, PX, PQ, a, UR, VR, nf, stages(t + 2));
+    }
+    for (; t <= full_end && (!WALL || t + 1 <= a.n); t += 3) {
         tb_step<T, DIVMODE, EDGE, WALL, false, 0, S, NV, DIVSRC, ADDSRC>(t, W, Q, PX, PQ, a, UR, VR, nf);
         tb_step<T, DIVMODE, EDGE, WALL, false, 1, S, NV, DIVSRC, ADDSRC>(t + 1, W, Q, PX, PQ, a, UR, VR, nf);
         tb_step<T, DIVMODE, EDGE, WALL, false, 2, S, NV, DIVSRC, ADDSRC>(t + 2, W, Q, PX, PQ, a, UR, VR, nf);
+    }
+    for (; t <= t1 && (!WALL || t + 1 <= a.n); t += 3) {
+        tb_step<T, DIVMODE, EDGE, WALL, false, 0, S, NV, DIVSRC, ADDSRC, true>(t, W, Q, PX, PQ, a, UR, VR, nf, stages(t));
+        tb_step<T, DIVMODE, EDGE, WALL, false, 1, S, NV, DIVSRC, ADDSRC, true>(t + 1, W, Q, PX, PQ, a, UR, VR, nf, stages(t + 1));
+        tb_step<T, DIVMODE, EDGE, WALL, false, 2, S, NV, DIVSRC, ADDSRC, true>(t + 2, W, Q, PX, PQ, a, UR, VR, nf, stages(t + 2));
     }
     if constexpr (WALL) {
         for (; t <= t1; t += 3) {
@@ -975,7 +1008,7 @@ constexpr int tb_waves_per_simd(int T, int NV) { return NV == 2 ? (T <= 8 ? 4 : 
 // diffusion): more waves per launch, hence taller strips and less pipeline-fill redundancy.
 template <int T, int DIVMODE, int NV, typename S, bool DIVSRC = false, bool ADDSRC = false>
 __global__ __launch_bounds__(256, tb_waves_per_simd(T, NV)) void k_jacobi_tb(TbBatch batch, int pitch, int n, int row_lo,
-                                                                             int row_hi, int rb, int rb_edge, TbGrid g)
+                                                                             int row_hi, int rb, int rb_edge, TbGrid g, int fill)
 {
     static_assert(!DIVSRC || DIVMODE == 4, "the divergence-sourced launch is the first launch of a pressure solve");
     static_assert(!(DIVSRC && ADDSRC) && (!ADDSRC || DIVMODE != 3), "one second store per launch; mode 3's tiles are taken from the summed field");
@@ -1077,6 +1110,7 @@ __global__ __launch_bounds__(256, tb_waves_per_simd(T, NV)) void k_jacobi_tb(TbB
     a.sy = (b == 2) ? 0x80000000u : 0u;
     a.alpha = alpha;
     a.k.beta = beta;
+    a.fill = fill != 0;
     const int t0 = max(0, a.q_lo - T), t1 = a.q_hi - 1 + T;
     // a strip whose input rows [q_lo-T, q_hi-1+T] all exist never needs a regenerated ghost row
     const bool wall = (a.q_lo < T) || (a.q_hi - 1 + T > n + 1);      // wave-uniform
@@ -1638,7 +1672,7 @@ void launch_jacobi(hipStream_t s, int st, int variant, const void* x, const void
 // 3: hi, lo = the two-term reciprocal where the tiles of |x0| minima allow it, yd elsewhere;
 // 5: beta = RN32(1/beta), hi = beta * 2^24, lo = -(RN32(1/beta) * 2^-24), yd for the second pass of a wave that met inf / NaN.
 void launch_jacobi_tb(hipStream_t s, int st, int T, int divmode, int nv, const TbBatch& batch, int pitch, int n, int row_lo,
-                      int row_hi, int rb, int rb_edge, bool divsrc, bool addsrc, int hole_lo, int hole_hi)
+                      int row_hi, int rb, int rb_edge, bool divsrc, bool addsrc, int hole_lo, int hole_hi, bool fill)
 {
     const int rows = row_hi - row_lo;
     if (rows <= 0 || batch.count <= 0) return;
@@ -1667,7 +1701,7 @@ void launch_jacobi_tb(hipStream_t s, int st, int T, int divmode, int nv, const T
     g.edge_blocks = g.edge_wins * (int)cdiv(strips(rb_edge), 4);
     const dim3 grid(8 * cdiv(g.inner_blocks + g.edge_blocks, 8), 1, batch.count), block(256);
 #define FLUID_TB2(TT, DD, NN) \
-    FLUID_BY_STORAGE(st, hipLaunchKernelGGL((k_jacobi_tb<TT, DD, NN, S>), grid, block, 0, s, batch, pitch, n, row_lo, row_hi, rb, rb_edge, g))
+    FLUID_BY_STORAGE(st, hipLaunchKernelGGL((k_jacobi_tb<TT, DD, NN, S>), grid, block, 0, s, batch, pitch, n, row_lo, row_hi, rb, rb_edge, g, fill ? 1 : 0))
 #define FLUID_TB1(TT, DD)            \
     if (nv == 2) FLUID_TB2(TT, DD, 2); \
     else FLUID_TB2(TT, DD, 4)
@@ -1678,9 +1712,9 @@ void launch_jacobi_tb(hipStream_t s, int st, int T, int divmode, int nv, const T
     else if (divmode == 2) { FLUID_TB1(TT, 2); } \
     else { FLUID_TB1(TT, 0); }
 #define FLUID_TBD(TT) \
-    FLUID_BY_STORAGE(st, hipLaunchKernelGGL((k_jacobi_tb<TT, 4, 2, S, true>), grid, block, 0, s, batch, pitch, n, row_lo, row_hi, rb, rb_edge, g))
+    FLUID_BY_STORAGE(st, hipLaunchKernelGGL((k_jacobi_tb<TT, 4, 2, S, true>), grid, block, 0, s, batch, pitch, n, row_lo, row_hi, rb, rb_edge, g, fill ? 1 : 0))
 #define FLUID_TBA2(TT, DD) \
-    FLUID_BY_STORAGE(st, hipLaunchKernelGGL((k_jacobi_tb<TT, DD, 2, S, false, true>), grid, block, 0, s, batch, pitch, n, row_lo, row_hi, rb, rb_edge, g))
+    FLUID_BY_STORAGE(st, hipLaunchKernelGGL((k_jacobi_tb<TT, DD, 2, S, false, true>), grid, block, 0, s, batch, pitch, n, row_lo, row_hi, rb, rb_edge, g, fill ? 1 : 0))
 #define FLUID_TBA(TT)                       \
     if (divmode == 5) { FLUID_TBA2(TT, 5); }      \
     else if (divmode == 2) { FLUID_TBA2(TT, 2); } \

@@ -478,7 +478,7 @@ unsigned long long tune_key(const fluid_ctx* c, int T, int m, int divmode, long 
     unsigned long long h = 1469598103934665603ull;
     for (unsigned long long v : {(unsigned long long)dev, (unsigned long long)c->n, (unsigned long long)rows_n, (unsigned long long)T,
                                  (unsigned long long)m, (unsigned long long)divmode, (unsigned long long)c->tb_nv, (unsigned long long)c->st,
-                                 (unsigned long long)c->tb_edge_pct}) {
+                                 (unsigned long long)c->tb_edge_pct, (unsigned long long)c->tb_fill}) {
         h ^= v;
         h *= 1099511628211ull;
     }
@@ -533,9 +533,14 @@ int tune_pick(fluid_ctx* c, unsigned long long key, int heuristic, int T, long l
     if (e.cand.empty()) {
         e.cand.push_back(heuristic);
         for (int r : {48, 56, 64, 80, 96, 112, 128, 160, 192}) {
-            if (r < 2 * T || r >= rows_n + 2 * T) continue;     // (a height past the rows is one strip: the tallest candidate covers it)
+            if (r < T || r >= rows_n + 2 * T) continue;         // (a height past the rows is one strip: the tallest candidate covers it)
             if (std::find(e.cand.begin(), e.cand.end(), r) == e.cand.end()) e.cand.push_back(r);
         }
+        // a strip repeats about T rows of pipeline fill (FLUID_PARAM_TB_FILL; 2T without it): large grids may gain
+        // waves from shorter strips too
+        if (rows_n > 2200)
+            for (int r : {32, 40})
+                if (r >= T && std::find(e.cand.begin(), e.cand.end(), r) == e.cand.end()) e.cand.push_back(r);
         // small grids are bound by the latency of one wave's march, rb + 2T steps: strips shorter than the pipeline is
         // deep pay there (256^2, 8 sweeps per launch: 0.21 ms per step at 4 rows against 0.26 at 16)
         if (rows_n <= 2200)
@@ -834,8 +839,9 @@ int edge_rows(const fluid_ctx* c, int T, int rb) { return std::max(2 * T, rb * (
 
 // Closed-form strip height of a fused launch of m solves, T sweeps, rows_n output rows (tools/tb_sweep.py on MI355X): the
 // kernel hides its latencies only behind other waves, so every block should be resident at once (a 256-thread block is one
-// wave per SIMD), in the tallest strips that allow (each pays 2T rows of pipeline fill): the smallest height whose blocks
-// fit 92 % of one round; grids too large for one round stop at 80 rows (160 for a batch; 192 at T = 16).
+// wave per SIMD), in the tallest strips that allow (a strip of rb rows marches rb + T - 1 rows of stages with
+// FLUID_PARAM_TB_FILL, rb + 2T without): the smallest height from T (2T without) whose blocks fit 92 % of one round;
+// grids too large for one round stop at 80 rows (160 for a batch; 192 at T = 16).
 int strip_rows(const fluid_ctx* c, int T, int m, long long rows_n)
 {
     const int nv = c->tb_nv;
@@ -845,12 +851,12 @@ int strip_rows(const fluid_ctx* c, int T, int m, long long rows_n)
     const int resident = nv == 2 ? (T >= 16 ? 2 : 4) : (T >= 8 ? 2 : 3);
     const long long room = (long long)c->num_cu * resident * 92 / 100;
     const int cap = T >= 16 ? 192 : (T >= 8 ? 80 : 96) * (m > 1 ? 2 : 1);
-    int rb = 2 * T;
+    int rb = c->tb_fill ? T : 2 * T;
     for (; rb < cap; rb += 2) {
         const long long si = (rows_n + rb - 1) / rb, se = (rows_n + edge_rows(c, T, rb) - 1) / edge_rows(c, T, rb);
         if ((inner * ((si + 3) / 4) + outer * ((se + 3) / 4)) * m <= room) break;
     }
-    // small grids: a launch lasts as long as one wave's march of rb + 2T rows, and the best height
+    // small grids: a launch lasts as long as one wave's march of rb + T - 1 rows (rb + 2T), and the best height
     // measured is about rows / 64 (2 at 128^2, 4 at 256^2, 8 at 512^2, 16 and more from 1024^2)
     if (rows_n <= 1100) rb = std::max(2, std::min(rb, (int)(rows_n / 64) & ~1));
     return rb;
@@ -881,7 +887,7 @@ int launch_fused(fluid_ctx* c, const fluid::TbBatch& bt, int T, int divmode, boo
         }
         if (trial >= 0) TRY(tune_begin(c, key, trial));
         fluid::launch_jacobi_tb(c->stream, c->st, T, divmode, c->tb_nv, bt, c->pitch, c->n, plo, phi, rb, std::min(rb, edge_rows(c, T, rb)),
-                                divsrc, addsrc, hole_lo, hole_hi);
+                                divsrc, addsrc, hole_lo, hole_hi, c->tb_fill);
         if (trial >= 0) TRY(tune_end(c));
     }
     if (split) c->split_launches += 1;
@@ -1719,6 +1725,9 @@ int fluid_set_param(fluid_ctx* c, int key, int value)
         return FLUID_OK;
     case FLUID_PARAM_TB_AUTOTUNE:
         c->autotune = value != 0;
+        return FLUID_OK;
+    case FLUID_PARAM_TB_FILL:
+        c->tb_fill = value != 0;
         return FLUID_OK;
     case FLUID_PARAM_SLAB_OVERLAP:
         c->slab_overlap = value != 0;

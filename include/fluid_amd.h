@@ -103,6 +103,9 @@ enum {
                                       h * |velocity| and fall into fp16's subnormal range from a few thousand cells per side
                                       on -- and divided back exactly (in the gradient subtraction; on the host when u_prev /
                                       v_prev are downloaded).  0: plain values.  Changes fp16 results (not fp32 ones).      */
+    ,FLUID_PARAM_TB_FILL = 15      /* 1 (default): the fused kernel skips the stage evaluations of each strip's pipeline fill
+                                      and drain that no stored row depends on (about T(T+1) of a strip's T(rows + 2T));
+                                      0: every stage at every step.  Speed only.                                        */
     ,FLUID_PARAM_TB_MIN_CELLS = 4  /* FLUID_JACOBI_TB fuses sweeps only on slabs of at least this many cells
                                       (default 0: always); smaller ones run one-thread-per-cell sweeps   */
 };
