@@ -354,7 +354,8 @@ void rows_with_walls(const fluid_ctx* c, int reach, int* lo, int* hi)
 // add_source of such a source adds dt*0 to every cell: nothing but the sign of -0 (and NaN/inf rules for a non-finite
 // dt), for a read and a write of the whole field.  With the fused Jacobi kernel the increment stays PENDING instead
 // (FieldState::pend): the solve that consumes the field as its right-hand side adds it to each row as it loads it, any
-// other reader settles it with the real kernel first (here), and a writer that replaces the field drops it (wrote).
+// other reader settles it with the real kernel first (here) -- a solve that takes it as its first guess included
+// (batch_prepare) -- and a writer that replaces the field drops it (wrote).
 int settle_source(fluid_ctx* c, int f);
 
 // a field kept scaled (fscale) goes back to plain values: every row of it, one multiplication by a power of two
@@ -736,6 +737,13 @@ int batch_prepare(fluid_ctx* c, Batch& B)
         return FLUID_OK;
     }
     for (int k = 0; k < B.count; ++k) TRY(materialize_zero(c, sv[k].x0));     // a pending increment rides along (TbBatch::x0_inc)
+    // A first guess has no such path: the fused kernel reads x as it is in memory.  It is pending only after
+    // fluid_op_add_source of a zero source (in a step the pending field is always the right-hand side), so settle it here
+    for (int k = 0; k < B.count; ++k)
+        if (c->field[sv[k].x].pend) {
+            TRY(xchg_join(c));                    // (its kernel touches rows that may be on their way)
+            TRY(settle(c, sv[k].x, /*keep_scale=*/true));
+        }
     return FLUID_OK;
 }
 
