@@ -29,8 +29,8 @@ struct TbBatch {
     const unsigned* tiles[3];    // division mode 3: |x0| minima per tile (k_tile_min_abs), tile_pitch words per tile row
     unsigned tile_thr[3];        //   ... and the bit pattern of beta * 2^-72 they must reach
     int tile_pitch;
-    void* div[3];                // divergence-sourced launch (launch_jacobi_tb divsrc): x / x0 hold u / v, the divergence is
-    float div_scale;             //   written here; div_scale = -0.5f * h.  Source-adding launch (addsrc): x is the source
+    void* div[3];                // divergence-sourced launch (TB_DIVSRC): x / x0 hold u / v, the divergence is
+    float div_scale;             //   written here; div_scale = -0.5f * h.  Source-adding launch (TB_ADDSRC): x is the source
                                  //   field s, x0 + div_scale * s (div_scale = dt) is the right-hand side and is written here
     int b[3];
     int x_zero[3];               // first guess known to be all +0: never read
@@ -42,11 +42,46 @@ void launch_set_bnd(hipStream_t s, int st, void* f, int pitch, int n, int b);
 void launch_add_source(hipStream_t s, int st, void* x, const void* src, int pitch, int row_lo, int row_hi, float dt);
 void launch_jacobi(hipStream_t s, int st, int variant, const void* x, const void* x0, void* out, int pitch, int n,
                    int row_lo, int row_hi, float alpha, float beta, int b);
-void launch_jacobi_tb(hipStream_t s, int st, int T, int divmode, int nv, const TbBatch& batch, int pitch, int n, int row_lo,
-                      int row_hi, int rb, int rb_edge, bool divsrc = false, bool addsrc = false, int hole_lo = 0, int hole_hi = 0,
-                      bool fill = true);
-// the launches that exist with addsrc: 2-column lanes, 8 / 12 / 16 sweeps, division modes 0, 2 and 5
-inline bool jacobi_tb_addsrc_exists(int T, int divmode, int nv) { return nv == 2 && (T == 8 || T == 12 || T == 16) && (divmode == 0 || divmode == 2 || divmode == 5); }
+// Shapes of the fused Jacobi kernel (k_jacobi_tb): sweeps T, division mode, columns per lane, and the form -- plain, the
+// first launch of a pressure solve that forms the divergence as its right-hand side (DIVSRC), or the first launch of a
+// diffusion that adds a deferred source to it (ADDSRC).  This table is the set of kernels built per storage type and the
+// set launch_jacobi_tb accepts; 4-column lanes stop at 8 sweeps (more would need > 256 registers).
+enum TbForm { TB_PLAIN = 0, TB_DIVSRC = 1, TB_ADDSRC = 2 };
+struct TbShape { int T, divmode, nv, form; };
+inline constexpr TbShape kTbShapes[] = {
+    {2, 0, 2, TB_PLAIN},   {2, 2, 2, TB_PLAIN},   {2, 3, 2, TB_PLAIN},   {2, 4, 2, TB_PLAIN},   {2, 5, 2, TB_PLAIN},
+    {2, 0, 4, TB_PLAIN},   {2, 2, 4, TB_PLAIN},   {2, 3, 4, TB_PLAIN},   {2, 4, 4, TB_PLAIN},   {2, 5, 4, TB_PLAIN},
+    {4, 0, 2, TB_PLAIN},   {4, 2, 2, TB_PLAIN},   {4, 3, 2, TB_PLAIN},   {4, 4, 2, TB_PLAIN},   {4, 5, 2, TB_PLAIN},
+    {4, 0, 4, TB_PLAIN},   {4, 2, 4, TB_PLAIN},   {4, 3, 4, TB_PLAIN},   {4, 4, 4, TB_PLAIN},   {4, 5, 4, TB_PLAIN},
+    {8, 0, 2, TB_PLAIN},   {8, 2, 2, TB_PLAIN},   {8, 3, 2, TB_PLAIN},   {8, 4, 2, TB_PLAIN},   {8, 5, 2, TB_PLAIN},
+    {8, 0, 4, TB_PLAIN},   {8, 2, 4, TB_PLAIN},   {8, 3, 4, TB_PLAIN},   {8, 4, 4, TB_PLAIN},   {8, 5, 4, TB_PLAIN},
+    {12, 0, 2, TB_PLAIN},  {12, 2, 2, TB_PLAIN},  {12, 3, 2, TB_PLAIN},  {12, 4, 2, TB_PLAIN},  {12, 5, 2, TB_PLAIN},
+    {16, 0, 2, TB_PLAIN},  {16, 2, 2, TB_PLAIN},  {16, 3, 2, TB_PLAIN},  {16, 4, 2, TB_PLAIN},  {16, 5, 2, TB_PLAIN},
+    {8, 4, 2, TB_DIVSRC},  {12, 4, 2, TB_DIVSRC}, {16, 4, 2, TB_DIVSRC}, {8, 0, 2, TB_ADDSRC},  {8, 2, 2, TB_ADDSRC},  {8, 5, 2, TB_ADDSRC},
+    {12, 0, 2, TB_ADDSRC}, {12, 2, 2, TB_ADDSRC}, {12, 5, 2, TB_ADDSRC}, {16, 0, 2, TB_ADDSRC}, {16, 2, 2, TB_ADDSRC}, {16, 5, 2, TB_ADDSRC},
+};
+constexpr int kTbShapeCount = sizeof(kTbShapes) / sizeof(kTbShapes[0]);
+// index of a shape in kTbShapes, -1 if it does not exist; a negative T or divmode matches any
+constexpr int jacobi_tb_index(int T, int divmode, int nv, int form)
+{
+    for (int i = 0; i < kTbShapeCount; ++i) {
+        const TbShape& s = kTbShapes[i];
+        if ((T < 0 || s.T == T) && (divmode < 0 || s.divmode == divmode) && s.nv == nv && s.form == form) return i;
+    }
+    return -1;
+}
+constexpr bool jacobi_tb_exists(int T, int divmode, int nv, int form) { return jacobi_tb_index(T, divmode, nv, form) >= 0; }
+constexpr bool tb_shapes_unique(int i = 0)
+{
+    return i == kTbShapeCount || (jacobi_tb_index(kTbShapes[i].T, kTbShapes[i].divmode, kTbShapes[i].nv, kTbShapes[i].form) == i && tb_shapes_unique(i + 1));
+}
+static_assert(kTbShapeCount == 52 && tb_shapes_unique(), "52 distinct shapes: adding or removing one is a change of this table");
+// sweeps per launch the fused kernel is built for, deepest first (FLUID_PARAM_TB_MAX_SWEEPS takes one of them)
+inline constexpr int kTbDepths[] = {16, 12, 8, 4, 2};
+constexpr bool is_tb_depth(int T) { for (int d : kTbDepths) if (d == T) return true; return false; }
+// false (nothing launched): the shape is not in kTbShapes
+bool launch_jacobi_tb(hipStream_t s, int st, int T, int divmode, int nv, int form, const TbBatch& batch, int pitch, int n, int row_lo,
+                      int row_hi, int rb, int rb_edge, int hole_lo = 0, int hole_hi = 0, bool fill = true);
 // tiles of kTileRows x kTileCols interior cells, tile (r, c) = rows 1 + r*kTileRows.., columns 1 + c*kTileCols..
 constexpr int kTileRows = 32, kTileCols = 64;
 inline int tile_rows(int n) { return (n + kTileRows - 1) / kTileRows; }

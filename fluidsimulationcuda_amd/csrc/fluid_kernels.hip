@@ -22,7 +22,9 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <array>
 #include <cstdlib>
+#include <utility>
 
 #include "fluid_kernels.h"
 
@@ -1604,16 +1606,28 @@ static inline unsigned cdiv(unsigned a, unsigned b) { return (a + b - 1) / b; }
 // element offsets into a field fit 32 bits (with a byte offset below 2^32 for the hardware's address add)
 static inline bool narrow_index(int st, int pitch, int n) { return (size_t)(n + 2) * (size_t)pitch * storage_bytes(st) < (1ull << 32); }
 
-#define FLUID_BY_STORAGE(st, CALL)            \
+#define FLUID_BY_STORAGE(st, ...)             \
     do {                                      \
         if ((st) == STORAGE_F16) {            \
             using S = half_t;                 \
-            CALL;                             \
+            __VA_ARGS__;                      \
         } else {                              \
             using S = float;                  \
-            CALL;                             \
+            __VA_ARGS__;                      \
         }                                     \
     } while (0)
+// ... and of the kernels that take the index type of their field offsets: 32-bit where they fit (narrow_index)
+#define FLUID_BY_STORAGE_INDEX(st, pitch, n, ...)                                                  \
+    do {                                                                                           \
+        if (narrow_index(st, pitch, n)) { using I = unsigned; FLUID_BY_STORAGE(st, __VA_ARGS__); } \
+        else { using I = size_t; FLUID_BY_STORAGE(st, __VA_ARGS__); }                              \
+    } while (0)
+
+// grid-stride kernels over rows [row_lo, row_hi): one thread per 4 elements, 1 .. 8192 blocks
+static inline unsigned stride_blocks(int pitch, int row_lo, int row_hi)
+{
+    return (unsigned)std::clamp<size_t>(((size_t)(row_hi - row_lo) * (pitch >> 2) + 255) / 256, 1, 8192);
+}
 
 void launch_set_bnd(hipStream_t s, int st, void* f, int pitch, int n, int b)
 {
@@ -1623,22 +1637,18 @@ void launch_set_bnd(hipStream_t s, int st, void* f, int pitch, int n, int b)
 // src == nullptr: the source is known to be all +0 (dt is then the pre-multiplied increment dt*0)
 void launch_add_source(hipStream_t s, int st, void* x, const void* src, int pitch, int row_lo, int row_hi, float dt)
 {
-    const size_t total = (size_t)(row_hi - row_lo) * (pitch >> 2);
-    const unsigned blocks = (unsigned)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+    const unsigned blocks = stride_blocks(pitch, row_lo, row_hi);
     if (!src) {
-        FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_add_zero_source<S>, dim3(blocks ? blocks : 1), dim3(256), 0, s, (S*)x,
-                                                pitch, row_lo, row_hi, dt));
+        FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_add_zero_source<S>, dim3(blocks), dim3(256), 0, s, (S*)x, pitch, row_lo, row_hi, dt));
         return;
     }
-    FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_add_source<S>, dim3(blocks ? blocks : 1), dim3(256), 0, s, (S*)x,
-                                            (const S*)src, pitch, row_lo, row_hi, dt));
+    FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_add_source<S>, dim3(blocks), dim3(256), 0, s, (S*)x, (const S*)src, pitch, row_lo, row_hi, dt));
 }
 
 void launch_scale(hipStream_t s, int st, void* x, int pitch, int row_lo, int row_hi, float factor)
 {
-    const size_t total = (size_t)(row_hi - row_lo) * (pitch >> 2);
-    const unsigned blocks = (unsigned)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_scale<S>, dim3(blocks ? blocks : 1), dim3(256), 0, s, (S*)x, pitch, row_lo, row_hi, factor));
+    FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_scale<S>, dim3(stride_blocks(pitch, row_lo, row_hi)), dim3(256), 0, s, (S*)x, pitch,
+                                            row_lo, row_hi, factor));
 }
 
 void launch_jacobi(hipStream_t s, int st, int variant, const void* x, const void* x0, void* out, int pitch, int n,
@@ -1667,20 +1677,32 @@ void launch_jacobi(hipStream_t s, int st, int variant, const void* x, const void
     }
 }
 
-// T in {8,4,2} sweeps per launch, nv in {2,4} columns per lane; batch.count solves per launch.
+// one kernel per shape of kTbShapes (taking its address is what instantiates it), in the table's order
+using TbKernel = void (*)(TbBatch, int, int, int, int, int, int, TbGrid, int);
+template <typename S, size_t... I>
+static std::array<TbKernel, kTbShapeCount> tb_kernels(std::index_sequence<I...>)
+{
+    return {&k_jacobi_tb<kTbShapes[I].T, kTbShapes[I].divmode, kTbShapes[I].nv, S, kTbShapes[I].form == TB_DIVSRC,
+                         kTbShapes[I].form == TB_ADDSRC>...};
+}
+
+// batch.count solves per launch of the shape (T, divmode, nv, form).
 // divmode 0: beta; 2: beta unused, yd = RN64(1/beta); 4: beta = exact reciprocal of a power of two and alpha == 1;
 // 3: hi, lo = the two-term reciprocal where the tiles of |x0| minima allow it, yd elsewhere;
 // 5: beta = RN32(1/beta), hi = beta * 2^24, lo = -(RN32(1/beta) * 2^-24), yd for the second pass of a wave that met inf / NaN.
-void launch_jacobi_tb(hipStream_t s, int st, int T, int divmode, int nv, const TbBatch& batch, int pitch, int n, int row_lo,
-                      int row_hi, int rb, int rb_edge, bool divsrc, bool addsrc, int hole_lo, int hole_hi, bool fill)
+bool launch_jacobi_tb(hipStream_t s, int st, int T, int divmode, int nv, int form, const TbBatch& batch, int pitch, int n, int row_lo,
+                      int row_hi, int rb, int rb_edge, int hole_lo, int hole_hi, bool fill)
 {
+    static const auto f32 = tb_kernels<float>(std::make_index_sequence<kTbShapeCount>());
+    static const auto f16 = tb_kernels<half_t>(std::make_index_sequence<kTbShapeCount>());
+    const int shape = jacobi_tb_index(T, divmode, nv, form);
+    if (shape < 0) return false;
     const int rows = row_hi - row_lo;
-    if (rows <= 0 || batch.count <= 0) return;
+    if (rows <= 0 || batch.count <= 0) return true;
     if (hole_lo < row_lo) hole_lo = row_lo;
     if (hole_hi > row_hi) hole_hi = row_hi;
     const bool hole = hole_lo < hole_hi;
-    if (hole && hole_lo == row_lo && hole_hi == row_hi) return;
-    if (T == 16 || T == 12) nv = 2;
+    if (hole && hole_lo == row_lo && hole_hi == row_hi) return true;
     const int HL = (T + nv - 1) / nv, VS = 64 - 2 * HL;
     const unsigned nvec = (n + nv - 1) / nv;
     rb_edge = rb_edge < 1 ? rb : (rb_edge > rb ? rb : rb_edge);
@@ -1700,58 +1722,9 @@ void launch_jacobi_tb(hipStream_t s, int st, int T, int divmode, int nv, const T
     g.inner_blocks = g.inner_wins * (int)cdiv(strips(rb), 4);
     g.edge_blocks = g.edge_wins * (int)cdiv(strips(rb_edge), 4);
     const dim3 grid(8 * cdiv(g.inner_blocks + g.edge_blocks, 8), 1, batch.count), block(256);
-#define FLUID_TB2(TT, DD, NN) \
-    FLUID_BY_STORAGE(st, hipLaunchKernelGGL((k_jacobi_tb<TT, DD, NN, S>), grid, block, 0, s, batch, pitch, n, row_lo, row_hi, rb, rb_edge, g, fill ? 1 : 0))
-#define FLUID_TB1(TT, DD)            \
-    if (nv == 2) FLUID_TB2(TT, DD, 2); \
-    else FLUID_TB2(TT, DD, 4)
-#define FLUID_TB(TT)                          \
-    if (divmode == 4) { FLUID_TB1(TT, 4); }      \
-    else if (divmode == 5) { FLUID_TB1(TT, 5); } \
-    else if (divmode == 3) { FLUID_TB1(TT, 3); } \
-    else if (divmode == 2) { FLUID_TB1(TT, 2); } \
-    else { FLUID_TB1(TT, 0); }
-#define FLUID_TBD(TT) \
-    FLUID_BY_STORAGE(st, hipLaunchKernelGGL((k_jacobi_tb<TT, 4, 2, S, true>), grid, block, 0, s, batch, pitch, n, row_lo, row_hi, rb, rb_edge, g, fill ? 1 : 0))
-#define FLUID_TBA2(TT, DD) \
-    FLUID_BY_STORAGE(st, hipLaunchKernelGGL((k_jacobi_tb<TT, DD, 2, S, false, true>), grid, block, 0, s, batch, pitch, n, row_lo, row_hi, rb, rb_edge, g, fill ? 1 : 0))
-#define FLUID_TBA(TT)                       \
-    if (divmode == 5) { FLUID_TBA2(TT, 5); }      \
-    else if (divmode == 2) { FLUID_TBA2(TT, 2); } \
-    else { FLUID_TBA2(TT, 0); }
-    if (addsrc) {                                        // first launch of a diffusion: right-hand side = x0 + dt * x, stored out of place
-        if (T == 16) { FLUID_TBA(16) }
-        else if (T == 12) { FLUID_TBA(12) }
-        else { FLUID_TBA(8) }
-    }
-    else if (divsrc) {                                   // first launch of a pressure solve, right-hand side computed from (u, v)
-        if (T == 16) { FLUID_TBD(16); }
-        else if (T == 12) { FLUID_TBD(12); }
-        else { FLUID_TBD(8); }
-    }
-    else if (T == 16) {                                  // 2-column lanes only (4-column ones would need > 256 registers)
-        if (divmode == 4) { FLUID_TB2(16, 4, 2); }
-        else if (divmode == 5) { FLUID_TB2(16, 5, 2); }
-        else if (divmode == 3) { FLUID_TB2(16, 3, 2); }
-        else if (divmode == 2) { FLUID_TB2(16, 2, 2); }
-        else { FLUID_TB2(16, 0, 2); }
-    }
-    else if (T == 12) {                                  // 2-column lanes, three waves per SIMD
-        if (divmode == 4) { FLUID_TB2(12, 4, 2); }
-        else if (divmode == 5) { FLUID_TB2(12, 5, 2); }
-        else if (divmode == 3) { FLUID_TB2(12, 3, 2); }
-        else if (divmode == 2) { FLUID_TB2(12, 2, 2); }
-        else { FLUID_TB2(12, 0, 2); }
-    }
-    else if (T == 8) { FLUID_TB(8) }
-    else if (T == 4) { FLUID_TB(4) }
-    else { FLUID_TB(2) }
-#undef FLUID_TBA
-#undef FLUID_TBA2
-#undef FLUID_TBD
-#undef FLUID_TB
-#undef FLUID_TB1
-#undef FLUID_TB2
+    const TbKernel k = (st == STORAGE_F16 ? f16 : f32)[shape];
+    hipLaunchKernelGGL(k, grid, block, 0, s, batch, pitch, n, row_lo, row_hi, rb, rb_edge, g, fill ? 1 : 0);
+    return true;
 }
 
 // tiles of |x0| minima for division mode 3, rows [row_lo, row_hi) within 1..n+1; tb.tiles[k] holds tile_rows(n) x tile_pitch words
@@ -1774,10 +1747,8 @@ void launch_validate_div(hipStream_t s, int divmode, float beta, float kbeta, do
     k.yd = yd;
     k.hi = hi;
     k.lo = lo;
-    if (divmode == 4) hipLaunchKernelGGL((k_validate_div<4>), dim3(8192), dim3(256), 0, s, beta, k, bad);
-    else if (divmode == 5) hipLaunchKernelGGL((k_validate_div<5>), dim3(8192), dim3(256), 0, s, beta, k, bad);
-    else if (divmode == 3) hipLaunchKernelGGL((k_validate_div<3>), dim3(8192), dim3(256), 0, s, beta, k, bad);
-    else hipLaunchKernelGGL((k_validate_div<2>), dim3(8192), dim3(256), 0, s, beta, k, bad);
+    const auto f = divmode == 4 ? k_validate_div<4> : divmode == 5 ? k_validate_div<5> : divmode == 3 ? k_validate_div<3> : k_validate_div<2>;
+    hipLaunchKernelGGL(f, dim3(8192), dim3(256), 0, s, beta, k, bad);
 }
 
 void launch_advect(hipStream_t s, int st, void* d, const void* d0, const void* u, const void* v, int pitch, int n,
@@ -1785,12 +1756,8 @@ void launch_advect(hipStream_t s, int st, void* d, const void* d0, const void* u
 {
     if (row_hi <= row_lo) return;
     const dim3 grid(cdiv(n, 1024), row_hi - row_lo);
-    if (narrow_index(st, pitch, n))
-        FLUID_BY_STORAGE(st, hipLaunchKernelGGL((k_advect<S, unsigned>), grid, dim3(256), 0, s, (S*)d, (const S*)d0, (const S*)u,
-                                                (const S*)v, pitch, n, row_lo, row_hi, dt0, b));
-    else
-        FLUID_BY_STORAGE(st, hipLaunchKernelGGL((k_advect<S, size_t>), grid, dim3(256), 0, s, (S*)d, (const S*)d0, (const S*)u,
-                                                (const S*)v, pitch, n, row_lo, row_hi, dt0, b));
+    FLUID_BY_STORAGE_INDEX(st, pitch, n, hipLaunchKernelGGL((k_advect<S, I>), grid, dim3(256), 0, s, (S*)d, (const S*)d0, (const S*)u,
+                                                            (const S*)v, pitch, n, row_lo, row_hi, dt0, b));
 }
 
 void launch_advect2(hipStream_t s, int st, void* da, const void* d0a, int ba, void* db, const void* d0b, int bb, const void* u,
@@ -1798,12 +1765,8 @@ void launch_advect2(hipStream_t s, int st, void* da, const void* d0a, int ba, vo
 {
     if (row_hi <= row_lo) return;
     const dim3 grid(cdiv(n, 1024), row_hi - row_lo);
-    if (narrow_index(st, pitch, n))
-        FLUID_BY_STORAGE(st, hipLaunchKernelGGL((k_advect2<S, unsigned>), grid, dim3(256), 0, s, (S*)da, (const S*)d0a, ba, (S*)db,
-                                                (const S*)d0b, bb, (const S*)u, (const S*)v, pitch, n, row_lo, row_hi, dt0));
-    else
-        FLUID_BY_STORAGE(st, hipLaunchKernelGGL((k_advect2<S, size_t>), grid, dim3(256), 0, s, (S*)da, (const S*)d0a, ba, (S*)db,
-                                                (const S*)d0b, bb, (const S*)u, (const S*)v, pitch, n, row_lo, row_hi, dt0));
+    FLUID_BY_STORAGE_INDEX(st, pitch, n, hipLaunchKernelGGL((k_advect2<S, I>), grid, dim3(256), 0, s, (S*)da, (const S*)d0a, ba, (S*)db,
+                                                            (const S*)d0b, bb, (const S*)u, (const S*)v, pitch, n, row_lo, row_hi, dt0));
 }
 
 void launch_divergence(hipStream_t s, int st, const void* u, const void* v, void* p, void* div, int pitch, int n,
@@ -1836,12 +1799,8 @@ void launch_gradient_advect(hipStream_t s, int st, void* u, void* v, const void*
 {
     if (row_hi <= row_lo) return;
     const dim3 grid(cdiv(n, 1024), row_hi - row_lo);
-    if (narrow_index(st, pitch, n))
-        FLUID_BY_STORAGE(st, hipLaunchKernelGGL((k_gradient_advect<S, unsigned>), grid, dim3(256), 0, s, (S*)u, (S*)v, (const S*)p,
-                                                (S*)d, (const S*)d0, pitch, n, row_lo, row_hi, h, dt0, b, pinv));
-    else
-        FLUID_BY_STORAGE(st, hipLaunchKernelGGL((k_gradient_advect<S, size_t>), grid, dim3(256), 0, s, (S*)u, (S*)v, (const S*)p,
-                                                (S*)d, (const S*)d0, pitch, n, row_lo, row_hi, h, dt0, b, pinv));
+    FLUID_BY_STORAGE_INDEX(st, pitch, n, hipLaunchKernelGGL((k_gradient_advect<S, I>), grid, dim3(256), 0, s, (S*)u, (S*)v, (const S*)p,
+                                                            (S*)d, (const S*)d0, pitch, n, row_lo, row_hi, h, dt0, b, pinv));
 }
 
 void launch_absmax2(hipStream_t s, int st, const void* u, const void* v, int pitch, int n, int row_lo, int row_hi,

@@ -436,7 +436,7 @@ int op_add_source(fluid_ctx* c, int x, int s, float dt, bool defer = false)
         TIMED(c, FLUID_TIME_SOURCE, fluid::launch_add_source(c->stream, c->st, c->ptr(x), nullptr, c->pitch, lo, hi, inc));
     } else {
         TRY(settle(c, s));                 // (a source that is itself owed something: never inside a step)
-        if (defer && c->fuse_add_source && c->variant == fluid::JACOBI_TB && c->tb_nv == 2) {
+        if (defer && c->fuse_add_source && c->variant == fluid::JACOBI_TB && fluid::jacobi_tb_exists(-1, -1, c->tb_nv, fluid::TB_ADDSRC)) {
             c->field[x].src_of = 1 + s;
             c->field[x].src_dt = dt;
             return FLUID_OK;               // x's reach unchanged: nothing was written
@@ -606,11 +606,11 @@ SweepShape sweep_shape(const fluid_ctx* c, int count)
 }
 
 // Sweeps fused into the next launch of a solve with `remaining` sweeps to go, of which `room` can run before rows must be
-// exchanged (slabs; = remaining on one GPU).  Depths 16 / 12 / 8 / 4 / 2 exist (2-column lanes, fp32 storage for 16 and
-// 12).  Per sweep the deep launches are the cheap ones where they pay at all, and a shallow remainder is dear (measured,
-// us per sweep of a pressure solve at 4096^2: 4.26 at 16, 4.05 at 12, 5.02 at 8; at 8192^2 13.6 / 16.3 / 23.5), so the
-// depths of a solve are PLANNED: the multiset of allowed depths that adds up to `remaining` at the least estimated cost,
-// deepest first -- 40 sweeps run as 16 + 12 + 12 rather than 16 + 16 + 8.
+// exchanged (slabs; = remaining on one GPU).  Depths 16 / 12 / 8 / 4 / 2 where kTbShapes has them in any division mode
+// (16 and 12: 2-column lanes), fp32 storage for 16 and 12.  Per sweep the deep launches are the cheap ones where they pay
+// at all, and a shallow remainder is dear (measured, us per sweep of a pressure solve at 4096^2: 4.26 at 16, 4.05 at 12,
+// 5.02 at 8; at 8192^2 13.6 / 16.3 / 23.5), so the depths of a solve are PLANNED: the multiset of allowed depths that adds
+// up to `remaining` at the least estimated cost, deepest first -- 40 sweeps run as 16 + 12 + 12 rather than 16 + 16 + 8.
 //   - 12 pays on grids (or slabs) of 8 M cells and more.  16 too, but for the general form (a double-precision multiply
 //     per cell: bound by arithmetic, which deeper blocking only adds to) only once a field outgrows the Infinity Cache
 //     (96 MiB rule), and it wants rows: on a 1024-row slab 12 beats it (3.3 against 3.8 us per sweep).
@@ -625,22 +625,26 @@ int pick_sweeps(const fluid_ctx* c, int remaining, int room, const SweepShape& s
     if (c->variant != fluid::JACOBI_TB || shape.small || c->field_bytes >= 0x7F000000ull) return 1;
     room = std::min(room, remaining);
     const int greedy = (room >= 8 && c->tb_max_t >= 8) ? 8 : (room >= 4 && c->tb_max_t >= 4) ? 4 : room >= 2 ? 2 : 1;
-    if (shape.canonical || c->tb_nv != 2 || c->tb_max_t < 12 || room < 12 || (remaining & 1)) return greedy;
+    if (shape.canonical || !fluid::jacobi_tb_exists(12, -1, c->tb_nv, fluid::TB_PLAIN) || c->tb_max_t < 12 || room < 12 || (remaining & 1)) return greedy;
     const bool forced = c->tb_t16_min_cells >= 0;
     const bool big = forced ? slab_cells >= c->tb_t16_min_cells : slab_cells >= (8ll << 20);
     if (!big) return greedy;
     const long long slab_rows = slab_cells / std::max(c->n, 1);
     // 16: the pressure form always; the general form once a field outgrows the Infinity Cache; never on short slabs
     const bool pays16 = forced || ((all_mode4 || (unsigned long long)slab_cells * c->esz > (96ull << 20)) && slab_rows >= 3000);
-    static const int depth[5] = {16, 12, 8, 4, 2};
-    static const double per_sweep[5] = {1.00, 1.04, 1.30, 2.6, 5.0};      // relative cost of one sweep at that depth
+    const int* depth = fluid::kTbDepths;
+    constexpr int nd = (int)std::size(fluid::kTbDepths);
+    static const double per_sweep[] = {1.00, 1.04, 1.30, 2.6, 5.0};      // relative cost of one sweep at that depth
+    static_assert(std::size(per_sweep) == nd, "one cost per depth");
     const double per_launch = 0.5;
-    bool allowed[5] = {c->tb_max_t >= 16 && pays16, true, c->tb_max_t >= 8, c->tb_max_t >= 4, true};
+    bool allowed[nd];
+    for (int k = 0; k < nd; ++k)
+        allowed[k] = depth[k] <= c->tb_max_t && (depth[k] != 16 || pays16) && fluid::jacobi_tb_exists(depth[k], -1, c->tb_nv, fluid::TB_PLAIN);
     // least cost to run exactly r sweeps (r even)
     std::vector<double> cost(remaining + 1, 1e300);
     cost[0] = 0.0;
     for (int r = 2; r <= remaining; r += 2)
-        for (int k = 0; k < 5; ++k) {
+        for (int k = 0; k < nd; ++k) {
             if (!allowed[k] || depth[k] > r) continue;
             const double v = cost[r - depth[k]] + depth[k] * per_sweep[k] + per_launch;
             if (v < cost[r] - 1e-9) cost[r] = v;
@@ -649,7 +653,7 @@ int pick_sweeps(const fluid_ctx* c, int remaining, int room, const SweepShape& s
     int best = 0;
     for (int r = remaining; r > 0;) {
         int pickd = 0;
-        for (int k = 0; k < 5 && !pickd; ++k)
+        for (int k = 0; k < nd && !pickd; ++k)
             if (allowed[k] && depth[k] <= r && std::fabs(cost[r - depth[k]] + depth[k] * per_sweep[k] + per_launch - cost[r]) < 1e-9)
                 pickd = depth[k];
         if (!pickd) break;
@@ -770,7 +774,7 @@ int batch_plan(fluid_ctx* c, Batch& B)
         const FieldState &x = c->field[sv[k].x], &x0 = c->field[sv[k].x0];
         add_src = add_src && x0.src_of == 1 + sv[k].x && x0.src_dt == x00.src_dt && !x.zero && !x.pend && !x.src_of;
     }
-    B.add_src = add_src && fluid::jacobi_tb_addsrc_exists(pick_sweeps(c, B.iters, B.iters, B.shape, B.all_mode4), B.plan[0].mode, c->tb_nv);
+    B.add_src = add_src && fluid::jacobi_tb_exists(pick_sweeps(c, B.iters, B.iters, B.shape, B.all_mode4), B.plan[0].mode, c->tb_nv, fluid::TB_ADDSRC);
     if (!B.add_src)
         for (int k = 0; k < B.count; ++k)
             if (c->field[sv[k].x0].src_of) {
@@ -880,6 +884,7 @@ int launch_fused(fluid_ctx* c, const fluid::TbBatch& bt, int T, int divmode, boo
     const int in_lo = owed && c->rank > 0 ? std::max(lo, c->own0 + T) : lo;
     const int in_hi = owed && c->rank < c->nranks - 1 ? std::min(hi, c->own1 - T) : hi;
     const bool split = owed && in_hi - in_lo >= 2 * T && (in_lo > lo || in_hi < hi);
+    const int form = divsrc ? fluid::TB_DIVSRC : addsrc ? fluid::TB_ADDSRC : fluid::TB_PLAIN;
     for (int part = split ? 0 : 1; part < 2; ++part) {     // 0: the interior of a split launch; 1: the rest (or all)
         const int plo = part ? lo : in_lo, phi = part ? hi : in_hi;
         const int hole_lo = part && split ? in_lo : 0, hole_hi = part && split ? in_hi : 0;
@@ -894,8 +899,9 @@ int launch_fused(fluid_ctx* c, const fluid::TbBatch& bt, int T, int divmode, boo
             rb = tune_pick(c, key, rb, T, rows_n, &trial);
         }
         if (trial >= 0) TRY(tune_begin(c, key, trial));
-        fluid::launch_jacobi_tb(c->stream, c->st, T, divmode, c->tb_nv, bt, c->pitch, c->n, plo, phi, rb, std::min(rb, edge_rows(c, T, rb)),
-                                divsrc, addsrc, hole_lo, hole_hi, c->tb_fill);
+        if (!fluid::launch_jacobi_tb(c->stream, c->st, T, divmode, c->tb_nv, form, bt, c->pitch, c->n, plo, phi, rb,
+                                     std::min(rb, edge_rows(c, T, rb)), hole_lo, hole_hi, c->tb_fill))
+            return fail(FLUID_E_INVALID, "no fused Jacobi kernel: %d sweeps, division mode %d, %d-column lanes, form %d", T, divmode, c->tb_nv, form);
         if (trial >= 0) TRY(tune_end(c));
     }
     if (split) c->split_launches += 1;
@@ -945,7 +951,7 @@ int batch_sweep(fluid_ctx* c, Batch& B)
             r = batch_reach(c, B);
         }
         const int T = canonical ? wantT : pick_sweeps(c, remaining, std::min(r, remaining), B.shape, B.all_mode4);
-        if (B.add_src && k == 0 && !fluid::jacobi_tb_addsrc_exists(T, B.plan[0].mode, c->tb_nv)) {
+        if (B.add_src && k == 0 && !fluid::jacobi_tb_exists(T, B.plan[0].mode, c->tb_nv, fluid::TB_ADDSRC)) {
             B.add_src = false;                   // a shallower first launch than planned (short reach): the kernel of its own after all
             TRY(xchg_join(c));
             for (int j = 0; j < B.count; ++j) TRY(settle_source(c, sv[j].x0));
@@ -1189,15 +1195,15 @@ struct AdvectAfter {
     float dt;
 };
 
-// can the divergence be computed inside the first launch of the pressure solve that follows it?  One GPU, the fused
-// kernel with 2-column lanes, a first launch of at least 8 sweeps, the exact-reciprocal division of (alpha 1, beta 4)
+// can the divergence be computed inside the first launch of the pressure solve that follows it?  The fused kernel, a first
+// launch of a shape that has a DIVSRC kernel (kTbShapes), the exact-reciprocal division of (alpha 1, beta 4)
 bool divergence_fuses(fluid_ctx* c, int iters, int reach)
 {
-    if (c->variant != fluid::JACOBI_TB || c->tb_nv != 2 || !c->fuse_divergence || iters < 8) return false;
+    if (c->variant != fluid::JACOBI_TB || !c->fuse_divergence) return false;
     const SweepShape shape = sweep_shape(c, 1);
     if (shape.small) return false;
     const int room = c->nranks > 1 ? std::min(reach + 1, iters) : iters;        // sweeps the first launch may fuse (op_diffuse_batch)
-    if (room < 8 || pick_sweeps(c, iters, room, shape, true) < 8) return false;
+    if (!fluid::jacobi_tb_exists(pick_sweeps(c, iters, room, shape, true), 4, c->tb_nv, fluid::TB_DIVSRC)) return false;
     return division_mode(c, 4.0f, 1.0f).mode == 4;
 }
 
@@ -1712,7 +1718,7 @@ int fluid_set_param(fluid_ctx* c, int key, int value)
     TRY(check_ctx(c));
     switch (key) {
     case FLUID_PARAM_TB_MAX_SWEEPS:
-        if (value != 16 && value != 12 && value != 8 && value != 4 && value != 2) return fail(FLUID_E_INVALID, "TB_MAX_SWEEPS must be 16, 12, 8, 4 or 2");
+        if (!fluid::is_tb_depth(value)) return fail(FLUID_E_INVALID, "TB_MAX_SWEEPS must be 16, 12, 8, 4 or 2");
         c->tb_max_t = value;
         return FLUID_OK;
     case FLUID_PARAM_TB_ROWS:
@@ -1783,8 +1789,7 @@ int fluid_plan_sweeps(int N, int rows, int storage, int pressure_form, int iters
     if (N < 1 || N > kMaxN || rows < 1 || rows > N || iters < 0 || (iters & 1) || !depths || !count || capacity < 0)
         return fail(FLUID_E_INVALID, "fluid_plan_sweeps: bad argument");
     if (storage != FLUID_STORAGE_F32 && storage != FLUID_STORAGE_F16) return fail(FLUID_E_INVALID, "unknown storage type %d", storage);
-    if (max_sweeps != 16 && max_sweeps != 12 && max_sweeps != 8 && max_sweeps != 4 && max_sweeps != 2)
-        return fail(FLUID_E_INVALID, "max_sweeps must be 16, 12, 8, 4 or 2");
+    if (!fluid::is_tb_depth(max_sweeps)) return fail(FLUID_E_INVALID, "max_sweeps must be 16, 12, 8, 4 or 2");
     fluid_ctx c;                            // host-side description only: no device, no stream
     c.n = N;
     c.st = storage;
