@@ -74,10 +74,11 @@ class FakeFabric:
         return cb
 
 
-def run_ranks(n, nranks, halo, fields, body, jacobi=0, storage=0, params=None):
-    """Run body(solver) on every fake rank; returns the gathered fields."""
+def run_ranks(n, nranks, halo, fields, body, jacobi=0, storage=0, params=None, fabric=FakeFabric):
+    """Run body(solver) on every fake rank; returns the gathered fields.  `fabric(nranks)`: the in-process transport
+    (test_gpu_slab_async.py passes one that leaves the rows in flight)."""
     from fluidsimulationcuda_amd.slab import SlabSolver
-    fab = FakeFabric(nranks)
+    fab = fabric(nranks)
     solvers = []
     for r in range(nranks):
         s = SlabSolver.__new__(SlabSolver)
