@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Tuning aid: time 40-sweep solves of the temporally blocked Jacobi kernel over
 strip heights (FLUID_PARAM_TB_ROWS) and sweeps per launch, one process, HIP
-events via the library's timing API.   python tools/tb_sweep.py [grid] [T...]"""
+events via the library's timing API (TB_F16=1: fp16 storage).   python tools/tb_sweep.py [grid] [T...]"""
 import os
 import sys
 
@@ -16,7 +16,8 @@ Ts = [int(x) for x in sys.argv[2:]] or [4, 8]
 n = grid - 2
 rng = np.random.default_rng(0)
 x = rng.random((n + 2, n + 2), dtype=np.float32)
-with F.FluidSolver(n, jacobi=capi.JACOBI_TB) as s:
+storage = capi.STORAGE_F16 if os.environ.get('TB_F16') else capi.STORAGE_F32
+with F.FluidSolver(n, jacobi=capi.JACOBI_TB, storage=storage) as s:
     s.upload(u=x, v=x)
     a, b = F.coefficients(n, 0.016, 0.0025)
     if os.environ.get('TB_NV'):
