@@ -52,8 +52,9 @@ enum {
 enum { FLUID_JACOBI_STREAM = 0, FLUID_JACOBI_LDS = 1, FLUID_JACOBI_NAIVE = 2, FLUID_JACOBI_TB = 3 };
 
 /* Tuning knobs for fluid_set_param(); none of them changes results with FLUID_STORAGE_F32.  (With FLUID_STORAGE_F16
- * a fused launch rounds once when it stores, so the launch schedule -- TB_MAX_SWEEPS, TB_MIN_CELLS -- is part of the
- * result there; all other knobs are speed only in both storage types.) */
+ * a fused launch rounds once when it stores, so the launch schedule -- TB_MAX_SWEEPS, TB_MIN_CELLS, and the Jacobi
+ * variant: FLUID_JACOBI_TB takes the greedy 8 / 4 / 2 sweeps per launch, the others one -- is part of the result there,
+ * and so is F16_PRESSURE_SCALE; all other knobs are speed only in both storage types.) */
 enum {
     FLUID_PARAM_TB_MAX_SWEEPS = 0, /* most sweeps fused per launch by FLUID_JACOBI_TB: 16 (default), 8, 4 or 2 */
     FLUID_PARAM_TB_ROWS = 1,       /* output rows per wave strip of FLUID_JACOBI_TB; 0 = auto          */
@@ -102,7 +103,9 @@ enum {
                                       projection are stored multiplied by 2^(floor(log2 N) - 2) -- plain, they are of the order
                                       h * |velocity| and fall into fp16's subnormal range from a few thousand cells per side
                                       on -- and divided back exactly (in the gradient subtraction; on the host when u_prev /
-                                      v_prev are downloaded).  0: plain values.  Changes fp16 results (not fp32 ones).      */
+                                      v_prev are downloaded).  Any other reader -- the add_source of a step with sources
+                                      after a step -- gets the field divided back in place and stored again, rounded to
+                                      fp16 a second time.  0: plain values.  Changes fp16 results (not fp32 ones).      */
     ,FLUID_PARAM_TB_FILL = 15      /* 1 (default): the fused kernel skips the stage evaluations of each strip's pipeline fill
                                       and drain that no stored row depends on (about T(T+1) of a strip's T(rows + 2T));
                                       0: every stage at every step.  Speed only.                                        */

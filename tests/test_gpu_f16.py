@@ -40,9 +40,11 @@ def launches(iters, max_t=8):
     return out
 
 
-def emu_solve(oracle, b, x, x0, alpha, beta, chunks):
-    x = h(x).copy()
-    x0 = h(x0)
+def emu_solve(oracle, b, x, x0, alpha, beta, chunks, store=h):
+    """one solve in launches of `chunks` sweeps (1: a single-sweep kernel), each launch's result stored through `store`
+    (the identity gives the fp32 solve: test_gpu_f16_steps.py)"""
+    x = store(x).copy()
+    x0 = store(x0)
     for t in chunks:
         if t == 1:
             out = np.zeros_like(x)
@@ -50,7 +52,7 @@ def emu_solve(oracle, b, x, x0, alpha, beta, chunks):
             x = out
         else:
             oracle.diffuse(b, x, x0, alpha, beta, t)
-        x = h(x)
+        x = store(x)
     return x
 
 
