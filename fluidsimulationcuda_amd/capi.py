@@ -71,6 +71,10 @@ SIGNATURES = {
     "fluid_layout": [_i, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_size_t)],
     "fluid_create": [_i, C.POINTER(_ctx)],
     "fluid_create_ex": [C.POINTER(Config), C.POINTER(_ctx)],
+    "fluid_create_ensemble": [C.POINTER(Config), _i, C.POINTER(_ctx)],
+    "fluid_members": [_ctx, C.POINTER(_i)],
+    "fluid_upload_member": [_ctx, _i, _i, _HOSTF],
+    "fluid_download_member": [_ctx, _i, _i, _HOSTF],
     "fluid_destroy": [_ctx],
     "fluid_synchronize": [_ctx],
     "fluid_owned_rows": [_ctx, C.POINTER(_i), C.POINTER(_i)],
@@ -114,7 +118,9 @@ SIGNATURES = {
 }
 # symbols with a non-status return type
 OTHER_SYMBOLS = {"fluid_last_error": (C.c_char_p, []), "fluid_arena_bytes": (C.c_size_t, [_i]),
-                 "fluid_arena_bytes_ex": (C.c_size_t, [_i, _i])}
+                 "fluid_arena_bytes_ex": (C.c_size_t, [_i, _i]),
+                 "fluid_arena_bytes_ensemble": (C.c_size_t, [_i, _i, _i])}
+MAX_MEMBERS = 21845
 
 _lib = None
 

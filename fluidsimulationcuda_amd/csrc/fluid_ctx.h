@@ -12,6 +12,7 @@
 namespace fluid_detail {
 int fail(int code, const char* fmt, ...);      // records the calling thread's error string, returns `code`
 int materialize_zero(fluid_ctx* c, int f);      // a field zero by definition gets its zeros in memory (fluid_solver.hip)
+int refuse_ensemble(const fluid_ctx* c, const char* what);   // FLUID_E_INVALID on a context of more than one member
 struct RcclExchange;                            // fluid_exchange_rccl.hip
 void rccl_release(RcclExchange* x);
 }  // namespace fluid_detail
@@ -32,6 +33,8 @@ void rccl_release(RcclExchange* x);
 
 // What one field's buffer holds beyond its memory (fluid_solver.hip: "row-slab bookkeeping", "fields that are zero by
 // definition").  Two fields trade buffers by trading the whole record; only wrote() and mark_zero() reset one.
+// An ensemble keeps ONE record per field id too: every member goes through the same calls, so what is owed or known of a
+// field is the same for all of them, and `ptr` is member 0's copy (member m: m * field_floats elements behind it).
 struct FieldState {
     void* ptr = nullptr;
     int reach = 0;            // rows past each inner slab edge that hold their owner's values (see "row-slab bookkeeping")
@@ -50,6 +53,8 @@ struct FieldState {
 struct fluid_ctx {
     int n = 0, w = 0, pitch = 0;
     size_t field_floats = 0;
+    int members = 1;                      // simulations in this context (fluid_create_ensemble): all of the same n, storage and
+                                          // knobs, all going through every call together; the arena is laid out [field][member]
     char* arena = nullptr;
     bool own_arena = false;
     int st = fluid::STORAGE_F32;          // field storage type
@@ -75,7 +80,7 @@ struct fluid_ctx {
     size_t field_bytes = 0;
     unsigned int* d_scalar = nullptr;     // device word for the reductions
     float* d_partials = nullptr;          // slabs: per-block maxima of the gradient subtraction (launch_subtract_gradient)
-    unsigned int* tiles = nullptr;        // 3 x tile_rows x tile_pitch words: |x0| minima per tile for division mode 3
+    unsigned int* tiles = nullptr;        // 3 x members x tile_rows x tile_pitch words: |x0| minima per tile for division mode 3
     unsigned int* h_scalar = nullptr;     // pinned host mirror
     hipEvent_t scalar_ready = nullptr;    // recorded behind the scalar's device-to-host copy
     int variant = fluid::JACOBI_TB;
@@ -117,6 +122,8 @@ struct fluid_ctx {
 
     bool valid_field(int id) const { return id >= 0 && id < FLUID_NFIELDS; }
     void* ptr(int id) const { return field[id].ptr; }
+    fluid::Members mb() const { return {members, field_floats}; }      // what every launch_* takes
+    size_t all_bytes() const { return field_bytes * (size_t)members; }   // one field in all its members (contiguous)
     void* row(int id, int r) const { return static_cast<char*>(ptr(id)) + (size_t)r * pitch * esz; }
     int lo_all() const { return own0 - (rank == 0 ? 1 : 0); }          // owned rows incl. ghost row
     int hi_all() const { return own1 + (rank == nranks - 1 ? 1 : 0); }

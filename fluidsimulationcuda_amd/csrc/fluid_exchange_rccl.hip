@@ -244,6 +244,7 @@ int fluid_rccl_unique_id(void* id, size_t bytes)
 int fluid_exchange_rccl_attach(fluid_ctx* c, const void* id, size_t bytes)
 {
     if (!c) return fail(FLUID_E_INVALID, "null context");
+    TRY(fluid_detail::refuse_ensemble(c, "fluid_exchange_rccl_attach"));
     if (!id || bytes < FLUID_RCCL_ID_BYTES) return fail(FLUID_E_INVALID, "fluid_exchange_rccl_attach: need the %d-byte id", FLUID_RCCL_ID_BYTES);
     RcclApi* api = rccl_api();
     if (!api->error.empty()) return fail(FLUID_E_COMM, "%s", api->error.c_str());
@@ -259,6 +260,7 @@ int fluid_exchange_rccl_attach(fluid_ctx* c, const void* id, size_t bytes)
 int fluid_exchange_rccl_attach_comm(fluid_ctx* c, void* nccl_comm)
 {
     if (!c || !nccl_comm) return fail(FLUID_E_INVALID, "null argument");
+    TRY(fluid_detail::refuse_ensemble(c, "fluid_exchange_rccl_attach_comm"));
     RcclApi* api = rccl_api();
     if (!api->error.empty()) return fail(FLUID_E_COMM, "%s", api->error.c_str());
     return attach(c, static_cast<ncclComm_t>(nccl_comm), false);
@@ -267,6 +269,7 @@ int fluid_exchange_rccl_attach_comm(fluid_ctx* c, void* nccl_comm)
 int fluid_exchange_rccl_detach(fluid_ctx* c)
 {
     if (!c) return fail(FLUID_E_INVALID, "null context");
+    TRY(fluid_detail::refuse_ensemble(c, "fluid_exchange_rccl_detach"));
     if (c->rccl) {
         if (c->stream) (void)hipStreamSynchronize(c->stream);
         if (c->xchg_user == c->rccl) {
@@ -282,6 +285,7 @@ int fluid_exchange_rccl_detach(fluid_ctx* c)
 int fluid_exchange_rccl_calls(fluid_ctx* c, long long* halo, long long* gather, long long* max)
 {
     if (!c) return fail(FLUID_E_INVALID, "null context");
+    TRY(fluid_detail::refuse_ensemble(c, "fluid_exchange_rccl_calls"));
     if (!c->rccl) return fail(FLUID_E_COMM, "no RCCL exchange attached");
     if (halo) *halo = c->rccl->calls[0];
     if (gather) *gather = c->rccl->calls[1];

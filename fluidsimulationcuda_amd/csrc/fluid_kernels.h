@@ -18,7 +18,17 @@ inline size_t storage_bytes(int st) { return st == STORAGE_F16 ? 2 : 4; }
 // right ghost, rounded to a multiple of 64 elements.
 inline int pitch_for(int n) { return ((XOFF + 1 + 4 * ((n + 3) / 4) + 1) + 63) / 64 * 64; }
 
-// up to three independent solves of the same shape, one per blockIdx.z of the fused Jacobi kernel
+// An ensemble: `count` members of every field, member m lying m * `stride` elements behind member 0 (fluid_ctx: fields are laid
+// out [field][member]).  Every launch below takes one and does to each member what it does to a single field: the member
+// index rides in the grid -- blockIdx.z of the kernels whose y is a row, blockIdx.y of the one-dimensional ones, blockIdx.z /
+// (solves per launch) of the fused Jacobi kernel -- so the number of launches does not depend on it.  {1, 0}: one simulation.
+struct Members {
+    int count = 1;
+    size_t stride = 0;
+};
+
+// up to three independent solves of the same shape, blockIdx.z % count of the fused Jacobi kernel (blockIdx.z / count: the
+// ensemble member, whose fields lie member * mstride elements behind the addresses given here)
 struct TbBatch {
     const void* x[3];
     const void* x0[3];
@@ -36,12 +46,15 @@ struct TbBatch {
     int x_zero[3];               // first guess known to be all +0: never read
     float x0_inc[3];             // added to every x0 value as it is loaded (-0.0f: nothing pending)
     int count;
+    int members;                 // ensemble members per solve (>= 1): gridDim.z = count * members
+    size_t mstride;              // elements between two members of a field
+    size_t tile_mstride;         // words between two members' tile minima (division mode 3)
 };
 
-void launch_set_bnd(hipStream_t s, int st, void* f, int pitch, int n, int b);
-void launch_add_source(hipStream_t s, int st, void* x, const void* src, int pitch, int row_lo, int row_hi, float dt);
+void launch_set_bnd(hipStream_t s, int st, void* f, int pitch, int n, int b, Members mb = {});
+void launch_add_source(hipStream_t s, int st, void* x, const void* src, int pitch, int row_lo, int row_hi, float dt, Members mb = {});
 void launch_jacobi(hipStream_t s, int st, int variant, const void* x, const void* x0, void* out, int pitch, int n,
-                   int row_lo, int row_hi, float alpha, float beta, int b);
+                   int row_lo, int row_hi, float alpha, float beta, int b, Members mb = {});
 // Shapes of the fused Jacobi kernel (k_jacobi_tb): sweeps T, division mode, columns per lane, and the form -- plain, the
 // first launch of a pressure solve that forms the divergence as its right-hand side (DIVSRC), or the first launch of a
 // diffusion that adds a deferred source to it (ADDSRC).  This table is the set of kernels built per storage type and the
@@ -86,30 +99,37 @@ bool launch_jacobi_tb(hipStream_t s, int st, int T, int divmode, int nv, int for
 constexpr int kTileRows = 32, kTileCols = 64;
 inline int tile_rows(int n) { return (n + kTileRows - 1) / kTileRows; }
 inline int tile_pitch(int n) { return (n + kTileCols - 1) / kTileCols; }
+// blockIdx.z = solve + count * member: a member's minima lie member * tile_mstride words behind tiles[solve]
 struct TileBatch {
     const void* field[3];
     unsigned* tiles[3];
+    int count;
+    size_t mstride, tile_mstride;
 };
-void launch_tile_min_abs(hipStream_t s, int st, const TileBatch& tb, int count, int pitch, int n, int row_lo, int row_hi, int tile_pitch);
+void launch_tile_min_abs(hipStream_t s, int st, const TileBatch& tb, int count, int pitch, int n, int row_lo, int row_hi, int tile_pitch,
+                         Members mb = {}, size_t tile_mstride = 0);
 void launch_validate_div(hipStream_t s, int divmode, float beta, float kbeta, double yd, float hi, float lo, unsigned long long* bad);
 void launch_advect(hipStream_t s, int st, void* d, const void* d0, const void* u, const void* v, int pitch, int n,
-                   int row_lo, int row_hi, float dt0, int b);
+                   int row_lo, int row_hi, float dt0, int b, Members mb = {});
 void launch_advect2(hipStream_t s, int st, void* da, const void* d0a, int ba, void* db, const void* d0b, int bb, const void* u,
-                    const void* v, int pitch, int n, int row_lo, int row_hi, float dt0);
+                    const void* v, int pitch, int n, int row_lo, int row_hi, float dt0, Members mb = {});
 // pscale: power of two the divergence is stored multiplied by (1: plain)
 void launch_divergence(hipStream_t s, int st, const void* u, const void* v, void* p, void* div, int pitch, int n,
-                       int row_lo, int row_hi, float h, int write_p, float pscale = 1.0f);
-void launch_scale(hipStream_t s, int st, void* x, int pitch, int row_lo, int row_hi, float factor);
+                       int row_lo, int row_hi, float h, int write_p, float pscale = 1.0f, Members mb = {});
+void launch_scale(hipStream_t s, int st, void* x, int pitch, int row_lo, int row_hi, float factor, Members mb = {});
 // max_out != nullptr: also leaves max(|u|, |v|) of the stored interior values in *max_out (the bit pattern of a
-// non-negative float; what launch_absmax2 would produce for the same rows), via `partials` (kMaxPartials floats of scratch)
+// non-negative float; what launch_absmax2 would produce for the same rows), via `partials` (kMaxPartials floats of scratch);
+// that form serves row slabs, which are never ensembles: one member only
 constexpr int kMaxPartials = 8192;
 void launch_subtract_gradient(hipStream_t s, int st, void* u, void* v, const void* p, int pitch, int n, int row_lo,
-                              int row_hi, float h, float* partials = nullptr, unsigned int* max_out = nullptr, float pinv = 1.0f);
+                              int row_hi, float h, float* partials = nullptr, unsigned int* max_out = nullptr, float pinv = 1.0f,
+                              Members mb = {});
 void launch_gradient_advect(hipStream_t s, int st, void* u, void* v, const void* p, void* d, const void* d0, int pitch, int n,
-                            int row_lo, int row_hi, float h, float dt0, int b, float pinv = 1.0f);
+                            int row_lo, int row_hi, float h, float dt0, int b, float pinv = 1.0f, Members mb = {});
+// (absmax2, residual: the maximum over all members -- every block ends in an atomicMax on the one word)
 void launch_absmax2(hipStream_t s, int st, const void* u, const void* v, int pitch, int n, int row_lo, int row_hi,
-                    unsigned int* result);
+                    unsigned int* result, Members mb = {});
 void launch_residual(hipStream_t s, int st, const void* x, const void* x0, int pitch, int n, int row_lo, int row_hi,
-                     float alpha, float beta, unsigned int* result);
+                     float alpha, float beta, unsigned int* result, Members mb = {});
 
 }  // namespace fluid

@@ -18,6 +18,11 @@
 // kernel applies the reference's set_bnd (FluidSequential.c:62-75) itself: the
 // thread that produces an interior cell next to a wall also writes the ghost
 // cell(s) derived from it, so no separate boundary launch is needed.
+//
+// Ensembles: every kernel that touches a field takes the member stride `ms` (elements between two members of a field) and
+// finds its member in the grid -- blockIdx.z where y is the row, blockIdx.y in the one-dimensional kernels, blockIdx.z /
+// (solves per launch) in the fused Jacobi kernel -- and adds member * ms to its field pointers first thing: scalar
+// arithmetic on the kernel arguments, after which the kernel is the one-simulation kernel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -140,10 +145,11 @@ __device__ __forceinline__ void emit_ghosts(S* __restrict__ f, size_t pitch, int
 // also writes the corners from the values it just produced.
 // ---------------------------------------------------------------------------
 template <typename S>
-__global__ __launch_bounds__(256) void k_set_bnd(S* __restrict__ f, int pitch, int n, int b)
+__global__ __launch_bounds__(256) void k_set_bnd(S* __restrict__ f, int pitch, int n, int b, size_t ms)
 {
     const int k = 1 + blockIdx.x * 256 + threadIdx.x;
     if (k > n) return;
+    f += blockIdx.y * ms;
     const size_t P = (size_t)pitch;
     const bool nx = (b == 1), ny = (b == 2);
     S* r0 = f + XOFF;
@@ -176,12 +182,12 @@ __global__ __launch_bounds__(256) void k_set_bnd(S* __restrict__ f, int pitch, i
 // ---------------------------------------------------------------------------
 template <typename S>
 __global__ __launch_bounds__(256) void k_add_source(S* __restrict__ x, const S* __restrict__ s, int pitch, int row_lo,
-                                                    int row_hi, float dt)
+                                                    int row_hi, float dt, size_t ms)
 {
     const int nvec = pitch >> 2;
     const size_t total = (size_t)(row_hi - row_lo) * nvec;
-    S* xv = x + (size_t)row_lo * pitch;
-    const S* sv = s + (size_t)row_lo * pitch;
+    S* xv = x + blockIdx.y * ms + (size_t)row_lo * pitch;
+    const S* sv = s + blockIdx.y * ms + (size_t)row_lo * pitch;
     for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
         float4 a = ld4(xv + 4 * t);
         const float4 c = ld4(sv + 4 * t);
@@ -196,11 +202,11 @@ __global__ __launch_bounds__(256) void k_add_source(S* __restrict__ x, const S* 
 // add_source when the source field is known to be all +0: x += inc with inc = dt*(+0)
 // formed on the host (so x = -0 still becomes +0 for dt >= 0, exactly as x + dt*0 does).
 template <typename S>
-__global__ __launch_bounds__(256) void k_add_zero_source(S* __restrict__ x, int pitch, int row_lo, int row_hi, float inc)
+__global__ __launch_bounds__(256) void k_add_zero_source(S* __restrict__ x, int pitch, int row_lo, int row_hi, float inc, size_t ms)
 {
     const int nvec = pitch >> 2;
     const size_t total = (size_t)(row_hi - row_lo) * nvec;
-    S* xv = x + (size_t)row_lo * pitch;
+    S* xv = x + blockIdx.y * ms + (size_t)row_lo * pitch;
     for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
         float4 a = ld4(xv + 4 * t);
         a.x = a.x + inc;
@@ -214,11 +220,11 @@ __global__ __launch_bounds__(256) void k_add_zero_source(S* __restrict__ x, int 
 // x *= factor on rows [row_lo, row_hi) (factor a power of two: how a field kept scaled -- the pressure and its right-hand
 // side with fp16 storage, see fluid_solver.hip: project -- goes back to its plain values for a reader that does not know)
 template <typename S>
-__global__ __launch_bounds__(256) void k_scale(S* __restrict__ x, int pitch, int row_lo, int row_hi, float factor)
+__global__ __launch_bounds__(256) void k_scale(S* __restrict__ x, int pitch, int row_lo, int row_hi, float factor, size_t ms)
 {
     const int nvec = pitch >> 2;
     const size_t total = (size_t)(row_hi - row_lo) * nvec;
-    S* xv = x + (size_t)row_lo * pitch;
+    S* xv = x + blockIdx.y * ms + (size_t)row_lo * pitch;
     for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
         float4 a = ld4(xv + 4 * t);
         a.x = a.x * factor;
@@ -240,11 +246,12 @@ __global__ __launch_bounds__(256) void k_scale(S* __restrict__ x, int pitch, int
 template <typename S>
 __global__ __launch_bounds__(256) void k_jacobi_naive(const S* __restrict__ x, const S* __restrict__ x0,
                                                       S* __restrict__ out, int pitch, int n, int row_lo,
-                                                      int row_hi, float alpha, float beta, int b)
+                                                      int row_hi, float alpha, float beta, int b, size_t ms)
 {
     const int j = 1 + blockIdx.x * 64 + (threadIdx.x & 63);
     const int i = row_lo + blockIdx.y * 4 + (threadIdx.x >> 6);
     if (j > n || i >= row_hi) return;
+    x += blockIdx.z * ms; x0 += blockIdx.z * ms; out += blockIdx.z * ms;
     const size_t P = (size_t)pitch;
     const S* c = x + (size_t)i * P + XOFF + j;
     float nb = ld1(c - 1) + ld1(c + 1);
@@ -262,9 +269,10 @@ constexpr int LT_X = 64, LT_Y = 16;
 template <typename S>
 __global__ __launch_bounds__(256) void k_jacobi_lds(const S* __restrict__ x, const S* __restrict__ x0,
                                                     S* __restrict__ out, int pitch, int n, int row_lo,
-                                                    int row_hi, float alpha, float beta, int b)
+                                                    int row_hi, float alpha, float beta, int b, size_t ms)
 {
     __shared__ float tile[LT_Y + 2][LT_X + 2 + 1];
+    x += blockIdx.z * ms; x0 += blockIdx.z * ms; out += blockIdx.z * ms;
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;      // ty in 0..3
     const int j0 = 1 + blockIdx.x * LT_X, i0 = row_lo + blockIdx.y * LT_Y;
     const int j = j0 + tx;
@@ -306,8 +314,9 @@ __global__ __launch_bounds__(256) void k_jacobi_lds(const S* __restrict__ x, con
 template <int RB, typename S>
 __global__ __launch_bounds__(256) void k_jacobi_stream(const S* __restrict__ x, const S* __restrict__ x0,
                                                        S* __restrict__ out, int pitch, int n, int row_lo,
-                                                       int row_hi, float alpha, float beta, int b)
+                                                       int row_hi, float alpha, float beta, int b, size_t ms)
 {
+    x += blockIdx.z * ms; x0 += blockIdx.z * ms; out += blockIdx.z * ms;
     const int lane = threadIdx.x & 63;
     const int vec = blockIdx.x * 256 + threadIdx.x;     // float4 index along the row
     const int nvec = (n + 3) >> 2;
@@ -1007,7 +1016,10 @@ struct TbGrid {
 constexpr int tb_waves_per_simd(int T, int NV) { return NV == 2 ? (T <= 8 ? 4 : T <= 12 ? 3 : 2) : (T <= 4 ? 3 : 2); }
 
 // blockIdx.z picks one of up to three independent solves of the same shape (u, v and density
-// diffusion): more waves per launch, hence taller strips and less pipeline-fill redundancy.
+// diffusion): more waves per launch, hence taller strips and less pipeline-fill redundancy -- and, in an ensemble, one
+// member: z = solve + count * member.  gridDim.x is a multiple of 8, so the XCD renumbering sees the same thing in every
+// z-slice.  The member's offset goes into the field pointers before the buffer descriptors are made (scalar arithmetic);
+// nothing in the march knows of it.
 template <int T, int DIVMODE, int NV, typename S, bool DIVSRC = false, bool ADDSRC = false>
 __global__ __launch_bounds__(256, tb_waves_per_simd(T, NV)) void k_jacobi_tb(TbBatch batch, int pitch, int n, int row_lo,
                                                                              int row_hi, int rb, int rb_edge, TbGrid g, int fill)
@@ -1035,12 +1047,16 @@ __global__ __launch_bounds__(256, tb_waves_per_simd(T, NV)) void k_jacobi_tb(TbB
         strip_group = (int)(vid / (unsigned)g.edge_wins);
         win = e == 0 ? 0 : g.first_right + e - 1;
     }
-    const S* __restrict__ x = static_cast<const S*>(batch.x[blockIdx.z]);
-    const S* __restrict__ x0 = static_cast<const S*>(batch.x0[blockIdx.z]);
-    S* __restrict__ out = static_cast<S*>(batch.out[blockIdx.z]);
-    const float alpha = batch.alpha[blockIdx.z], beta = batch.beta[blockIdx.z];
-    const double yd = batch.yd[blockIdx.z];
-    const int b = batch.b[blockIdx.z];
+    // (count is 1, 2 or 3: divisions by constants, not by a run-time value)
+    const unsigned member = batch.count == 3 ? blockIdx.z / 3u : batch.count == 2 ? blockIdx.z >> 1 : blockIdx.z;
+    const unsigned sv = blockIdx.z - member * (unsigned)batch.count;
+    const size_t mofs = (size_t)member * batch.mstride;
+    const S* __restrict__ x = static_cast<const S*>(batch.x[sv]) + mofs;
+    const S* __restrict__ x0 = static_cast<const S*>(batch.x0[sv]) + mofs;
+    S* __restrict__ out = static_cast<S*>(batch.out[sv]) + mofs;
+    const float alpha = batch.alpha[sv], beta = batch.beta[sv];
+    const double yd = batch.yd[sv];
+    const int b = batch.b[sv];
     constexpr int HL = (T + NV - 1) / NV;                // lanes of overlap per side: T columns
     constexpr int VS = 64 - 2 * HL;
     constexpr int C0 = (XOFF + 1) / NV;                  // vector index of column 1 within a row
@@ -1058,9 +1074,9 @@ __global__ __launch_bounds__(256, tb_waves_per_simd(T, NV)) void k_jacobi_tb(TbB
     const int rbw = edge ? rb_edge : rb;
     TbArgs<S, NV> a;
     a.k.yd = yd;
-    a.k.lo = batch.lo[blockIdx.z];
-    a.k.hi = batch.hi[blockIdx.z];
-    a.x0_inc = batch.x0_inc[blockIdx.z];
+    a.k.lo = batch.lo[sv];
+    a.k.hi = batch.hi[sv];
+    a.x0_inc = batch.x0_inc[sv];
     int seg_hi = row_hi;                                 // this wave's output rows [q_lo, q_hi): strips do not straddle the hole
     a.q_lo = row_lo + strip * rbw;
     if (g.hole_lo < g.hole_hi) {
@@ -1084,10 +1100,10 @@ __global__ __launch_bounds__(256, tb_waves_per_simd(T, NV)) void k_jacobi_tb(TbB
         // a first guess known to be all +0 (sources after step 0, the pressure) is never read: an
         // empty descriptor makes every load of it return 0
         // (DIVSRC: x and x0 are u and v, both read; the first guess is +0 by definition and lives nowhere)
-        a.bx = __builtin_amdgcn_make_buffer_rsrc(const_cast<S*>(x), 0, (batch.x_zero[blockIdx.z] && !DIVSRC) ? 0u : field_bytes, 0x00020000);
+        a.bx = __builtin_amdgcn_make_buffer_rsrc(const_cast<S*>(x), 0, (batch.x_zero[sv] && !DIVSRC) ? 0u : field_bytes, 0x00020000);
         a.br = __builtin_amdgcn_make_buffer_rsrc(const_cast<S*>(x0), 0, field_bytes, 0x00020000);
         a.bo = __builtin_amdgcn_make_buffer_rsrc(out, 0, field_bytes, 0x00020000);
-        S* dv = (DIVSRC || ADDSRC) ? static_cast<S*>(batch.div[blockIdx.z]) : out;
+        S* dv = (DIVSRC || ADDSRC) ? static_cast<S*>(batch.div[sv]) + mofs : out;
         a.dc = dv + cofs;
         a.bd = __builtin_amdgcn_make_buffer_rsrc(dv, 0, field_bytes, 0x00020000);
         a.div_scale = batch.div_scale;
@@ -1123,8 +1139,9 @@ __global__ __launch_bounds__(256, tb_waves_per_simd(T, NV)) void k_jacobi_tb(TbB
         // above): the x0 rows q_lo-T+1 .. q_hi+T-2 are the ones that reach a cell this wave stores, the columns are
         // those of its 64 * NV lanes; both clipped to the interior (ghost cells repeat interior values, and what
         // lanes past the row's ends compute is never stored)
-        const unsigned* __restrict__ tiles = batch.tiles[blockIdx.z];
-        const unsigned thr = batch.tile_thr[blockIdx.z];
+        // this member's own minima: a wave never takes the two-term path on the strength of another member's
+        const unsigned* __restrict__ tiles = batch.tiles[sv] ? batch.tiles[sv] + (size_t)member * batch.tile_mstride : nullptr;
+        const unsigned thr = batch.tile_thr[sv];
         const int tr0 = (max(1, a.q_lo - T + 1) - 1) / kTileRows, tr1 = (min(n, a.q_hi + T - 2) - 1) / kTileRows;
         const int c0 = max(1, 1 + NV * (win * VS - HL)), c1 = min(n, NV * (win * VS - HL + 64));
         const int tc0 = (c0 - 1) / kTileCols, tc1 = (c1 - 1) / kTileCols, ntc = tc1 - tc0 + 1;
@@ -1153,8 +1170,9 @@ __global__ __launch_bounds__(256, tb_waves_per_simd(T, NV)) void k_jacobi_tb(TbB
 template <typename S>
 __global__ __launch_bounds__(256) void k_tile_min_abs(TileBatch tb, int pitch, int n, int row_lo, int row_hi, int tile_row0, int tile_pitch)
 {
-    const S* __restrict__ f = static_cast<const S*>(tb.field[blockIdx.z]);
-    unsigned* __restrict__ out = tb.tiles[blockIdx.z];
+    const unsigned member = blockIdx.z / (unsigned)tb.count, sv = blockIdx.z - member * (unsigned)tb.count;
+    const S* __restrict__ f = static_cast<const S*>(tb.field[sv]) + (size_t)member * tb.mstride;
+    unsigned* __restrict__ out = tb.tiles[sv] + (size_t)member * tb.tile_mstride;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int tr = tile_row0 + blockIdx.y;
     const int j = 1 + 4 * (lane + 64 * (blockIdx.x * 4 + wave));         // first of this lane's four columns
@@ -1311,9 +1329,11 @@ __device__ __forceinline__ void wave_cells_out(S* __restrict__ p, int cells, flo
 template <typename S, typename IDX>
 __global__ __launch_bounds__(256) void k_advect(S* __restrict__ d, const S* __restrict__ d0, const S* __restrict__ u,
                                                 const S* __restrict__ v, int pitch, int n, int row_lo, int row_hi,
-                                                float dt0, int b)
+                                                float dt0, int b, size_t ms)
 {
     __shared__ __attribute__((aligned(16))) float tiles[4][2][256];
+    // the member's offset goes into the scalar bases: the offsets' width (IDX) depends on one field's size only
+    d += blockIdx.z * ms; d0 += blockIdx.z * ms; u += blockIdx.z * ms; v += blockIdx.z * ms;
     const int j0 = advect_col0();
     const int i = row_lo + blockIdx.y;
     if (i >= row_hi) return;
@@ -1345,9 +1365,10 @@ __global__ __launch_bounds__(256) void k_advect(S* __restrict__ d, const S* __re
 template <typename S, typename IDX>
 __global__ __launch_bounds__(256) void k_advect2(S* __restrict__ da, const S* __restrict__ d0a, int ba, S* __restrict__ db,
                                                  const S* __restrict__ d0b, int bb, const S* __restrict__ u,
-                                                 const S* __restrict__ v, int pitch, int n, int row_lo, int row_hi, float dt0)
+                                                 const S* __restrict__ v, int pitch, int n, int row_lo, int row_hi, float dt0, size_t ms)
 {
     __shared__ __attribute__((aligned(16))) float tiles[4][2][256];
+    da += blockIdx.z * ms; d0a += blockIdx.z * ms; db += blockIdx.z * ms; d0b += blockIdx.z * ms; u += blockIdx.z * ms; v += blockIdx.z * ms;
     const int j0 = advect_col0();
     const int i = row_lo + blockIdx.y;
     if (i >= row_hi) return;
@@ -1389,11 +1410,12 @@ __global__ __launch_bounds__(256) void k_advect2(S* __restrict__ da, const S* __
 template <typename S>
 __global__ __launch_bounds__(256) void k_divergence(const S* __restrict__ u, const S* __restrict__ v, S* __restrict__ p,
                                                     S* __restrict__ div, int pitch, int n, int row_lo, int row_hi,
-                                                    float h, int write_p, float pscale)
+                                                    float h, int write_p, float pscale, size_t ms)
 {
     const int j = 1 + blockIdx.x * 256 + threadIdx.x;
     const int i = row_lo + blockIdx.y;
     if (j > n || i >= row_hi) return;
+    u += blockIdx.z * ms; v += blockIdx.z * ms; p += blockIdx.z * ms; div += blockIdx.z * ms;
     const size_t P = (size_t)pitch;
     const size_t c = (size_t)i * P + XOFF + j;
     const float scale = (-0.5f * h) * pscale;            // pscale: a power of two (1 unless the solver keeps a scaled pressure, fp16 storage)
@@ -1423,11 +1445,12 @@ __device__ __forceinline__ float wave_max(float m)
 // ---------------------------------------------------------------------------
 template <typename S>
 __global__ __launch_bounds__(256) void k_subtract_gradient(S* __restrict__ u, S* __restrict__ v, const S* __restrict__ p,
-                                                           int pitch, int n, int row_lo, int row_hi, float h, float pinv)
+                                                           int pitch, int n, int row_lo, int row_hi, float h, float pinv, size_t ms)
 {
     const int j = 1 + blockIdx.x * 256 + threadIdx.x;
     const int i = row_lo + blockIdx.y;
     if (j > n || i >= row_hi) return;
+    u += blockIdx.z * ms; v += blockIdx.z * ms; p += blockIdx.z * ms;
     const size_t P = (size_t)pitch;
     const size_t c = (size_t)i * P + XOFF + j;
     const float gx = 0.5f * (ld1(p + c + 1) - ld1(p + c - 1));
@@ -1494,8 +1517,9 @@ __global__ __launch_bounds__(256) void k_max_partials(const float* __restrict__ 
 template <typename S, typename IDX>
 __global__ __launch_bounds__(256) void k_gradient_advect(S* __restrict__ u, S* __restrict__ v, const S* __restrict__ p,
                                                          S* __restrict__ d, const S* __restrict__ d0, int pitch, int n,
-                                                         int row_lo, int row_hi, float h, float dt0, int b, float pinv)
+                                                         int row_lo, int row_hi, float h, float dt0, int b, float pinv, size_t ms)
 {
+    u += blockIdx.z * ms; v += blockIdx.z * ms; p += blockIdx.z * ms; d += blockIdx.z * ms; d0 += blockIdx.z * ms;
     const int j0 = advect_col0();
     const int i = row_lo + blockIdx.y;
     if (i >= row_hi) return;
@@ -1562,8 +1586,9 @@ __device__ __forceinline__ void block_max_to(unsigned int* __restrict__ result, 
 // one workgroup per group of rows, whole float4 vectors (columns beyond 1..n masked out)
 template <typename S>
 __global__ __launch_bounds__(256) void k_absmax2(const S* __restrict__ u, const S* __restrict__ v, int pitch, int n,
-                                                 int row_lo, int row_hi, unsigned int* __restrict__ result)
+                                                 int row_lo, int row_hi, unsigned int* __restrict__ result, size_t ms)
 {
+    u += blockIdx.y * ms; v += blockIdx.y * ms;
     const size_t P = (size_t)pitch;
     const int nvec = (n + 3) >> 2;
     float m = 0.0f;
@@ -1584,8 +1609,9 @@ __global__ __launch_bounds__(256) void k_absmax2(const S* __restrict__ u, const 
 template <typename S>
 __global__ __launch_bounds__(256) void k_residual(const S* __restrict__ x, const S* __restrict__ x0, int pitch, int n,
                                                   int row_lo, int row_hi, float alpha, float beta,
-                                                  unsigned int* __restrict__ result)
+                                                  unsigned int* __restrict__ result, size_t ms)
 {
+    x += blockIdx.y * ms; x0 += blockIdx.y * ms;
     const size_t P = (size_t)pitch;
     float m = 0.0f;
     for (int i = row_lo + blockIdx.x; i < row_hi; i += gridDim.x)
@@ -1629,50 +1655,50 @@ static inline unsigned stride_blocks(int pitch, int row_lo, int row_hi)
     return (unsigned)std::clamp<size_t>(((size_t)(row_hi - row_lo) * (pitch >> 2) + 255) / 256, 1, 8192);
 }
 
-void launch_set_bnd(hipStream_t s, int st, void* f, int pitch, int n, int b)
+void launch_set_bnd(hipStream_t s, int st, void* f, int pitch, int n, int b, Members mb)
 {
-    FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_set_bnd<S>, dim3(cdiv(n, 256)), dim3(256), 0, s, (S*)f, pitch, n, b));
+    FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_set_bnd<S>, dim3(cdiv(n, 256), mb.count), dim3(256), 0, s, (S*)f, pitch, n, b, mb.stride));
 }
 
 // src == nullptr: the source is known to be all +0 (dt is then the pre-multiplied increment dt*0)
-void launch_add_source(hipStream_t s, int st, void* x, const void* src, int pitch, int row_lo, int row_hi, float dt)
+void launch_add_source(hipStream_t s, int st, void* x, const void* src, int pitch, int row_lo, int row_hi, float dt, Members mb)
 {
-    const unsigned blocks = stride_blocks(pitch, row_lo, row_hi);
+    const dim3 grid(stride_blocks(pitch, row_lo, row_hi), mb.count);
     if (!src) {
-        FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_add_zero_source<S>, dim3(blocks), dim3(256), 0, s, (S*)x, pitch, row_lo, row_hi, dt));
+        FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_add_zero_source<S>, grid, dim3(256), 0, s, (S*)x, pitch, row_lo, row_hi, dt, mb.stride));
         return;
     }
-    FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_add_source<S>, dim3(blocks), dim3(256), 0, s, (S*)x, (const S*)src, pitch, row_lo, row_hi, dt));
+    FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_add_source<S>, grid, dim3(256), 0, s, (S*)x, (const S*)src, pitch, row_lo, row_hi, dt, mb.stride));
 }
 
-void launch_scale(hipStream_t s, int st, void* x, int pitch, int row_lo, int row_hi, float factor)
+void launch_scale(hipStream_t s, int st, void* x, int pitch, int row_lo, int row_hi, float factor, Members mb)
 {
-    FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_scale<S>, dim3(stride_blocks(pitch, row_lo, row_hi)), dim3(256), 0, s, (S*)x, pitch,
-                                            row_lo, row_hi, factor));
+    FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_scale<S>, dim3(stride_blocks(pitch, row_lo, row_hi), mb.count), dim3(256), 0, s, (S*)x, pitch,
+                                            row_lo, row_hi, factor, mb.stride));
 }
 
 void launch_jacobi(hipStream_t s, int st, int variant, const void* x, const void* x0, void* out, int pitch, int n,
-                   int row_lo, int row_hi, float alpha, float beta, int b)
+                   int row_lo, int row_hi, float alpha, float beta, int b, Members mb)
 {
     const int rows = row_hi - row_lo;
     if (rows <= 0) return;
     switch (variant) {
     case JACOBI_NAIVE:
-        FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_jacobi_naive<S>, dim3(cdiv(n, 64), cdiv(rows, 4)), dim3(256), 0, s,
+        FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_jacobi_naive<S>, dim3(cdiv(n, 64), cdiv(rows, 4), mb.count), dim3(256), 0, s,
                                                 (const S*)x, (const S*)x0, (S*)out, pitch, n, row_lo, row_hi, alpha,
-                                                beta, b));
+                                                beta, b, mb.stride));
         break;
     case JACOBI_LDS:
-        FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_jacobi_lds<S>, dim3(cdiv(n, LT_X), cdiv(rows, LT_Y)), dim3(256), 0, s,
+        FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_jacobi_lds<S>, dim3(cdiv(n, LT_X), cdiv(rows, LT_Y), mb.count), dim3(256), 0, s,
                                                 (const S*)x, (const S*)x0, (S*)out, pitch, n, row_lo, row_hi, alpha,
-                                                beta, b));
+                                                beta, b, mb.stride));
         break;
     default: {
         constexpr int RB = 8;
         const unsigned nvec = (n + 3) / 4;
-        FLUID_BY_STORAGE(st, hipLaunchKernelGGL((k_jacobi_stream<RB, S>), dim3(cdiv(nvec, 256), cdiv(rows, RB)), dim3(256),
+        FLUID_BY_STORAGE(st, hipLaunchKernelGGL((k_jacobi_stream<RB, S>), dim3(cdiv(nvec, 256), cdiv(rows, RB), mb.count), dim3(256),
                                                 0, s, (const S*)x, (const S*)x0, (S*)out, pitch, n, row_lo, row_hi,
-                                                alpha, beta, b));
+                                                alpha, beta, b, mb.stride));
     }
     }
 }
@@ -1698,7 +1724,7 @@ bool launch_jacobi_tb(hipStream_t s, int st, int T, int divmode, int nv, int for
     const int shape = jacobi_tb_index(T, divmode, nv, form);
     if (shape < 0) return false;
     const int rows = row_hi - row_lo;
-    if (rows <= 0 || batch.count <= 0) return true;
+    if (rows <= 0 || batch.count <= 0 || batch.members <= 0) return true;
     if (hole_lo < row_lo) hole_lo = row_lo;
     if (hole_hi > row_hi) hole_hi = row_hi;
     const bool hole = hole_lo < hole_hi;
@@ -1721,20 +1747,26 @@ bool launch_jacobi_tb(hipStream_t s, int st, int T, int divmode, int nv, int for
     g.hole_hi = hole ? hole_hi : 0;
     g.inner_blocks = g.inner_wins * (int)cdiv(strips(rb), 4);
     g.edge_blocks = g.edge_wins * (int)cdiv(strips(rb_edge), 4);
-    const dim3 grid(8 * cdiv(g.inner_blocks + g.edge_blocks, 8), 1, batch.count), block(256);
+    const dim3 grid(8 * cdiv(g.inner_blocks + g.edge_blocks, 8), 1, batch.count * batch.members), block(256);
     const TbKernel k = (st == STORAGE_F16 ? f16 : f32)[shape];
     hipLaunchKernelGGL(k, grid, block, 0, s, batch, pitch, n, row_lo, row_hi, rb, rb_edge, g, fill ? 1 : 0);
     return true;
 }
 
 // tiles of |x0| minima for division mode 3, rows [row_lo, row_hi) within 1..n+1; tb.tiles[k] holds tile_rows(n) x tile_pitch words
-void launch_tile_min_abs(hipStream_t s, int st, const TileBatch& tb, int count, int pitch, int n, int row_lo, int row_hi, int tile_pitch)
+// per member: member m's minima lie m * tile_mstride words behind them
+void launch_tile_min_abs(hipStream_t s, int st, const TileBatch& tiles, int count, int pitch, int n, int row_lo, int row_hi, int tile_pitch,
+                         Members mb, size_t tile_mstride)
 {
     if (row_lo < 1) row_lo = 1;
     if (row_hi > n + 1) row_hi = n + 1;
     if (row_hi <= row_lo || count <= 0) return;
     const int tr0 = (row_lo - 1) / kTileRows, tr1 = (row_hi - 2) / kTileRows;
-    const dim3 grid(cdiv(cdiv(n, 4), 256), tr1 - tr0 + 1, count);
+    const dim3 grid(cdiv(cdiv(n, 4), 256), tr1 - tr0 + 1, count * mb.count);
+    TileBatch tb = tiles;
+    tb.count = count;
+    tb.mstride = mb.stride;
+    tb.tile_mstride = tile_mstride;
     FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_tile_min_abs<S>, grid, dim3(256), 0, s, tb, pitch, n, row_lo, row_hi, tr0, tile_pitch));
 }
 
@@ -1752,37 +1784,37 @@ void launch_validate_div(hipStream_t s, int divmode, float beta, float kbeta, do
 }
 
 void launch_advect(hipStream_t s, int st, void* d, const void* d0, const void* u, const void* v, int pitch, int n,
-                   int row_lo, int row_hi, float dt0, int b)
+                   int row_lo, int row_hi, float dt0, int b, Members mb)
 {
     if (row_hi <= row_lo) return;
-    const dim3 grid(cdiv(n, 1024), row_hi - row_lo);
+    const dim3 grid(cdiv(n, 1024), row_hi - row_lo, mb.count);
     FLUID_BY_STORAGE_INDEX(st, pitch, n, hipLaunchKernelGGL((k_advect<S, I>), grid, dim3(256), 0, s, (S*)d, (const S*)d0, (const S*)u,
-                                                            (const S*)v, pitch, n, row_lo, row_hi, dt0, b));
+                                                            (const S*)v, pitch, n, row_lo, row_hi, dt0, b, mb.stride));
 }
 
 void launch_advect2(hipStream_t s, int st, void* da, const void* d0a, int ba, void* db, const void* d0b, int bb, const void* u,
-                    const void* v, int pitch, int n, int row_lo, int row_hi, float dt0)
+                    const void* v, int pitch, int n, int row_lo, int row_hi, float dt0, Members mb)
 {
     if (row_hi <= row_lo) return;
-    const dim3 grid(cdiv(n, 1024), row_hi - row_lo);
+    const dim3 grid(cdiv(n, 1024), row_hi - row_lo, mb.count);
     FLUID_BY_STORAGE_INDEX(st, pitch, n, hipLaunchKernelGGL((k_advect2<S, I>), grid, dim3(256), 0, s, (S*)da, (const S*)d0a, ba, (S*)db,
-                                                            (const S*)d0b, bb, (const S*)u, (const S*)v, pitch, n, row_lo, row_hi, dt0));
+                                                            (const S*)d0b, bb, (const S*)u, (const S*)v, pitch, n, row_lo, row_hi, dt0, mb.stride));
 }
 
 void launch_divergence(hipStream_t s, int st, const void* u, const void* v, void* p, void* div, int pitch, int n,
-                       int row_lo, int row_hi, float h, int write_p, float pscale)
+                       int row_lo, int row_hi, float h, int write_p, float pscale, Members mb)
 {
     if (row_hi <= row_lo) return;
-    FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_divergence<S>, dim3(cdiv(n, 256), row_hi - row_lo), dim3(256), 0, s,
+    FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_divergence<S>, dim3(cdiv(n, 256), row_hi - row_lo, mb.count), dim3(256), 0, s,
                                             (const S*)u, (const S*)v, (S*)p, (S*)div, pitch, n, row_lo, row_hi, h,
-                                            write_p, pscale));
+                                            write_p, pscale, mb.stride));
 }
 
 void launch_subtract_gradient(hipStream_t s, int st, void* u, void* v, const void* p, int pitch, int n, int row_lo,
-                              int row_hi, float h, float* partials, unsigned int* max_out, float pinv)
+                              int row_hi, float h, float* partials, unsigned int* max_out, float pinv, Members mb)
 {
     if (row_hi <= row_lo) return;
-    if (max_out) {
+    if (max_out && mb.count == 1) {          // (slabs: one member)
         const unsigned per_col = cdiv(n, 256), rows = (unsigned)(row_hi - row_lo);
         const unsigned gy = std::max(1u, std::min(rows, (unsigned)kMaxPartials / per_col));     // a few rows per block
         FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_subtract_gradient_max<S>, dim3(per_col, gy), dim3(256), 0, s, (S*)u, (S*)v,
@@ -1790,35 +1822,35 @@ void launch_subtract_gradient(hipStream_t s, int st, void* u, void* v, const voi
         hipLaunchKernelGGL(k_max_partials, dim3(1), dim3(256), 0, s, partials, (int)(per_col * gy), max_out);
         return;
     }
-    FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_subtract_gradient<S>, dim3(cdiv(n, 256), row_hi - row_lo), dim3(256), 0, s,
-                                            (S*)u, (S*)v, (const S*)p, pitch, n, row_lo, row_hi, h, pinv));
+    FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_subtract_gradient<S>, dim3(cdiv(n, 256), row_hi - row_lo, mb.count), dim3(256), 0, s,
+                                            (S*)u, (S*)v, (const S*)p, pitch, n, row_lo, row_hi, h, pinv, mb.stride));
 }
 
 void launch_gradient_advect(hipStream_t s, int st, void* u, void* v, const void* p, void* d, const void* d0, int pitch, int n,
-                            int row_lo, int row_hi, float h, float dt0, int b, float pinv)
+                            int row_lo, int row_hi, float h, float dt0, int b, float pinv, Members mb)
 {
     if (row_hi <= row_lo) return;
-    const dim3 grid(cdiv(n, 1024), row_hi - row_lo);
+    const dim3 grid(cdiv(n, 1024), row_hi - row_lo, mb.count);
     FLUID_BY_STORAGE_INDEX(st, pitch, n, hipLaunchKernelGGL((k_gradient_advect<S, I>), grid, dim3(256), 0, s, (S*)u, (S*)v, (const S*)p,
-                                                            (S*)d, (const S*)d0, pitch, n, row_lo, row_hi, h, dt0, b, pinv));
+                                                            (S*)d, (const S*)d0, pitch, n, row_lo, row_hi, h, dt0, b, pinv, mb.stride));
 }
 
 void launch_absmax2(hipStream_t s, int st, const void* u, const void* v, int pitch, int n, int row_lo, int row_hi,
-                    unsigned int* result)
+                    unsigned int* result, Members mb)
 {
     if (row_hi <= row_lo) return;
     const unsigned blocks = (unsigned)(row_hi - row_lo) < 1024u ? (unsigned)(row_hi - row_lo) : 1024u;
-    FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_absmax2<S>, dim3(blocks), dim3(256), 0, s, (const S*)u, (const S*)v, pitch,
-                                            n, row_lo, row_hi, result));
+    FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_absmax2<S>, dim3(blocks, mb.count), dim3(256), 0, s, (const S*)u, (const S*)v, pitch,
+                                            n, row_lo, row_hi, result, mb.stride));
 }
 
 void launch_residual(hipStream_t s, int st, const void* x, const void* x0, int pitch, int n, int row_lo, int row_hi,
-                     float alpha, float beta, unsigned int* result)
+                     float alpha, float beta, unsigned int* result, Members mb)
 {
     if (row_hi <= row_lo) return;
     const unsigned blocks = (unsigned)(row_hi - row_lo) < 1024u ? (unsigned)(row_hi - row_lo) : 1024u;
-    FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_residual<S>, dim3(blocks), dim3(256), 0, s, (const S*)x, (const S*)x0, pitch,
-                                            n, row_lo, row_hi, alpha, beta, result));
+    FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_residual<S>, dim3(blocks, mb.count), dim3(256), 0, s, (const S*)x, (const S*)x0, pitch,
+                                            n, row_lo, row_hi, alpha, beta, result, mb.stride));
 }
 
 }  // namespace fluid

@@ -38,8 +38,14 @@ int fail(int code, const char* fmt, ...)
 int materialize_zero(fluid_ctx* c, int f)
 {
     if (!c->field[f].zero) return FLUID_OK;
-    HIP_TRY(hipMemsetAsync(c->ptr(f), 0, c->field_bytes, c->stream));
+    HIP_TRY(hipMemsetAsync(c->ptr(f), 0, c->all_bytes(), c->stream));     // every member: they lie back to back
     c->field[f].zero = false;
+    return FLUID_OK;
+}
+
+int refuse_ensemble(const fluid_ctx* c, const char* what)
+{
+    if (c && c->members > 1) return fail(FLUID_E_INVALID, "%s: not available on an ensemble (this context has %d members)", what, c->members);
     return FLUID_OK;
 }
 
@@ -52,6 +58,7 @@ using fluid_detail::g_err;
 using fluid_detail::materialize_zero;
 
 constexpr size_t kControlBytes = 256;   // tail of the arena: reduction scalar (+0), division-proof counter (+8)
+constexpr int kMaxMembers = 21845;   // 3 solves x members blocks in z of the fused Jacobi kernel (HIP: gridDim.z <= 65535)
 constexpr int kMaxN = 65533;     // one grid row per blockIdx.y in the pointwise kernels (HIP: gridDim.y <= 65535 = N + 2);
                                  // 65535^2 x 9 fields is 155 GB of the 288 GB, so nothing practical is cut off
 
@@ -365,7 +372,7 @@ int unscale(fluid_ctx* c, int f)
     const float inv = 1.0f / c->field[f].fscale;
     c->field[f].fscale = 1.0f;
     if (c->field[f].zero) return FLUID_OK;
-    fluid::launch_scale(c->stream, c->st, c->ptr(f), c->pitch, 0, c->n + 2, inv);
+    fluid::launch_scale(c->stream, c->st, c->ptr(f), c->pitch, 0, c->n + 2, inv, c->mb());
     return FLUID_OK;
 }
 
@@ -379,7 +386,7 @@ int settle(fluid_ctx* c, int f, bool keep_scale = false)
     rows_with_walls(c, reach, &lo, &hi);
     const float inc = c->field[f].pend_inc;
     c->field[f].pend = false;
-    TIMED(c, FLUID_TIME_SOURCE, fluid::launch_add_source(c->stream, c->st, c->ptr(f), nullptr, c->pitch, lo, hi, inc));
+    TIMED(c, FLUID_TIME_SOURCE, fluid::launch_add_source(c->stream, c->st, c->ptr(f), nullptr, c->pitch, lo, hi, inc, c->mb()));
     return FLUID_OK;
 }
 
@@ -394,7 +401,7 @@ int settle_source(fluid_ctx* c, int f)
     int lo, hi;
     rows_with_walls(c, reach, &lo, &hi);
     c->field[f].src_of = 0;
-    TIMED(c, FLUID_TIME_SOURCE, fluid::launch_add_source(c->stream, c->st, c->ptr(f), c->ptr(s), c->pitch, lo, hi, c->field[f].src_dt));
+    TIMED(c, FLUID_TIME_SOURCE, fluid::launch_add_source(c->stream, c->st, c->ptr(f), c->ptr(s), c->pitch, lo, hi, c->field[f].src_dt, c->mb()));
     wrote(c, f, reach);
     return FLUID_OK;
 }
@@ -433,7 +440,7 @@ int op_add_source(fluid_ctx* c, int x, int s, float dt, bool defer = false)
             c->field[x].pend_inc = inc;
             return FLUID_OK;               // x's reach unchanged: nothing was written
         }
-        TIMED(c, FLUID_TIME_SOURCE, fluid::launch_add_source(c->stream, c->st, c->ptr(x), nullptr, c->pitch, lo, hi, inc));
+        TIMED(c, FLUID_TIME_SOURCE, fluid::launch_add_source(c->stream, c->st, c->ptr(x), nullptr, c->pitch, lo, hi, inc, c->mb()));
     } else {
         TRY(settle(c, s));                 // (a source that is itself owed something: never inside a step)
         if (defer && c->fuse_add_source && c->variant == fluid::JACOBI_TB && fluid::jacobi_tb_exists(-1, -1, c->tb_nv, fluid::TB_ADDSRC)) {
@@ -441,7 +448,7 @@ int op_add_source(fluid_ctx* c, int x, int s, float dt, bool defer = false)
             c->field[x].src_dt = dt;
             return FLUID_OK;               // x's reach unchanged: nothing was written
         }
-        TIMED(c, FLUID_TIME_SOURCE, fluid::launch_add_source(c->stream, c->st, c->ptr(x), c->ptr(s), c->pitch, lo, hi, dt));
+        TIMED(c, FLUID_TIME_SOURCE, fluid::launch_add_source(c->stream, c->st, c->ptr(x), c->ptr(s), c->pitch, lo, hi, dt, c->mb()));
     }
     wrote(c, x, reach);
     return FLUID_OK;
@@ -461,6 +468,7 @@ struct RbTuner {
         std::vector<float> best_ms;
         std::vector<int> samples, issued;
         int fixed = 0;
+        std::string what;             // the launch shape in words (FLUID_TUNE_LOG)
     };
     std::mutex mu;
     std::unordered_map<unsigned long long, Entry> table;
@@ -479,7 +487,8 @@ unsigned long long tune_key(const fluid_ctx* c, int T, int m, int divmode, long 
     unsigned long long h = 1469598103934665603ull;
     for (unsigned long long v : {(unsigned long long)dev, (unsigned long long)c->n, (unsigned long long)rows_n, (unsigned long long)T,
                                  (unsigned long long)m, (unsigned long long)divmode, (unsigned long long)c->tb_nv, (unsigned long long)c->st,
-                                 (unsigned long long)c->tb_edge_pct, (unsigned long long)c->tb_fill}) {
+                                 (unsigned long long)c->tb_edge_pct, (unsigned long long)c->tb_fill,
+                                 (unsigned long long)c->members}) {      // an ensemble fills the chip: not the heights of one small grid
         h ^= v;
         h *= 1099511628211ull;
     }
@@ -512,7 +521,7 @@ void tune_harvest(fluid_ctx* c)
                 if (std::getenv("FLUID_TUNE_LOG")) {
                     std::string msg;
                     for (size_t q = 0; q < e.cand.size(); ++q) msg += " " + std::to_string(e.cand[q]) + ":" + std::to_string((int)(e.best_ms[q] * 1e3f));
-                    fprintf(stderr, "[fluid tune] key %016llx -> %d rows  (height:us%s)\n", tr.key, e.fixed, msg.c_str());
+                    fprintf(stderr, "[fluid tune] key %016llx [%s] -> %d rows  (height:us%s)\n", tr.key, e.what.c_str(), e.fixed, msg.c_str());
                 }
             }
         }
@@ -523,7 +532,8 @@ void tune_harvest(fluid_ctx* c)
 }
 
 // the height to use for this launch; *trial >= 0: it is a measurement of candidate *trial (tune_begin / tune_end bracket the launch)
-int tune_pick(fluid_ctx* c, unsigned long long key, int heuristic, int T, long long rows_n, int* trial)
+// (solves, form, divmode: for the shape's name in the log only)
+int tune_pick(fluid_ctx* c, unsigned long long key, int heuristic, int T, long long rows_n, int* trial, int solves = 0, int form = 0, int divmode = 0)
 {
     *trial = -1;
     tune_harvest(c);
@@ -532,6 +542,9 @@ int tune_pick(fluid_ctx* c, unsigned long long key, int heuristic, int T, long l
     RbTuner::Entry& e = t.table[key];
     if (e.fixed) return e.fixed;
     if (e.cand.empty()) {
+        char what[96];
+        snprintf(what, sizeof what, "N=%d T=%d solves=%d members=%d form=%d divmode=%d rows=%lld", c->n, T, solves, c->members, form, divmode, rows_n);
+        e.what = what;
         e.cand.push_back(heuristic);
         for (int r : {48, 56, 64, 80, 96, 112, 128, 160, 192}) {
             if (r < T || r >= rows_n + 2 * T) continue;         // (a height past the rows is one strip: the tallest candidate covers it)
@@ -598,6 +611,10 @@ struct SweepShape {
 };
 
 // for `count` solves per launch: fp32 weighs a batch's cells against TB_MIN_CELLS (plans made ahead of a batch pass 1)
+// Ensembles: every size here is ONE member's.  fp16 storage must (the schedule is part of the result, and member m has to
+// equal a one-member context); for fp32 it is a choice, speed only: the depth rules ("12 and 16 pay from 8 M cells") were
+// measured on single grids, where they mark the point at which a field's rows fall out of cache between a strip's stages --
+// a property of one member's rows, not of how many members share the launch.  No ensemble measurement backs either choice.
 SweepShape sweep_shape(const fluid_ctx* c, int count)
 {
     const bool canonical = c->st == fluid::STORAGE_F16;
@@ -704,7 +721,9 @@ struct Batch {
 };
 
 // a solve's |x0| minima per tile (division mode 3) go with its scratch field: a batch on the second stream has slots of its own
-unsigned* solve_tiles(const fluid_ctx* c, int slot) { return c->tiles + (size_t)slot * fluid::tile_rows(c->n) * fluid::tile_pitch(c->n); }
+// (per solve AND member: slot s holds `members` tables back to back)
+size_t tile_words(const fluid_ctx* c) { return (size_t)fluid::tile_rows(c->n) * fluid::tile_pitch(c->n); }
+unsigned* solve_tiles(const fluid_ctx* c, int slot) { return c->tiles + (size_t)slot * c->members * tile_words(c); }
 
 // argument checks, the scales of the solves reconciled, right-hand sides that are zero by definition materialised
 int batch_prepare(fluid_ctx* c, Batch& B)
@@ -795,11 +814,10 @@ int batch_plan(fluid_ctx* c, Batch& B)
     if (m == 0) return FLUID_OK;
     TRY(xchg_join(c));
     if (c->nranks > 1)
-        HIP_TRY(hipMemsetAsync(solve_tiles(c, B.scratch_base), 0,
-                               (size_t)B.count * fluid::tile_rows(c->n) * fluid::tile_pitch(c->n) * sizeof(unsigned), c->stream));
+        HIP_TRY(hipMemsetAsync(solve_tiles(c, B.scratch_base), 0, (size_t)B.count * c->members * tile_words(c) * sizeof(unsigned), c->stream));
     int lo, hi;
     rows(c, std::min(valid, c->n), &lo, &hi);
-    fluid::launch_tile_min_abs(c->stream, c->st, tb, m, c->pitch, c->n, lo, hi, fluid::tile_pitch(c->n));
+    fluid::launch_tile_min_abs(c->stream, c->st, tb, m, c->pitch, c->n, lo, hi, fluid::tile_pitch(c->n), c->mb(), tile_words(c));
     return FLUID_OK;
 }
 
@@ -835,6 +853,9 @@ fluid::TbBatch fill_batch(const fluid_ctx* c, const Batch& B, int first, int las
         if (addsrc) bt.div[q] = c->ptr(B.sum[j]);
     }
     bt.count = last - first;
+    bt.members = c->members;
+    bt.mstride = c->field_floats;
+    bt.tile_mstride = tile_words(c);
     bt.tile_pitch = fluid::tile_pitch(c->n);
     if (addsrc) bt.div_scale = c->field[B.sv[first].x0].src_dt;
     if (divsrc) {
@@ -864,13 +885,22 @@ int strip_rows(const fluid_ctx* c, int T, int m, long long rows_n)
     const long long room = (long long)c->num_cu * resident * 92 / 100;
     const int cap = T >= 16 ? 192 : (T >= 8 ? 80 : 96) * (m > 1 ? 2 : 1);
     int rb = c->tb_fill ? T : 2 * T;
-    for (; rb < cap; rb += 2) {
-        const long long si = (rows_n + rb - 1) / rb, se = (rows_n + edge_rows(c, T, rb) - 1) / edge_rows(c, T, rb);
-        if ((inner * ((si + 3) / 4) + outer * ((se + 3) / 4)) * m <= room) break;
-    }
+    auto fits = [&](int r) {
+        const long long si = (rows_n + r - 1) / r, se = (rows_n + edge_rows(c, T, r) - 1) / edge_rows(c, T, r);
+        return (inner * ((si + 3) / 4) + outer * ((se + 3) / 4)) * m <= room;
+    };
+    for (; rb < cap; rb += 2)
+        if (fits(rb)) break;
     // small grids: a launch lasts as long as one wave's march of rb + T - 1 rows (rb + 2T), and the best height
-    // measured is about rows / 64 (2 at 128^2, 4 at 256^2, 8 at 512^2, 16 and more from 1024^2)
-    if (rows_n <= 1100) rb = std::max(2, std::min(rb, (int)(rows_n / 64) & ~1));
+    // measured is about rows / 64 (2 at 128^2, 4 at 256^2, 8 at 512^2, 16 and more from 1024^2).
+    // An ensemble (m = solves x members) whose blocks no longer fit one round at that height is not waiting for one wave's
+    // march any more: it keeps the tall strips of the loop above, which repeat less pipeline fill.  (Closed form only: the
+    // tuner measures short and tall candidates alike)
+    if (rows_n <= 1100) {
+        const int low = std::max(2, std::min(rb, (int)(rows_n / 64) & ~1));
+        if (c->members == 1 || fits(low)) rb = low;
+        else rb = (int)std::min<long long>(rb, std::max<long long>(low, (rows_n + 1) & ~1ll));      // (no taller than the rows there are)
+    }
     return rb;
 }
 
@@ -890,13 +920,13 @@ int launch_fused(fluid_ctx* c, const fluid::TbBatch& bt, int T, int divmode, boo
         const int hole_lo = part && split ? in_lo : 0, hole_hi = part && split ? in_hi : 0;
         if (part) TRY(xchg_join(c));
         const long long rows_n = (phi - plo) - std::max(0, hole_hi - hole_lo);
-        int rb = c->tb_rows > 0 ? c->tb_rows : strip_rows(c, T, bt.count, rows_n);
+        int rb = c->tb_rows > 0 ? c->tb_rows : strip_rows(c, T, bt.count * c->members, rows_n);   // solves per launch: every member's
         int trial = -1;
         unsigned long long key = 0;
         if (c->tb_rows <= 0 && c->autotune) {
             // (the two edge parts of a split launch: keyed by their rows, and as a shape of their own)
             key = tune_key(c, T, bt.count + (divsrc ? 8 : 0) + (addsrc ? 16 : 0) + (hole_hi > hole_lo ? 32 : 0), divmode, rows_n);
-            rb = tune_pick(c, key, rb, T, rows_n, &trial);
+            rb = tune_pick(c, key, rb, T, rows_n, &trial, bt.count, form, divmode);
         }
         if (trial >= 0) TRY(tune_begin(c, key, trial));
         if (!fluid::launch_jacobi_tb(c->stream, c->st, T, divmode, c->tb_nv, form, bt, c->pitch, c->n, plo, phi, rb,
@@ -966,10 +996,10 @@ int batch_sweep(fluid_ctx* c, Batch& B)
             for (int j = 0; j < B.count; ++j) TRY(settle(c, sv[j].x0, /*keep_scale=*/true));
             for (int j = 0; j < B.count; ++j)
                 fluid::launch_jacobi(c->stream, c->st, v, c->ptr(B.cur[j]), c->ptr(sv[j].x0), c->ptr(B.nxt[j]), c->pitch, c->n, lo, hi,
-                                     sv[j].alpha, sv[j].beta, sv[j].b);
+                                     sv[j].alpha, sv[j].beta, sv[j].b, c->mb());
             if (c->timing) {
                 c->launches += B.count;
-                c->field_launches += B.count;
+                c->field_launches += (long long)B.count * c->members;
             }
         } else {
             // one launch per group of solves that share a division mode (normally: all of them)
@@ -979,7 +1009,7 @@ int batch_sweep(fluid_ctx* c, Batch& B)
                 TRY(launch_fused(c, fill_batch(c, B, first, last, divsrc, addsrc), T, B.plan[first].mode, divsrc, addsrc, lo, hi));
                 if (c->timing) {
                     c->launches += 1;
-                    c->field_launches += last - first;
+                    c->field_launches += (long long)(last - first) * c->members;
                 }
             }
         }
@@ -1007,7 +1037,7 @@ int op_diffuse_batch(fluid_ctx* c, const Solve* sv, int count, int iters, int fi
         wrote(c, B.scratch[j], 0);
         c->field[sv[j].x].fscale = B.out_scale[j];
     }
-    return timing_end(c, stop, iters * count);
+    return timing_end(c, stop, iters * count * c->members);
 }
 
 int op_diffuse(fluid_ctx* c, int b, int x, int x0, float alpha, float beta, int iters, int final_reach = 0, const DivSource* ds = nullptr)
@@ -1031,7 +1061,7 @@ int vmax_begin(fluid_ctx* c, int u, int v, bool have_max = false)
     if (!have_max) {
         TRY(materialize(c, {u, v}));
         HIP_TRY(hipMemsetAsync(c->d_scalar, 0, sizeof(unsigned), c->stream));
-        fluid::launch_absmax2(c->stream, c->st, c->ptr(u), c->ptr(v), c->pitch, c->n, c->own0, c->own1, c->d_scalar);
+        fluid::launch_absmax2(c->stream, c->st, c->ptr(u), c->ptr(v), c->pitch, c->n, c->own0, c->own1, c->d_scalar, c->mb());
     }
     TRY(exchange(c, FLUID_XCHG_MAX_BEGIN, {}, 0));       // in-place MAX over ranks on the device scalar
     HIP_TRY(hipMemcpyAsync(c->h_scalar, c->d_scalar, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
@@ -1088,7 +1118,7 @@ int op_advect(fluid_ctx* c, int b, int d, int d0, int u, int v, float dt)
     const float dt0 = dt * (float)c->n;
     TRY(materialize(c, {d0, u, v}));
     TIMED(c, FLUID_TIME_ADVECTION,
-          fluid::launch_advect(c->stream, c->st, c->ptr(d), c->ptr(d0), c->ptr(u), c->ptr(v), c->pitch, c->n, c->own0, c->own1, dt0, b));
+          fluid::launch_advect(c->stream, c->st, c->ptr(d), c->ptr(d0), c->ptr(u), c->ptr(v), c->pitch, c->n, c->own0, c->own1, dt0, b, c->mb()));
     wrote(c, d, 0);
     return FLUID_OK;
 }
@@ -1103,7 +1133,7 @@ int op_advect2(fluid_ctx* c, int ba, int da, int d0a, int bb, int db, int d0b, i
     TRY(materialize(c, {d0a, d0b, u, v}));
     TIMED(c, FLUID_TIME_ADVECTION,
           fluid::launch_advect2(c->stream, c->st, c->ptr(da), c->ptr(d0a), ba, c->ptr(db), c->ptr(d0b), bb, c->ptr(u), c->ptr(v), c->pitch,
-                                c->n, c->own0, c->own1, dt0));
+                                c->n, c->own0, c->own1, dt0, c->mb()));
     wrote(c, da, 0);
     wrote(c, db, 0);
     return FLUID_OK;
@@ -1129,7 +1159,7 @@ int op_divergence(fluid_ctx* c, int u, int v, int p, int div, int want = 0, floa
     // p = 0 everywhere (FluidSequential.c:153 + set_bnd(0,p)): marked, not written
     TIMED(c, FLUID_TIME_DIVERGENCE,
           fluid::launch_divergence(c->stream, c->st, c->ptr(u), c->ptr(v), c->ptr(p), c->ptr(div), c->pitch, c->n, lo, hi, h,
-                                   /*write_p=*/0, pscale));
+                                   /*write_p=*/0, pscale, c->mb()));
     wrote(c, div, reach);
     c->field[div].fscale = pscale;
     mark_zero(c, p);
@@ -1148,7 +1178,7 @@ int op_subtract_gradient(fluid_ctx* c, int u, int v, int p, bool with_max = fals
     with_max = with_max && c->nranks > 1 && c->d_partials;
     TIMED(c, FLUID_TIME_PROJECTION,
           fluid::launch_subtract_gradient(c->stream, c->st, c->ptr(u), c->ptr(v), c->ptr(p), c->pitch, c->n, c->own0, c->own1, h,
-                                          c->d_partials, with_max ? c->d_scalar : nullptr, 1.0f / c->field[p].fscale));
+                                          c->d_partials, with_max ? c->d_scalar : nullptr, 1.0f / c->field[p].fscale, c->mb()));
     wrote(c, u, 0);
     wrote(c, v, 0);
     return FLUID_OK;
@@ -1168,7 +1198,7 @@ int op_gradient_advect(fluid_ctx* c, int u, int v, int p, int b, int d, int d0, 
     TRY(materialize(c, p, /*keep_scale=*/true));
     TIMED(c, FLUID_TIME_PROJECTION,
           fluid::launch_gradient_advect(c->stream, c->st, c->ptr(u), c->ptr(v), c->ptr(p), c->ptr(d), c->ptr(d0), c->pitch, c->n, c->own0,
-                                        c->own1, h, dt * (float)c->n, b, 1.0f / c->field[p].fscale));
+                                        c->own1, h, dt * (float)c->n, b, 1.0f / c->field[p].fscale, c->mb()));
     wrote(c, u, 0);
     wrote(c, v, 0);
     wrote(c, d, 0);
@@ -1372,7 +1402,10 @@ int zero_sources(fluid_ctx* c)
 }
 
 // `wait` = false only enqueues (fp32 storage): step() / step_src() queue all their fields and wait once
-int copy_rows(fluid_ctx* c, int field, float* host, const float* chost, int row_lo, int row_hi, bool to_device, bool wait = true)
+// `member`: whose copy of the field.  An upload settles the field for ALL members first (materialize: the marks are shared,
+// and the members that are not uploaded must end up holding what the marks stood for), then overwrites that member's rows.
+int copy_rows(fluid_ctx* c, int field, float* host, const float* chost, int row_lo, int row_hi, bool to_device, bool wait = true,
+              int member = 0)
 {
     if (row_lo < 0 || row_hi > c->w || row_lo > row_hi) return fail(FLUID_E_INVALID, "bad row range");
     if (row_lo == row_hi) return FLUID_OK;
@@ -1380,7 +1413,7 @@ int copy_rows(fluid_ctx* c, int field, float* host, const float* chost, int row_
     // pass over the fp16 field would round the plain values into fp16's subnormals again
     const float host_scale = (!to_device && c->st != fluid::STORAGE_F32) ? 1.0f / c->field[field].fscale : 1.0f;
     TRY(materialize(c, field, /*keep_scale=*/host_scale != 1.0f));
-    char* dev = static_cast<char*>(c->row(field, row_lo)) + (size_t)XOFF * c->esz;
+    char* dev = static_cast<char*>(c->row(field, row_lo)) + (size_t)member * c->field_bytes + (size_t)XOFF * c->esz;
     const size_t rows = (size_t)(row_hi - row_lo), w = (size_t)c->w;
     const size_t dp = (size_t)c->pitch * c->esz;
     if (to_device) c->field[field].reach = 0;     // the caller vouches only for its own rows
@@ -1446,20 +1479,29 @@ int fluid_layout(int N, int* pitch, int* xoff, size_t* field_floats)
     return FLUID_OK;
 }
 
-size_t fluid_arena_bytes_ex(int N, int storage)
+size_t fluid_arena_bytes_ensemble(int N, int storage, int members)
 {
     size_t ff = 0;
     if (fluid_layout(N, nullptr, nullptr, &ff) != FLUID_OK) return 0;
     if (storage != FLUID_STORAGE_F32 && storage != FLUID_STORAGE_F16) return 0;
-    return ff * FLUID_NFIELDS * fluid::storage_bytes(storage) + kControlBytes;
+    if (members < 1 || members > kMaxMembers) return 0;
+    return ff * FLUID_NFIELDS * fluid::storage_bytes(storage) * (size_t)members + kControlBytes;
 }
+
+size_t fluid_arena_bytes_ex(int N, int storage) { return fluid_arena_bytes_ensemble(N, storage, 1); }
 
 size_t fluid_arena_bytes(int N) { return fluid_arena_bytes_ex(N, FLUID_STORAGE_F32); }
 
-int fluid_create_ex(const fluid_config* cfg, fluid_ctx** out)
+int fluid_create_ex(const fluid_config* cfg, fluid_ctx** out) { return fluid_create_ensemble(cfg, 1, out); }
+
+// Every argument is checked before the device is touched.  Fields are laid out [field][member]: member m of field f starts
+// (f * members + m) * field_bytes into the arena, the control block behind the last one.
+int fluid_create_ensemble(const fluid_config* cfg, int members, fluid_ctx** out)
 {
-    if (!cfg || !out) return fail(FLUID_E_INVALID, "fluid_create_ex: null argument");
+    if (!cfg || !out) return fail(FLUID_E_INVALID, "fluid_create_ex / fluid_create_ensemble: null argument");
     *out = nullptr;
+    if (members < 1 || members > kMaxMembers) return fail(FLUID_E_INVALID, "members must be in [1, %d] (got %d)", kMaxMembers, members);
+    if (members > 1 && cfg->nranks > 1) return fail(FLUID_E_INVALID, "an ensemble runs on one GPU: nranks must be 1 (got %d)", cfg->nranks);
     const int n = cfg->n;
     if (n < 1 || n > kMaxN) return fail(FLUID_E_INVALID, "N must be in [1, %d] (got %d)", kMaxN, n);
     const int P = cfg->nranks < 1 ? 1 : cfg->nranks;
@@ -1475,6 +1517,7 @@ int fluid_create_ex(const fluid_config* cfg, fluid_ctx** out)
     c->w = n + 2;
     c->pitch = fluid::pitch_for(n);
     c->field_floats = (size_t)c->w * c->pitch;
+    c->members = members;
     c->st = cfg->storage;
     c->esz = fluid::storage_bytes(c->st);
     c->field_bytes = c->field_floats * c->esz;
@@ -1508,7 +1551,7 @@ int fluid_create_ex(const fluid_config* cfg, fluid_ctx** out)
         }
         c->halo = std::max(c->halo, 8);
     }
-    const size_t bytes = c->field_bytes * FLUID_NFIELDS + kControlBytes;
+    const size_t bytes = c->all_bytes() * FLUID_NFIELDS + kControlBytes;
     int rc = FLUID_OK;
     auto bail = [&](int code) { fluid_destroy(c); return code; };
     if (cfg->arena) {
@@ -1527,7 +1570,7 @@ int fluid_create_ex(const fluid_config* cfg, fluid_ctx** out)
         if (e != hipSuccess) return bail(fail(FLUID_E_HIP, "hipStreamCreate: %s", hipGetErrorString(e)));
         c->own_stream = true;
     }
-    for (int k = 0; k < FLUID_NFIELDS; ++k) c->field[k].ptr = c->arena + (size_t)k * c->field_bytes;
+    for (int k = 0; k < FLUID_NFIELDS; ++k) c->field[k].ptr = c->arena + (size_t)k * c->all_bytes();
     auto hip_ok = [&](hipError_t e, const char* what) {
         if (e == hipSuccess) return true;
         rc = fail(e == hipErrorOutOfMemory ? FLUID_E_NOMEM : FLUID_E_HIP, "%s: %s", what, hipGetErrorString(e));
@@ -1548,9 +1591,9 @@ int fluid_create_ex(const fluid_config* cfg, fluid_ctx** out)
         if (!hip_ok(hipEventCreateWithFlags(&c->ev_xdone, hipEventDisableTiming), "hipEventCreate")) return bail(rc);
     }
     if (!hip_ok(hipMemsetAsync(c->arena, 0, bytes, c->stream), "hipMemsetAsync(arena)")) return bail(rc);
-    c->d_scalar = reinterpret_cast<unsigned int*>(c->arena + c->field_bytes * FLUID_NFIELDS);   // RCCL-addressable
+    c->d_scalar = reinterpret_cast<unsigned int*>(c->arena + c->all_bytes() * FLUID_NFIELDS);   // RCCL-addressable
     {
-        const size_t words = 3 * (size_t)fluid::tile_rows(n) * fluid::tile_pitch(n);
+        const size_t words = 3 * (size_t)members * tile_words(c);
         if (!hip_ok(hipMalloc((void**)&c->tiles, words * sizeof(unsigned)), "hipMalloc(tiles)")) return bail(rc);
         if (!hip_ok(hipMemsetAsync(c->tiles, 0, words * sizeof(unsigned), c->stream), "hipMemsetAsync(tiles)")) return bail(rc);
     }
@@ -1662,9 +1705,50 @@ int fluid_scalar_ptr(fluid_ctx* c, void** dev_ptr)
     return FLUID_OK;
 }
 
+int fluid_members(fluid_ctx* c, int* members)
+{
+    TRY(check_ctx(c));
+    if (!members) return fail(FLUID_E_INVALID, "null pointer");
+    *members = c->members;
+    return FLUID_OK;
+}
+
+// the whole-field copies of a one-member context would have to pick a member or broadcast: either would be a trap
+static int refuse_plain_copy(const fluid_ctx* c, const char* what)
+{
+    if (c->members > 1)
+        return fail(FLUID_E_INVALID, "%s: this context has %d members -- use fluid_upload_member / fluid_download_member", what, c->members);
+    return FLUID_OK;
+}
+
+static int check_member(const fluid_ctx* c, int member)
+{
+    if (member < 0 || member >= c->members) return fail(FLUID_E_INVALID, "member %d outside [0, %d)", member, c->members);
+    return FLUID_OK;
+}
+
+int fluid_upload_member(fluid_ctx* c, int member, int field, const float* host)
+{
+    TRY(check_ctx(c));
+    TRY(check_fields(c, {field}));
+    TRY(check_member(c, member));
+    if (!host) return fail(FLUID_E_INVALID, "null host pointer");
+    return copy_rows(c, field, nullptr, host, 0, c->w, true, true, member);
+}
+
+int fluid_download_member(fluid_ctx* c, int member, int field, float* host)
+{
+    TRY(check_ctx(c));
+    TRY(check_fields(c, {field}));
+    TRY(check_member(c, member));
+    if (!host) return fail(FLUID_E_INVALID, "null host pointer");
+    return copy_rows(c, field, host, nullptr, 0, c->w, false, true, member);
+}
+
 int fluid_upload_rows(fluid_ctx* c, int field, const float* host, int row_lo, int row_hi)
 {
     TRY(check_ctx(c));
+    TRY(refuse_plain_copy(c, "fluid_upload_rows"));
     TRY(check_fields(c, {field}));
     if (!host) return fail(FLUID_E_INVALID, "null host pointer");
     return copy_rows(c, field, nullptr, host, row_lo, row_hi, true);
@@ -1673,6 +1757,7 @@ int fluid_upload_rows(fluid_ctx* c, int field, const float* host, int row_lo, in
 int fluid_download_rows(fluid_ctx* c, int field, float* host, int row_lo, int row_hi)
 {
     TRY(check_ctx(c));
+    TRY(refuse_plain_copy(c, "fluid_download_rows"));
     TRY(check_fields(c, {field}));
     if (!host) return fail(FLUID_E_INVALID, "null host pointer");
     return copy_rows(c, field, host, nullptr, row_lo, row_hi, false);
@@ -1681,12 +1766,14 @@ int fluid_download_rows(fluid_ctx* c, int field, float* host, int row_lo, int ro
 int fluid_upload(fluid_ctx* c, int field, const float* host)
 {
     TRY(check_ctx(c));
+    TRY(refuse_plain_copy(c, "fluid_upload"));
     return fluid_upload_rows(c, field, host, 0, c->w);
 }
 
 int fluid_download(fluid_ctx* c, int field, float* host)
 {
     TRY(check_ctx(c));
+    TRY(refuse_plain_copy(c, "fluid_download"));
     return fluid_download_rows(c, field, host, 0, c->w);
 }
 
@@ -1695,12 +1782,12 @@ int fluid_fill(fluid_ctx* c, int field, float value)
     TRY(check_ctx(c));
     TRY(check_fields(c, {field}));
     if (value == 0.0f && !std::signbit(value)) {
-        HIP_TRY(hipMemsetAsync(c->ptr(field), 0, c->field_bytes, c->stream));
+        HIP_TRY(hipMemsetAsync(c->ptr(field), 0, c->all_bytes(), c->stream));
         wrote(c, field, kEverywhere);
         return FLUID_OK;
     }
     std::vector<float> row((size_t)c->w * c->w, value);
-    TRY(fluid_upload(c, field, row.data()));
+    for (int m = 0; m < c->members; ++m) TRY(fluid_upload_member(c, m, field, row.data()));     // every member
     wrote(c, field, kEverywhere);
     return FLUID_OK;
 }
@@ -1833,6 +1920,7 @@ int fluid_division_mode(fluid_ctx* c, float alpha, float beta, int* mode)
 int fluid_set_exchange(fluid_ctx* c, fluid_exchange_fn fn, void* user)
 {
     TRY(check_ctx(c));
+    TRY(fluid_detail::refuse_ensemble(c, "fluid_set_exchange"));
     c->xchg = fn;
     c->xchg_user = user;
     return FLUID_OK;
@@ -1841,6 +1929,7 @@ int fluid_set_exchange(fluid_ctx* c, fluid_exchange_fn fn, void* user)
 int fluid_exchange_now(fluid_ctx* c, int kind, const int* fields, int nfields, int depth)
 {
     TRY(check_ctx(c));
+    TRY(fluid_detail::refuse_ensemble(c, "fluid_exchange_now"));
     if (!c->xchg) return fail(FLUID_E_COMM, "no exchange installed");
     if (kind != FLUID_XCHG_HALO && kind != FLUID_XCHG_GATHER) return fail(FLUID_E_INVALID, "fluid_exchange_now moves rows: HALO or GATHER");
     if (nfields < 0 || (nfields > 0 && !fields)) return fail(FLUID_E_INVALID, "bad field list");
@@ -1901,7 +1990,7 @@ int fluid_op_set_bnd(fluid_ctx* c, int b, int x)
     if (b < 0 || b > 2) return fail(FLUID_E_INVALID, "b must be 0, 1 or 2");
     if (c->nranks != 1) return fail(FLUID_E_INVALID, "fluid_op_set_bnd is a whole-grid operator (1 GPU)");
     TRY(materialize(c, x));
-    fluid::launch_set_bnd(c->stream, c->st, c->ptr(x), c->pitch, c->n, b);
+    fluid::launch_set_bnd(c->stream, c->st, c->ptr(x), c->pitch, c->n, b, c->mb());
     HIP_TRY(hipGetLastError());
     return FLUID_OK;
 }
@@ -1925,7 +2014,8 @@ int fluid_op_jacobi_sweep(fluid_ctx* c, int b, int x, int x0, int out, float alp
     TRY(materialize(c, {x, x0}));
     TRY(need(c, {x}, 1));
     const int v1 = c->variant == fluid::JACOBI_TB ? fluid::JACOBI_STREAM : c->variant;   // one sweep: nothing to block
-    fluid::launch_jacobi(c->stream, c->st, v1, c->ptr(x), c->ptr(x0), c->ptr(out), c->pitch, c->n, c->own0, c->own1, alpha, beta, b);
+    fluid::launch_jacobi(c->stream, c->st, v1, c->ptr(x), c->ptr(x0), c->ptr(out), c->pitch, c->n, c->own0, c->own1, alpha, beta, b,
+                         c->mb());
     wrote(c, out, 0);
     HIP_TRY(hipGetLastError());
     return FLUID_OK;
@@ -1983,7 +2073,8 @@ int fluid_residual(fluid_ctx* c, int x, int x0, float alpha, float beta, float* 
     TRY(materialize(c, {x, x0}));
     TRY(need(c, {x}, 1));
     HIP_TRY(hipMemsetAsync(c->d_scalar, 0, sizeof(unsigned), c->stream));
-    fluid::launch_residual(c->stream, c->st, c->ptr(x), c->ptr(x0), c->pitch, c->n, c->own0, c->own1, alpha, beta, c->d_scalar);
+    fluid::launch_residual(c->stream, c->st, c->ptr(x), c->ptr(x0), c->pitch, c->n, c->own0, c->own1, alpha, beta, c->d_scalar,
+                           c->mb());      // (an ensemble: the maximum over all members)
     TRY(reduce_to_host(c, out));
     return exchange(c, FLUID_XCHG_MAX, {}, 0, out);
 }
@@ -1995,7 +2086,7 @@ int fluid_absmax_velocity(fluid_ctx* c, int u, int v, float* out)
     if (!out) return fail(FLUID_E_INVALID, "null pointer");
     TRY(materialize(c, {u, v}));
     HIP_TRY(hipMemsetAsync(c->d_scalar, 0, sizeof(unsigned), c->stream));
-    fluid::launch_absmax2(c->stream, c->st, c->ptr(u), c->ptr(v), c->pitch, c->n, c->own0, c->own1, c->d_scalar);
+    fluid::launch_absmax2(c->stream, c->st, c->ptr(u), c->ptr(v), c->pitch, c->n, c->own0, c->own1, c->d_scalar, c->mb());
     TRY(reduce_to_host(c, out));
     return exchange(c, FLUID_XCHG_MAX, {}, 0, out);
 }
@@ -2045,6 +2136,8 @@ int fluid_op_diffuse_tol(fluid_ctx* c, int b, int x, int x0, float alpha, float 
                          int check_every, int* iters_done, float* residual)
 {
     TRY(check_ctx(c));
+    // (a residual-terminated solve would make every member's sweep count depend on the others)
+    TRY(fluid_detail::refuse_ensemble(c, "fluid_op_diffuse_tol"));
     TRY(check_fields(c, {x, x0}));
     if (b < 0 || b > 2) return fail(FLUID_E_INVALID, "b must be 0, 1 or 2");
     if (check_every < 2 || (check_every & 1) || max_iters < 0 || !(tol >= 0.f))

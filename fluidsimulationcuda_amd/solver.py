@@ -32,16 +32,24 @@ def _host(a, n):
 
 
 class FluidSolver:
-    """Six resident fields + scratch on one GPU (or one row slab of several)."""
+    """Six resident fields + scratch on one GPU (or one row slab of several).
+
+    `members=M` makes it an ensemble: M independent simulations of the same size that go through every call together, in
+    the same kernel launches.  Member m's fields are moved with upload(member=m, ...) / download(field, member=m), or all
+    at once as (M, N+2, N+2) arrays with upload_members / download_members."""
 
     def __init__(self, n, rank=0, nranks=1, halo=0, jacobi=capi.JACOBI_TB, stream=None,
-                 arena_ptr=None, arena_bytes=0, params=None, storage=capi.STORAGE_F32):
+                 arena_ptr=None, arena_bytes=0, params=None, storage=capi.STORAGE_F32, members=1):
         self._h = C.c_void_p()
         self.n = int(n)
+        self.members = int(members)
         self.storage = storage
         cfg = capi.Config(n=self.n, rank=rank, nranks=nranks, halo=halo, jacobi_variant=jacobi,
                           stream=stream, arena=arena_ptr, arena_bytes=arena_bytes, storage=storage)
-        capi.check(capi.lib().fluid_create_ex(C.byref(cfg), C.byref(self._h)))
+        if self.members == 1:
+            capi.check(capi.lib().fluid_create_ex(C.byref(cfg), C.byref(self._h)))
+        else:
+            capi.check(capi.lib().fluid_create_ensemble(C.byref(cfg), self.members, C.byref(self._h)))
         lo, hi = C.c_int(), C.c_int()
         capi.check(capi.lib().fluid_owned_rows(self._h, C.byref(lo), C.byref(hi)))
         self.owned_rows = (lo.value, hi.value)
@@ -69,17 +77,48 @@ class FluidSolver:
         self.close()
 
     # -- data movement
-    def upload(self, **fields):
+    def upload(self, member=None, **fields):
+        """upload(u=..., dens=...) on a single simulation; upload(member=m, u=...) into member m of an ensemble."""
         for name, arr in fields.items():
-            capi.check(capi.lib().fluid_upload(self._h, _fid(name), _host(arr, self.n)))
+            if member is None:
+                capi.check(capi.lib().fluid_upload(self._h, _fid(name), _host(arr, self.n)))
+            else:
+                capi.check(capi.lib().fluid_upload_member(self._h, int(member), _fid(name), _host(arr, self.n)))
+
+    def upload_members(self, **fields):
+        """Every member of each named field at once: arrays of shape (members, N+2, N+2)."""
+        for name, arr in fields.items():
+            arr = np.ascontiguousarray(arr, dtype=np.float32)
+            if arr.shape != (self.members, self.n + 2, self.n + 2):
+                raise ValueError("field must have shape (%d, %d, %d), got %s" % (self.members, self.n + 2, self.n + 2, arr.shape))
+            for m in range(self.members):
+                capi.check(capi.lib().fluid_upload_member(self._h, m, _fid(name), arr[m]))
+
+    def download_members(self, field, out=None):
+        """All members of a field as one (members, N+2, N+2) array."""
+        if out is None:
+            out = np.empty((self.members, self.n + 2, self.n + 2), dtype=np.float32)
+        if out.dtype != np.float32 or not out.flags.c_contiguous or out.shape != (self.members, self.n + 2, self.n + 2):
+            raise ValueError("out must be C-contiguous float32 of shape (%d, %d, %d)" % (self.members, self.n + 2, self.n + 2))
+        for m in range(self.members):
+            capi.check(capi.lib().fluid_download_member(self._h, m, _fid(field), out[m]))
+        return out
+
+    def member_count(self):
+        m = C.c_int()
+        capi.check(capi.lib().fluid_members(self._h, C.byref(m)))
+        return m.value
 
     def upload_rows(self, field, arr, row_lo, row_hi):
         capi.check(capi.lib().fluid_upload_rows(self._h, _fid(field), _host(arr, self.n), row_lo, row_hi))
 
-    def download(self, field, out=None):
+    def download(self, field, out=None, member=None):
         if out is None:
             out = np.empty((self.n + 2, self.n + 2), dtype=np.float32)
-        capi.check(capi.lib().fluid_download(self._h, _fid(field), _host(out, self.n)))
+        if member is None:
+            capi.check(capi.lib().fluid_download(self._h, _fid(field), _host(out, self.n)))
+        else:
+            capi.check(capi.lib().fluid_download_member(self._h, int(member), _fid(field), _host(out, self.n)))
         return out
 
     def download_rows(self, field, out, row_lo, row_hi):

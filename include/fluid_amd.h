@@ -161,13 +161,39 @@ enum { FLUID_STORAGE_F32 = 0, FLUID_STORAGE_F16 = 1 };
 size_t fluid_arena_bytes(int N);                       /* fp32 storage */
 size_t fluid_arena_bytes_ex(int N, int storage);
 /* Device layout of one field: W = N+2 rows of `pitch` elements, column c at
- * element index c + xoff; field f starts f*field_floats elements into the arena. */
+ * element index c + xoff; field f starts f*field_floats elements into the arena.
+ * In an ensemble of M members (fluid_create_ensemble) the fields are laid out [field][member]: field f starts
+ * f*M*field_floats elements into the arena and holds its M members back to back, member m field_floats*m elements
+ * behind the address fluid_field_ptr() returns (which is member 0's) -- one (M, N+2, pitch) array per field. */
 int fluid_layout(int N, int *pitch, int *xoff, size_t *field_floats);
 
 int fluid_create(int N, fluid_ctx **out);                      /* 1 GPU, defaults */
 int fluid_create_ex(const fluid_config *cfg, fluid_ctx **out);
 int fluid_destroy(fluid_ctx *ctx);
 int fluid_synchronize(fluid_ctx *ctx);
+
+/* ---- ensembles: M independent simulations of the same size in one context ---------------------------------
+ * Every member has its own twelve fields; all members share N, the storage type, every fluid_set_param knob and the
+ * scalar arguments of each call.  One call to fluid_step / fluid_vel_step / fluid_dens_step / fluid_op_* / fluid_fill
+ * does to every member what it does to a one-member context, in the SAME kernel launches (the member index rides in the
+ * launch grid), and member m ends up with exactly the bits a one-member context given m's arrays would hold.
+ * `members` in [1, 21845]; cfg->nranks must be 1 when members > 1; cfg->arena, if given, holds
+ * fluid_arena_bytes_ensemble() bytes: 12 x members fields plus the 256-byte control block.
+ * fluid_create_ensemble(cfg, 1, ..) is fluid_create_ex(cfg, ..).  Argument errors are reported before the device is touched.
+ * On a context with more than one member:
+ *   - fluid_upload / fluid_download / fluid_upload_rows / fluid_download_rows return FLUID_E_INVALID (they would have to
+ *     pick a member or broadcast silently): use the _member calls;
+ *   - fluid_residual and fluid_absmax_velocity return the maximum over all members;
+ *   - fluid_op_diffuse_tol (every member's sweep count would depend on the others), fluid_set_exchange,
+ *     fluid_exchange_now and the fluid_exchange_rccl_* calls return FLUID_E_INVALID;
+ *   - fluid_timing counts jacobi_field_launches, sweeps and pressure_sweeps once per member, jacobi_launches per launch. */
+int fluid_create_ensemble(const fluid_config *cfg, int members, fluid_ctx **out);
+size_t fluid_arena_bytes_ensemble(int N, int storage, int members);   /* host logic; 0 on bad arguments */
+int fluid_members(fluid_ctx *ctx, int *members);
+/* Whole-field copies of one member (host pointer: the (N+2)^2 array).  Synchronous.  An upload first settles whatever the
+ * library still owes the field (zeros by definition, a deferred add_source) in ALL members, then replaces this one. */
+int fluid_upload_member(fluid_ctx *ctx, int member, int field, const float *host);
+int fluid_download_member(fluid_ctx *ctx, int member, int field, float *host);
 
 /* Interior rows [*row_lo, *row_hi) owned by this context's slab (1..N+1 for one GPU). */
 int fluid_owned_rows(fluid_ctx *ctx, int *row_lo, int *row_hi);
@@ -243,7 +269,8 @@ typedef struct fluid_timing {
     long long category_calls[FLUID_TIMING_CATEGORIES];
     long long jacobi_launches;        /* Jacobi kernel launches in those solves                              */
     long long jacobi_field_launches;  /* the same, counting a launch once per field it sweeps (a batched launch
-                                         sweeps up to three): x12 B x cells = the launches' compulsory bytes */
+                                         sweeps up to three, in every member of an ensemble): x12 B x cells = the
+                                         launches' compulsory bytes */
     double pressure_ms;               /* the part of jacobi_ms spent in the pressure solves of fluid_step /
                                          fluid_vel_step (alpha 1, beta 4, b 0: FluidSequential.c:222,240)     */
     long long pressure_sweeps;
