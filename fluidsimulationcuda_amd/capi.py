@@ -60,6 +60,7 @@ EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_
 _HOSTF = np.ctypeslib.ndpointer(dtype=np.float32, flags="C_CONTIGUOUS")
 _ctx = C.c_void_p
 _i, _f = C.c_int, C.c_float
+_MF = C.POINTER(C.c_float)          # one float per ensemble member (the *_members calls); None passes as a null pointer
 
 # name -> argtypes; every listed function returns int status.  This table is
 # also what tests/test_abi.py checks against include/fluid_amd.h.
@@ -75,6 +76,13 @@ SIGNATURES = {
     "fluid_members": [_ctx, C.POINTER(_i)],
     "fluid_upload_member": [_ctx, _i, _i, _HOSTF],
     "fluid_download_member": [_ctx, _i, _i, _HOSTF],
+    "fluid_step_members": [_ctx, _MF, _MF, _MF, _i, _i, _i],
+    "fluid_vel_step_members": [_ctx, _MF, _MF, _i],
+    "fluid_dens_step_members": [_ctx, _MF, _MF, _i],
+    "fluid_op_add_source_members": [_ctx, _i, _i, _MF],
+    "fluid_op_jacobi_sweep_members": [_ctx, _i, _i, _i, _i, _MF, _MF],
+    "fluid_op_diffuse_members": [_ctx, _i, _i, _i, _MF, _MF, _i],
+    "fluid_op_advect_members": [_ctx, _i, _i, _i, _i, _i, _MF],
     "fluid_destroy": [_ctx],
     "fluid_synchronize": [_ctx],
     "fluid_owned_rows": [_ctx, C.POINTER(_i), C.POINTER(_i)],

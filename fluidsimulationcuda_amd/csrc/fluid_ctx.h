@@ -44,10 +44,28 @@ struct FieldState {
     // add_source of a real source, deferred into the next diffusion's first launch (fluid_solver.hip: op_add_source)
     int src_of = 0;           // 0: nothing owed; else 1 + the id of the source field s: owes itself + src_dt * s
     float src_dt = 0.0f;
+    // After a fluid_*_members call the two values above differ from member to member: one entry per member then (and the
+    // scalar holds member 0's); empty: the scalar holds for everybody.  Everything else in this record stays shared.
+    std::vector<float> pend_incv, src_dtv;
     // fp16 storage: a projection's pressure is of the order h * |velocity| -- 1e-5 at 16384^2, fp16 subnormals -- so in a
     // step the divergence and the pressure are kept multiplied by a power of two (fluid_solver.hip: project): fscale (1:
     // plain values), undone exactly when the field is downloaded and by a pass over it for any reader that does not know
     float fscale = 1.0f;
+};
+
+// Per-member constants (the fluid_*_members calls) reach the kernels through tables in device memory: a ring of device
+// memory with a pinned host twin, library-owned and outside the arena, allocated at the first such call.  A table is copied
+// host twin -> device on the context's stream, so it is in place before the launches that read it and is not overwritten
+// before the launches queued ahead of the next copy have run; the host twin's bytes are reused only after the event behind
+// their copy has completed.  A table whose bytes equal one still in the ring is not copied again (fluid_solver.hip:
+// member_consts): a stepping loop with the same arrays every call uploads nothing and waits for nothing.
+struct ConstRing {
+    char *dev = nullptr, *host = nullptr;
+    size_t bytes = 0, head = 0;
+    struct Blob { size_t off, len; unsigned long long hash; hipEvent_t copied; };
+    std::vector<Blob> live;                 // tables in the ring, oldest first
+    std::vector<hipEvent_t> free_events;
+    long long uploads = 0;
 };
 
 struct fluid_ctx {
@@ -80,6 +98,7 @@ struct fluid_ctx {
     size_t field_bytes = 0;
     unsigned int* d_scalar = nullptr;     // device word for the reductions
     float* d_partials = nullptr;          // slabs: per-block maxima of the gradient subtraction (launch_subtract_gradient)
+    ConstRing consts;                     // tables of per-member constants (fluid_*_members)
     unsigned int* tiles = nullptr;        // 3 x members x tile_rows x tile_pitch words: |x0| minima per tile for division mode 3
     unsigned int* h_scalar = nullptr;     // pinned host mirror
     hipEvent_t scalar_ready = nullptr;    // recorded behind the scalar's device-to-host copy

@@ -27,6 +27,16 @@ struct Members {
     size_t stride = 0;
 };
 
+// Per-member constants of one solve of a fused launch (the fluid_*_members calls): what TbBatch carries once per solve, here
+// once per (solve, member) in a table in device memory, record [solve * members + member].  Each wave reads its record in
+// the kernel's prologue with wave-uniform loads; the host writes the table (a copy), nothing on the device does.
+struct TbMemberK {
+    double yd;
+    float alpha, beta, hi, lo;   // as TbBatch's
+    float x0_inc, div_scale;     // div_scale: the source-adding launch's dt (other forms: the launch's own value)
+    unsigned tile_thr, pad;
+};
+
 // up to three independent solves of the same shape, blockIdx.z % count of the fused Jacobi kernel (blockIdx.z / count: the
 // ensemble member, whose fields lie member * mstride elements behind the addresses given here)
 struct TbBatch {
@@ -49,12 +59,16 @@ struct TbBatch {
     int members;                 // ensemble members per solve (>= 1): gridDim.z = count * members
     size_t mstride;              // elements between two members of a field
     size_t tile_mstride;         // words between two members' tile minima (division mode 3)
+    const TbMemberK* mk;         // nullptr: alpha .. x0_inc, tile_thr and div_scale above hold for every member; else this table does
 };
 
 void launch_set_bnd(hipStream_t s, int st, void* f, int pitch, int n, int b, Members mb = {});
-void launch_add_source(hipStream_t s, int st, void* x, const void* src, int pitch, int row_lo, int row_hi, float dt, Members mb = {});
+void launch_add_source(hipStream_t s, int st, void* x, const void* src, int pitch, int row_lo, int row_hi, float dt, Members mb = {},
+                       const float* mdt = nullptr);
+// mdt / mab / mdt0 (here and below): nullptr, or a device array with one value per member that replaces the scalar argument
+// (dt or the increment; float2 {alpha, beta}; dt0) -- read once per wave, indexed by the member's grid coordinate
 void launch_jacobi(hipStream_t s, int st, int variant, const void* x, const void* x0, void* out, int pitch, int n,
-                   int row_lo, int row_hi, float alpha, float beta, int b, Members mb = {});
+                   int row_lo, int row_hi, float alpha, float beta, int b, Members mb = {}, const float2* mab = nullptr);
 // Shapes of the fused Jacobi kernel (k_jacobi_tb): sweeps T, division mode, columns per lane, and the form -- plain, the
 // first launch of a pressure solve that forms the divergence as its right-hand side (DIVSRC), or the first launch of a
 // diffusion that adds a deferred source to it (ADDSRC).  This table is the set of kernels built per storage type and the
@@ -110,9 +124,9 @@ void launch_tile_min_abs(hipStream_t s, int st, const TileBatch& tb, int count, 
                          Members mb = {}, size_t tile_mstride = 0);
 void launch_validate_div(hipStream_t s, int divmode, float beta, float kbeta, double yd, float hi, float lo, unsigned long long* bad);
 void launch_advect(hipStream_t s, int st, void* d, const void* d0, const void* u, const void* v, int pitch, int n,
-                   int row_lo, int row_hi, float dt0, int b, Members mb = {});
+                   int row_lo, int row_hi, float dt0, int b, Members mb = {}, const float* mdt0 = nullptr);
 void launch_advect2(hipStream_t s, int st, void* da, const void* d0a, int ba, void* db, const void* d0b, int bb, const void* u,
-                    const void* v, int pitch, int n, int row_lo, int row_hi, float dt0, Members mb = {});
+                    const void* v, int pitch, int n, int row_lo, int row_hi, float dt0, Members mb = {}, const float* mdt0 = nullptr);
 // pscale: power of two the divergence is stored multiplied by (1: plain)
 void launch_divergence(hipStream_t s, int st, const void* u, const void* v, void* p, void* div, int pitch, int n,
                        int row_lo, int row_hi, float h, int write_p, float pscale = 1.0f, Members mb = {});
@@ -125,7 +139,8 @@ void launch_subtract_gradient(hipStream_t s, int st, void* u, void* v, const voi
                               int row_hi, float h, float* partials = nullptr, unsigned int* max_out = nullptr, float pinv = 1.0f,
                               Members mb = {});
 void launch_gradient_advect(hipStream_t s, int st, void* u, void* v, const void* p, void* d, const void* d0, int pitch, int n,
-                            int row_lo, int row_hi, float h, float dt0, int b, float pinv = 1.0f, Members mb = {});
+                            int row_lo, int row_hi, float h, float dt0, int b, float pinv = 1.0f, Members mb = {},
+                            const float* mdt0 = nullptr);
 // (absmax2, residual: the maximum over all members -- every block ends in an atomicMax on the one word)
 void launch_absmax2(hipStream_t s, int st, const void* u, const void* v, int pitch, int n, int row_lo, int row_hi,
                     unsigned int* result, Members mb = {});

@@ -182,8 +182,9 @@ __global__ __launch_bounds__(256) void k_set_bnd(S* __restrict__ f, int pitch, i
 // ---------------------------------------------------------------------------
 template <typename S>
 __global__ __launch_bounds__(256) void k_add_source(S* __restrict__ x, const S* __restrict__ s, int pitch, int row_lo,
-                                                    int row_hi, float dt, size_t ms)
+                                                    int row_hi, float dt, size_t ms, const float* __restrict__ mdt)
 {
+    if (mdt) dt = mdt[blockIdx.y];          // this member's own dt (wave-uniform)
     const int nvec = pitch >> 2;
     const size_t total = (size_t)(row_hi - row_lo) * nvec;
     S* xv = x + blockIdx.y * ms + (size_t)row_lo * pitch;
@@ -202,8 +203,10 @@ __global__ __launch_bounds__(256) void k_add_source(S* __restrict__ x, const S* 
 // add_source when the source field is known to be all +0: x += inc with inc = dt*(+0)
 // formed on the host (so x = -0 still becomes +0 for dt >= 0, exactly as x + dt*0 does).
 template <typename S>
-__global__ __launch_bounds__(256) void k_add_zero_source(S* __restrict__ x, int pitch, int row_lo, int row_hi, float inc, size_t ms)
+__global__ __launch_bounds__(256) void k_add_zero_source(S* __restrict__ x, int pitch, int row_lo, int row_hi, float inc, size_t ms,
+                                                         const float* __restrict__ minc)
 {
+    if (minc) inc = minc[blockIdx.y];       // this member's own increment (wave-uniform)
     const int nvec = pitch >> 2;
     const size_t total = (size_t)(row_hi - row_lo) * nvec;
     S* xv = x + blockIdx.y * ms + (size_t)row_lo * pitch;
@@ -246,8 +249,13 @@ __global__ __launch_bounds__(256) void k_scale(S* __restrict__ x, int pitch, int
 template <typename S>
 __global__ __launch_bounds__(256) void k_jacobi_naive(const S* __restrict__ x, const S* __restrict__ x0,
                                                       S* __restrict__ out, int pitch, int n, int row_lo,
-                                                      int row_hi, float alpha, float beta, int b, size_t ms)
+                                                      int row_hi, float alpha, float beta, int b, size_t ms, const float2* __restrict__ mab)
 {
+    if (mab) {                              // this member's own coefficients (wave-uniform)
+        const float2 ab = mab[blockIdx.z];
+        alpha = ab.x;
+        beta = ab.y;
+    }
     const int j = 1 + blockIdx.x * 64 + (threadIdx.x & 63);
     const int i = row_lo + blockIdx.y * 4 + (threadIdx.x >> 6);
     if (j > n || i >= row_hi) return;
@@ -269,8 +277,13 @@ constexpr int LT_X = 64, LT_Y = 16;
 template <typename S>
 __global__ __launch_bounds__(256) void k_jacobi_lds(const S* __restrict__ x, const S* __restrict__ x0,
                                                     S* __restrict__ out, int pitch, int n, int row_lo,
-                                                    int row_hi, float alpha, float beta, int b, size_t ms)
+                                                    int row_hi, float alpha, float beta, int b, size_t ms, const float2* __restrict__ mab)
 {
+    if (mab) {                              // this member's own coefficients (wave-uniform)
+        const float2 ab = mab[blockIdx.z];
+        alpha = ab.x;
+        beta = ab.y;
+    }
     __shared__ float tile[LT_Y + 2][LT_X + 2 + 1];
     x += blockIdx.z * ms; x0 += blockIdx.z * ms; out += blockIdx.z * ms;
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;      // ty in 0..3
@@ -314,8 +327,13 @@ __global__ __launch_bounds__(256) void k_jacobi_lds(const S* __restrict__ x, con
 template <int RB, typename S>
 __global__ __launch_bounds__(256) void k_jacobi_stream(const S* __restrict__ x, const S* __restrict__ x0,
                                                        S* __restrict__ out, int pitch, int n, int row_lo,
-                                                       int row_hi, float alpha, float beta, int b, size_t ms)
+                                                       int row_hi, float alpha, float beta, int b, size_t ms, const float2* __restrict__ mab)
 {
+    if (mab) {                              // this member's own coefficients (wave-uniform)
+        const float2 ab = mab[blockIdx.z];
+        alpha = ab.x;
+        beta = ab.y;
+    }
     x += blockIdx.z * ms; x0 += blockIdx.z * ms; out += blockIdx.z * ms;
     const int lane = threadIdx.x & 63;
     const int vec = blockIdx.x * 256 + threadIdx.x;     // float4 index along the row
@@ -1054,8 +1072,27 @@ __global__ __launch_bounds__(256, tb_waves_per_simd(T, NV)) void k_jacobi_tb(TbB
     const S* __restrict__ x = static_cast<const S*>(batch.x[sv]) + mofs;
     const S* __restrict__ x0 = static_cast<const S*>(batch.x0[sv]) + mofs;
     S* __restrict__ out = static_cast<S*>(batch.out[sv]) + mofs;
-    const float alpha = batch.alpha[sv], beta = batch.beta[sv];
-    const double yd = batch.yd[sv];
+    // the solve's constants: the launch's own, or this member's record of the table (fluid_*_members) -- wave-uniform loads
+    // either way, and nothing below this prologue knows which
+    float alpha = batch.alpha[sv], beta = batch.beta[sv];
+    double yd = batch.yd[sv];
+    float k_hi = batch.hi[sv], k_lo = batch.lo[sv], x0_inc = batch.x0_inc[sv], div_scale = batch.div_scale;
+    unsigned tile_thr = batch.tile_thr[sv];
+    if (batch.mk != nullptr) {
+        // (through the constant address space -- nothing on the device writes the table -- so that a wave-uniform address
+        // gives scalar loads into SGPRs: a generic pointer here made the compiler select between the two ADDRESSES and
+        // load per lane, eleven more VGPRs for the whole march)
+        typedef const TbMemberK __attribute__((address_space(4))) * MemberKPtr;
+        const MemberKPtr mk = (MemberKPtr)(uintptr_t)batch.mk + ((size_t)sv * (unsigned)batch.members + member);
+        alpha = mk->alpha;
+        beta = mk->beta;
+        yd = mk->yd;
+        k_hi = mk->hi;
+        k_lo = mk->lo;
+        x0_inc = mk->x0_inc;
+        if (ADDSRC) div_scale = mk->div_scale;
+        if (DIVMODE == 3) tile_thr = mk->tile_thr;
+    }
     const int b = batch.b[sv];
     constexpr int HL = (T + NV - 1) / NV;                // lanes of overlap per side: T columns
     constexpr int VS = 64 - 2 * HL;
@@ -1074,9 +1111,9 @@ __global__ __launch_bounds__(256, tb_waves_per_simd(T, NV)) void k_jacobi_tb(TbB
     const int rbw = edge ? rb_edge : rb;
     TbArgs<S, NV> a;
     a.k.yd = yd;
-    a.k.lo = batch.lo[sv];
-    a.k.hi = batch.hi[sv];
-    a.x0_inc = batch.x0_inc[sv];
+    a.k.lo = k_lo;
+    a.k.hi = k_hi;
+    a.x0_inc = x0_inc;
     int seg_hi = row_hi;                                 // this wave's output rows [q_lo, q_hi): strips do not straddle the hole
     a.q_lo = row_lo + strip * rbw;
     if (g.hole_lo < g.hole_hi) {
@@ -1106,7 +1143,7 @@ __global__ __launch_bounds__(256, tb_waves_per_simd(T, NV)) void k_jacobi_tb(TbB
         S* dv = (DIVSRC || ADDSRC) ? static_cast<S*>(batch.div[sv]) + mofs : out;
         a.dc = dv + cofs;
         a.bd = __builtin_amdgcn_make_buffer_rsrc(dv, 0, field_bytes, 0x00020000);
-        a.div_scale = batch.div_scale;
+        a.div_scale = div_scale;
         a.row_bytes = (unsigned)((size_t)pitch * sizeof(S));
         const unsigned col = (unsigned)((XOFF + 1 + NV * (ptrdiff_t)k) * (ptrdiff_t)sizeof(S));
         a.ld_off = ld_ok ? col : kBufOff;
@@ -1141,7 +1178,7 @@ __global__ __launch_bounds__(256, tb_waves_per_simd(T, NV)) void k_jacobi_tb(TbB
         // lanes past the row's ends compute is never stored)
         // this member's own minima: a wave never takes the two-term path on the strength of another member's
         const unsigned* __restrict__ tiles = batch.tiles[sv] ? batch.tiles[sv] + (size_t)member * batch.tile_mstride : nullptr;
-        const unsigned thr = batch.tile_thr[sv];
+        const unsigned thr = tile_thr;
         const int tr0 = (max(1, a.q_lo - T + 1) - 1) / kTileRows, tr1 = (min(n, a.q_hi + T - 2) - 1) / kTileRows;
         const int c0 = max(1, 1 + NV * (win * VS - HL)), c1 = min(n, NV * (win * VS - HL + 64));
         const int tc0 = (c0 - 1) / kTileCols, tc1 = (c1 - 1) / kTileCols, ntc = tc1 - tc0 + 1;
@@ -1329,9 +1366,10 @@ __device__ __forceinline__ void wave_cells_out(S* __restrict__ p, int cells, flo
 template <typename S, typename IDX>
 __global__ __launch_bounds__(256) void k_advect(S* __restrict__ d, const S* __restrict__ d0, const S* __restrict__ u,
                                                 const S* __restrict__ v, int pitch, int n, int row_lo, int row_hi,
-                                                float dt0, int b, size_t ms)
+                                                float dt0, int b, size_t ms, const float* __restrict__ mdt0)
 {
     __shared__ __attribute__((aligned(16))) float tiles[4][2][256];
+    if (mdt0) dt0 = mdt0[blockIdx.z];       // this member's own dt * N (wave-uniform)
     // the member's offset goes into the scalar bases: the offsets' width (IDX) depends on one field's size only
     d += blockIdx.z * ms; d0 += blockIdx.z * ms; u += blockIdx.z * ms; v += blockIdx.z * ms;
     const int j0 = advect_col0();
@@ -1365,9 +1403,11 @@ __global__ __launch_bounds__(256) void k_advect(S* __restrict__ d, const S* __re
 template <typename S, typename IDX>
 __global__ __launch_bounds__(256) void k_advect2(S* __restrict__ da, const S* __restrict__ d0a, int ba, S* __restrict__ db,
                                                  const S* __restrict__ d0b, int bb, const S* __restrict__ u,
-                                                 const S* __restrict__ v, int pitch, int n, int row_lo, int row_hi, float dt0, size_t ms)
+                                                 const S* __restrict__ v, int pitch, int n, int row_lo, int row_hi, float dt0, size_t ms,
+                                                 const float* __restrict__ mdt0)
 {
     __shared__ __attribute__((aligned(16))) float tiles[4][2][256];
+    if (mdt0) dt0 = mdt0[blockIdx.z];       // this member's own dt * N (wave-uniform)
     da += blockIdx.z * ms; d0a += blockIdx.z * ms; db += blockIdx.z * ms; d0b += blockIdx.z * ms; u += blockIdx.z * ms; v += blockIdx.z * ms;
     const int j0 = advect_col0();
     const int i = row_lo + blockIdx.y;
@@ -1517,8 +1557,10 @@ __global__ __launch_bounds__(256) void k_max_partials(const float* __restrict__ 
 template <typename S, typename IDX>
 __global__ __launch_bounds__(256) void k_gradient_advect(S* __restrict__ u, S* __restrict__ v, const S* __restrict__ p,
                                                          S* __restrict__ d, const S* __restrict__ d0, int pitch, int n,
-                                                         int row_lo, int row_hi, float h, float dt0, int b, float pinv, size_t ms)
+                                                         int row_lo, int row_hi, float h, float dt0, int b, float pinv, size_t ms,
+                                                         const float* __restrict__ mdt0)
 {
+    if (mdt0) dt0 = mdt0[blockIdx.z];       // this member's own dt * N (wave-uniform)
     u += blockIdx.z * ms; v += blockIdx.z * ms; p += blockIdx.z * ms; d += blockIdx.z * ms; d0 += blockIdx.z * ms;
     const int j0 = advect_col0();
     const int i = row_lo + blockIdx.y;
@@ -1661,14 +1703,16 @@ void launch_set_bnd(hipStream_t s, int st, void* f, int pitch, int n, int b, Mem
 }
 
 // src == nullptr: the source is known to be all +0 (dt is then the pre-multiplied increment dt*0)
-void launch_add_source(hipStream_t s, int st, void* x, const void* src, int pitch, int row_lo, int row_hi, float dt, Members mb)
+void launch_add_source(hipStream_t s, int st, void* x, const void* src, int pitch, int row_lo, int row_hi, float dt, Members mb,
+                       const float* mdt)
 {
     const dim3 grid(stride_blocks(pitch, row_lo, row_hi), mb.count);
     if (!src) {
-        FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_add_zero_source<S>, grid, dim3(256), 0, s, (S*)x, pitch, row_lo, row_hi, dt, mb.stride));
+        FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_add_zero_source<S>, grid, dim3(256), 0, s, (S*)x, pitch, row_lo, row_hi, dt, mb.stride, mdt));
         return;
     }
-    FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_add_source<S>, grid, dim3(256), 0, s, (S*)x, (const S*)src, pitch, row_lo, row_hi, dt, mb.stride));
+    FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_add_source<S>, grid, dim3(256), 0, s, (S*)x, (const S*)src, pitch, row_lo, row_hi, dt, mb.stride,
+                                            mdt));
 }
 
 void launch_scale(hipStream_t s, int st, void* x, int pitch, int row_lo, int row_hi, float factor, Members mb)
@@ -1678,7 +1722,7 @@ void launch_scale(hipStream_t s, int st, void* x, int pitch, int row_lo, int row
 }
 
 void launch_jacobi(hipStream_t s, int st, int variant, const void* x, const void* x0, void* out, int pitch, int n,
-                   int row_lo, int row_hi, float alpha, float beta, int b, Members mb)
+                   int row_lo, int row_hi, float alpha, float beta, int b, Members mb, const float2* mab)
 {
     const int rows = row_hi - row_lo;
     if (rows <= 0) return;
@@ -1686,19 +1730,19 @@ void launch_jacobi(hipStream_t s, int st, int variant, const void* x, const void
     case JACOBI_NAIVE:
         FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_jacobi_naive<S>, dim3(cdiv(n, 64), cdiv(rows, 4), mb.count), dim3(256), 0, s,
                                                 (const S*)x, (const S*)x0, (S*)out, pitch, n, row_lo, row_hi, alpha,
-                                                beta, b, mb.stride));
+                                                beta, b, mb.stride, mab));
         break;
     case JACOBI_LDS:
         FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_jacobi_lds<S>, dim3(cdiv(n, LT_X), cdiv(rows, LT_Y), mb.count), dim3(256), 0, s,
                                                 (const S*)x, (const S*)x0, (S*)out, pitch, n, row_lo, row_hi, alpha,
-                                                beta, b, mb.stride));
+                                                beta, b, mb.stride, mab));
         break;
     default: {
         constexpr int RB = 8;
         const unsigned nvec = (n + 3) / 4;
         FLUID_BY_STORAGE(st, hipLaunchKernelGGL((k_jacobi_stream<RB, S>), dim3(cdiv(nvec, 256), cdiv(rows, RB), mb.count), dim3(256),
                                                 0, s, (const S*)x, (const S*)x0, (S*)out, pitch, n, row_lo, row_hi,
-                                                alpha, beta, b, mb.stride));
+                                                alpha, beta, b, mb.stride, mab));
     }
     }
 }
@@ -1784,21 +1828,22 @@ void launch_validate_div(hipStream_t s, int divmode, float beta, float kbeta, do
 }
 
 void launch_advect(hipStream_t s, int st, void* d, const void* d0, const void* u, const void* v, int pitch, int n,
-                   int row_lo, int row_hi, float dt0, int b, Members mb)
+                   int row_lo, int row_hi, float dt0, int b, Members mb, const float* mdt0)
 {
     if (row_hi <= row_lo) return;
     const dim3 grid(cdiv(n, 1024), row_hi - row_lo, mb.count);
     FLUID_BY_STORAGE_INDEX(st, pitch, n, hipLaunchKernelGGL((k_advect<S, I>), grid, dim3(256), 0, s, (S*)d, (const S*)d0, (const S*)u,
-                                                            (const S*)v, pitch, n, row_lo, row_hi, dt0, b, mb.stride));
+                                                            (const S*)v, pitch, n, row_lo, row_hi, dt0, b, mb.stride, mdt0));
 }
 
 void launch_advect2(hipStream_t s, int st, void* da, const void* d0a, int ba, void* db, const void* d0b, int bb, const void* u,
-                    const void* v, int pitch, int n, int row_lo, int row_hi, float dt0, Members mb)
+                    const void* v, int pitch, int n, int row_lo, int row_hi, float dt0, Members mb, const float* mdt0)
 {
     if (row_hi <= row_lo) return;
     const dim3 grid(cdiv(n, 1024), row_hi - row_lo, mb.count);
     FLUID_BY_STORAGE_INDEX(st, pitch, n, hipLaunchKernelGGL((k_advect2<S, I>), grid, dim3(256), 0, s, (S*)da, (const S*)d0a, ba, (S*)db,
-                                                            (const S*)d0b, bb, (const S*)u, (const S*)v, pitch, n, row_lo, row_hi, dt0, mb.stride));
+                                                            (const S*)d0b, bb, (const S*)u, (const S*)v, pitch, n, row_lo, row_hi, dt0, mb.stride,
+                                                            mdt0));
 }
 
 void launch_divergence(hipStream_t s, int st, const void* u, const void* v, void* p, void* div, int pitch, int n,
@@ -1827,12 +1872,13 @@ void launch_subtract_gradient(hipStream_t s, int st, void* u, void* v, const voi
 }
 
 void launch_gradient_advect(hipStream_t s, int st, void* u, void* v, const void* p, void* d, const void* d0, int pitch, int n,
-                            int row_lo, int row_hi, float h, float dt0, int b, float pinv, Members mb)
+                            int row_lo, int row_hi, float h, float dt0, int b, float pinv, Members mb, const float* mdt0)
 {
     if (row_hi <= row_lo) return;
     const dim3 grid(cdiv(n, 1024), row_hi - row_lo, mb.count);
     FLUID_BY_STORAGE_INDEX(st, pitch, n, hipLaunchKernelGGL((k_gradient_advect<S, I>), grid, dim3(256), 0, s, (S*)u, (S*)v, (const S*)p,
-                                                            (S*)d, (const S*)d0, pitch, n, row_lo, row_hi, h, dt0, b, pinv, mb.stride));
+                                                            (S*)d, (const S*)d0, pitch, n, row_lo, row_hi, h, dt0, b, pinv, mb.stride,
+                                                            mdt0));
 }
 
 void launch_absmax2(hipStream_t s, int st, const void* u, const void* v, int pitch, int n, int row_lo, int row_hi,

@@ -81,6 +81,103 @@ int check_fields(const fluid_ctx* c, std::initializer_list<int> ids)
     return FLUID_OK;
 }
 
+// A call's physical parameter: one scalar for every member (the classic calls), or one value per member (the
+// fluid_*_members calls; `m` then points at fluid_members() floats the library owns for the duration of the call).
+struct MVal {
+    float s;
+    const float* m;
+    MVal(float v) : s(v), m(nullptr) {}
+    MVal(float v, const float* pm) : s(v), m(pm) {}
+    float at(int i) const { return m ? m[i] : s; }
+};
+
+// ---- tables of per-member constants (fluid_ctx.h: ConstRing) -------------------------------------------------------
+constexpr size_t kConstAlign = 256, kConstSlots = 8, kConstBlobs = 64;
+size_t const_pad(size_t len) { return (len + kConstAlign - 1) / kConstAlign * kConstAlign; }
+
+// the ring, allocated once: at the first fluid_*_members call of a context with more than one member
+int ensure_consts(fluid_ctx* c)
+{
+    ConstRing& r = c->consts;
+    if (r.dev) return FLUID_OK;
+    // the largest table is a batch's: 3 solves x members records; room for kConstSlots of them
+    const size_t bytes = std::max<size_t>(64u << 10, kConstSlots * const_pad(3 * (size_t)c->members * sizeof(fluid::TbMemberK)));
+    HIP_TRY(hipMalloc((void**)&r.dev, bytes));
+    HIP_TRY(hipHostMalloc((void**)&r.host, bytes, hipHostMallocDefault));
+    for (size_t k = 0; k < kConstBlobs; ++k) {
+        hipEvent_t ev;
+        HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        r.free_events.push_back(ev);
+    }
+    r.bytes = bytes;
+    return FLUID_OK;
+}
+
+// *dev: device memory that holds `len` bytes equal to `data` for every launch enqueued on the context's stream from now
+// until the next call of this function
+int member_consts(fluid_ctx* c, const void* data, size_t len, const void** dev)
+{
+    ConstRing& r = c->consts;
+    if (!r.dev || const_pad(len) * kConstSlots > r.bytes) return fail(FLUID_E_INVALID, "per-member constants: no table (internal)");
+    unsigned long long hash = 1469598103934665603ull;
+    for (size_t k = 0; k < len; ++k) hash = (hash ^ static_cast<const unsigned char*>(data)[k]) * 1099511628211ull;
+    for (const ConstRing::Blob& b : r.live)
+        if (b.len == len && b.hash == hash && std::memcmp(r.host + b.off, data, len) == 0) {
+            *dev = r.dev + b.off;
+            return FLUID_OK;
+        }
+    if (r.head + const_pad(len) > r.bytes) r.head = 0;
+    const size_t lo = r.head, hi = lo + const_pad(len);
+    // The tables this one overwrites (and the oldest, if all events are out) leave the ring.  Their device bytes are safe
+    // without a wait: the copy below runs behind every launch enqueued so far.  Their host bytes must have been read:
+    // that copy was enqueued kConstSlots tables ago, so the wait is a formality unless the queue is that deep.
+    for (size_t k = 0; k < r.live.size();) {
+        const ConstRing::Blob b = r.live[k];
+        const bool overlap = b.off < hi && lo < b.off + const_pad(b.len);
+        if (!overlap && !(k == 0 && r.free_events.empty())) {
+            ++k;
+            continue;
+        }
+        HIP_TRY(hipEventSynchronize(b.copied));
+        r.free_events.push_back(b.copied);
+        r.live.erase(r.live.begin() + (ptrdiff_t)k);
+    }
+    std::memcpy(r.host + lo, data, len);
+    HIP_TRY(hipMemcpyAsync(r.dev + lo, r.host + lo, len, hipMemcpyHostToDevice, c->stream));
+    hipEvent_t ev = r.free_events.back();
+    r.free_events.pop_back();
+    HIP_TRY(hipEventRecord(ev, c->stream));
+    r.live.push_back({lo, len, hash, ev});
+    r.head = hi;
+    r.uploads += 1;
+    *dev = r.dev + lo;
+    return FLUID_OK;
+}
+
+// the single-sweep kernels' {alpha, beta} per member (nullptr: the scalars hold)
+int member_pairs(fluid_ctx* c, const float* alpha, const float* beta, const float2** dev)
+{
+    *dev = nullptr;
+    if (!alpha || !beta) return FLUID_OK;
+    std::vector<float2> ab(c->members);
+    for (int m = 0; m < c->members; ++m) ab[m] = make_float2(alpha[m], beta[m]);
+    const void* p = nullptr;
+    TRY(member_consts(c, ab.data(), ab.size() * sizeof ab[0], &p));
+    *dev = static_cast<const float2*>(p);
+    return FLUID_OK;
+}
+
+// a device array with one float per member, or nullptr when `v` is empty (the scalar holds for everybody)
+int member_floats(fluid_ctx* c, const std::vector<float>& v, const float** dev)
+{
+    *dev = nullptr;
+    if (v.empty()) return FLUID_OK;
+    const void* p = nullptr;
+    TRY(member_consts(c, v.data(), v.size() * sizeof(float), &p));
+    *dev = static_cast<const float*>(p);
+    return FLUID_OK;
+}
+
 // the bit of fluid_ctx::xowed of the compute stream work is enqueued on now
 unsigned stream_bit(const fluid_ctx* c) { return c->stream2 && c->stream == c->stream2 ? 2u : 1u; }
 
@@ -230,7 +327,8 @@ float round_down_to_float(double v)
     return f;
 }
 
-DivPlan division_mode(fluid_ctx* c, float beta, float alpha)
+// `force` (2): the mode to try instead of the best one for this beta -- what a solve whose members disagree settles on
+DivPlan division_mode(fluid_ctx* c, float beta, float alpha, int force = 0)
 {
     DivPlan plan;
     plan.arg = beta;
@@ -248,7 +346,7 @@ DivPlan division_mode(fluid_ctx* c, float beta, float alpha)
     // mode 5 (the default for every other beta): r = RN32(1/beta), beta * 2^24 and r * 2^-24 must be ordinary numbers
     const bool residual = c->fast_div == 2 && beta >= 0x1p-60f && beta <= 0x1p60f;
     const float r5_hi = beta * 0x1p24f, r5_lo = -(rbeta * 0x1p-24f);
-    int want = (pow2 && alpha == 1.0f) ? 4 : two_term ? 3 : residual ? 5 : 2;
+    int want = force ? force : (pow2 && alpha == 1.0f) ? 4 : two_term ? 3 : residual ? 5 : 2;
     unsigned bits;
     std::memcpy(&bits, &beta, sizeof bits);
     int dev = 0;
@@ -385,8 +483,10 @@ int settle(fluid_ctx* c, int f, bool keep_scale = false)
     int lo, hi;
     rows_with_walls(c, reach, &lo, &hi);
     const float inc = c->field[f].pend_inc;
+    const float* minc = nullptr;
+    TRY(member_floats(c, c->field[f].pend_incv, &minc));       // each member its own increment
     c->field[f].pend = false;
-    TIMED(c, FLUID_TIME_SOURCE, fluid::launch_add_source(c->stream, c->st, c->ptr(f), nullptr, c->pitch, lo, hi, inc, c->mb()));
+    TIMED(c, FLUID_TIME_SOURCE, fluid::launch_add_source(c->stream, c->st, c->ptr(f), nullptr, c->pitch, lo, hi, inc, c->mb(), minc));
     return FLUID_OK;
 }
 
@@ -400,8 +500,11 @@ int settle_source(fluid_ctx* c, int f)
     const int reach = c->nranks > 1 ? std::min({c->field[f].reach, c->field[s].reach, exchange_cap(c)}) : 0;
     int lo, hi;
     rows_with_walls(c, reach, &lo, &hi);
+    const float* mdt = nullptr;
+    TRY(member_floats(c, c->field[f].src_dtv, &mdt));           // each member its own dt
     c->field[f].src_of = 0;
-    TIMED(c, FLUID_TIME_SOURCE, fluid::launch_add_source(c->stream, c->st, c->ptr(f), c->ptr(s), c->pitch, lo, hi, c->field[f].src_dt, c->mb()));
+    TIMED(c, FLUID_TIME_SOURCE,
+          fluid::launch_add_source(c->stream, c->st, c->ptr(f), c->ptr(s), c->pitch, lo, hi, c->field[f].src_dt, c->mb(), mdt));
     wrote(c, f, reach);
     return FLUID_OK;
 }
@@ -425,7 +528,7 @@ void mark_zero(fluid_ctx* c, int f) { wrote(c, f, kEverywhere); c->field[f].zero
 // there): with the fused Jacobi kernel a real source is not added now -- the first launch of the solve whose right-hand
 // side x is and whose first guess s is (FluidSequential.c:181, :201, :209: SWAP, then diffuse) reads both fields anyway,
 // forms x + dt*s as it loads them and stores the sum out of place (op_diffuse_batch).  Any other reader settles it first.
-int op_add_source(fluid_ctx* c, int x, int s, float dt, bool defer = false)
+int op_add_source(fluid_ctx* c, int x, int s, MVal dt, bool defer = false)
 {
     // pointwise: valid as far out as both operands are
     const int reach = c->nranks > 1 ? std::min({c->field[x].reach, c->field[s].reach, exchange_cap(c)}) : 0;
@@ -434,21 +537,31 @@ int op_add_source(fluid_ctx* c, int x, int s, float dt, bool defer = false)
     TRY(materialize(c, x));
     if (c->field[s].zero) {
         volatile float z = 0.0f;
-        const float inc = dt * z;          // the reference's dt * s[i] with s[i] = +0 (sign and NaN rules included)
+        const float inc = dt.at(0) * z;    // the reference's dt * s[i] with s[i] = +0 (sign and NaN rules included)
+        std::vector<float> incv;           // ... per member: +0 or -0 as each member's dt has it
+        if (dt.m)
+            for (int m = 0; m < c->members; ++m) incv.push_back(dt.m[m] * z);
         if (c->variant == fluid::JACOBI_TB && c->defer_zero_source) {
             c->field[x].pend = true;             // (x was settled just above: one pending increment at a time)
             c->field[x].pend_inc = inc;
+            c->field[x].pend_incv = std::move(incv);
             return FLUID_OK;               // x's reach unchanged: nothing was written
         }
-        TIMED(c, FLUID_TIME_SOURCE, fluid::launch_add_source(c->stream, c->st, c->ptr(x), nullptr, c->pitch, lo, hi, inc, c->mb()));
+        const float* minc = nullptr;
+        TRY(member_floats(c, incv, &minc));
+        TIMED(c, FLUID_TIME_SOURCE, fluid::launch_add_source(c->stream, c->st, c->ptr(x), nullptr, c->pitch, lo, hi, inc, c->mb(), minc));
     } else {
         TRY(settle(c, s));                 // (a source that is itself owed something: never inside a step)
         if (defer && c->fuse_add_source && c->variant == fluid::JACOBI_TB && fluid::jacobi_tb_exists(-1, -1, c->tb_nv, fluid::TB_ADDSRC)) {
             c->field[x].src_of = 1 + s;
-            c->field[x].src_dt = dt;
+            c->field[x].src_dt = dt.at(0);
+            c->field[x].src_dtv.assign(dt.m, dt.m + (dt.m ? c->members : 0));
             return FLUID_OK;               // x's reach unchanged: nothing was written
         }
-        TIMED(c, FLUID_TIME_SOURCE, fluid::launch_add_source(c->stream, c->st, c->ptr(x), c->ptr(s), c->pitch, lo, hi, dt, c->mb()));
+        const float* mdt = nullptr;
+        if (dt.m) TRY(member_floats(c, std::vector<float>(dt.m, dt.m + c->members), &mdt));
+        TIMED(c, FLUID_TIME_SOURCE,
+              fluid::launch_add_source(c->stream, c->st, c->ptr(x), c->ptr(s), c->pitch, lo, hi, dt.at(0), c->mb(), mdt));
     }
     wrote(c, x, reach);
     return FLUID_OK;
@@ -686,6 +799,7 @@ int pick_sweeps(const fluid_ctx* c, int remaining, int room, const SweepShape& s
 struct Solve {
     int b, x, x0;
     float alpha, beta;
+    const float *malpha = nullptr, *mbeta = nullptr;     // fluid_*_members: one pair per member (alpha, beta above: member 0's)
 };
 
 // FluidSequential.c:85-104.  Results land in the fields `x`.  A sweep that writes
@@ -715,6 +829,7 @@ struct Batch {
     const int* sum;            // where x0 + dt*s of a deferred add_source lands
     int cur[3], nxt[3];        // the fields each solve's next launch reads its guess from / writes to
     DivPlan plan[3];
+    std::vector<DivPlan> mplan[3];   // a solve with per-member coefficients: each member's constants, all of plan[k].mode
     bool same_mode, all_mode4, add_src;   // add_src: the right-hand sides' deferred add_source rides in the first launch
     float out_scale[3];
     SweepShape shape;
@@ -724,6 +839,34 @@ struct Batch {
 // (per solve AND member: slot s holds `members` tables back to back)
 size_t tile_words(const fluid_ctx* c) { return (size_t)fluid::tile_rows(c->n) * fluid::tile_pitch(c->n); }
 unsigned* solve_tiles(const fluid_ctx* c, int slot) { return c->tiles + (size_t)slot * c->members * tile_words(c); }
+
+// Division modes across the members of one solve.  The mode is a template parameter of the kernel, so one launch runs one
+// mode, and the members of a solve cannot be launched apart (every member goes through the same launches): each member's
+// beta is planned as a solve of its own would be (division_mode: proof per distinct beta, cached per process), and the solve
+// takes the members' common mode if they agree -- the ordinary case -- and otherwise the most general one proven for every
+// member's beta: 2, else 0.  Every mode is exact, so only speed depends on the choice.
+void plan_members(fluid_ctx* c, const float* alpha, const float* beta, std::vector<DivPlan>& out)
+{
+    const int M = c->members;
+    out.resize(M);
+    bool same = true;
+    for (int m = 0; m < M; ++m) {
+        out[m] = (m > 0 && beta[m] == beta[m - 1] && alpha[m] == alpha[m - 1]) ? out[m - 1] : division_mode(c, beta[m], alpha[m]);
+        same = same && out[m].mode == out[0].mode;
+    }
+    if (same) return;
+    bool all2 = true;
+    for (int m = 0; m < M; ++m) {
+        out[m] = division_mode(c, beta[m], alpha[m], /*force=*/2);
+        all2 = all2 && out[m].mode == 2;
+    }
+    if (all2) return;
+    for (int m = 0; m < M; ++m) {
+        out[m] = DivPlan{};
+        out[m].arg = beta[m];
+        out[m].yd = 1.0 / (double)beta[m];
+    }
+}
 
 // argument checks, the scales of the solves reconciled, right-hand sides that are zero by definition materialised
 int batch_prepare(fluid_ctx* c, Batch& B)
@@ -780,6 +923,11 @@ int batch_plan(fluid_ctx* c, Batch& B)
         B.nxt[k] = B.scratch[k];
         B.plan[k].arg = sv[k].beta;
         if (c->variant == fluid::JACOBI_TB) B.plan[k] = division_mode(c, sv[k].beta, sv[k].alpha);
+        if (c->variant == fluid::JACOBI_TB && sv[k].mbeta) {
+            if (k > 0 && sv[k].mbeta == sv[k - 1].mbeta && sv[k].malpha == sv[k - 1].malpha) B.mplan[k] = B.mplan[k - 1];   // (u and v)
+            else plan_members(c, sv[k].malpha, sv[k].mbeta, B.mplan[k]);
+            B.plan[k] = B.mplan[k][0];            // (the mode is every member's; the constants are read per member)
+        }
         B.same_mode = B.same_mode && B.plan[k].mode == B.plan[0].mode;
         B.all_mode4 = B.all_mode4 && B.plan[k].mode == 4;
     }
@@ -791,7 +939,7 @@ int batch_plan(fluid_ctx* c, Batch& B)
     bool add_src = x00.src_of != 0 && B.ds == nullptr && B.same_mode;
     for (int k = 0; k < B.count; ++k) {
         const FieldState &x = c->field[sv[k].x], &x0 = c->field[sv[k].x0];
-        add_src = add_src && x0.src_of == 1 + sv[k].x && x0.src_dt == x00.src_dt && !x.zero && !x.pend && !x.src_of;
+        add_src = add_src && x0.src_of == 1 + sv[k].x && x0.src_dt == x00.src_dt && x0.src_dtv == x00.src_dtv && !x.zero && !x.pend && !x.src_of;
     }
     B.add_src = add_src && fluid::jacobi_tb_exists(pick_sweeps(c, B.iters, B.iters, B.shape, B.all_mode4), B.plan[0].mode, c->tb_nv, fluid::TB_ADDSRC);
     if (!B.add_src)
@@ -830,9 +978,10 @@ int batch_reach(const fluid_ctx* c, const Batch& B)
 }
 
 // the fused kernel's arguments for solves [first, last); divsrc / addsrc: the launch forms (and stores) the right-hand sides
-fluid::TbBatch fill_batch(const fluid_ctx* c, const Batch& B, int first, int last, bool divsrc, bool addsrc)
+int fill_batch(fluid_ctx* c, const Batch& B, int first, int last, bool divsrc, bool addsrc, fluid::TbBatch* out)
 {
     fluid::TbBatch bt{};
+    bool per_member = false;
     for (int j = first; j < last; ++j) {
         const int q = j - first;
         const DivPlan& p = B.plan[j];
@@ -851,6 +1000,8 @@ fluid::TbBatch fill_batch(const fluid_ctx* c, const Batch& B, int first, int las
         bt.x_zero[q] = c->field[B.cur[j]].zero ? 1 : 0;
         bt.x0_inc[q] = x0.pend && !addsrc && !divsrc ? x0.pend_inc : -0.0f;     // x + (-0) is x for every x
         if (addsrc) bt.div[q] = c->ptr(B.sum[j]);
+        per_member = per_member || !B.mplan[j].empty() || (x0.pend && !addsrc && !divsrc && !x0.pend_incv.empty()) ||
+                     (addsrc && !x0.src_dtv.empty());
     }
     bt.count = last - first;
     bt.members = c->members;
@@ -864,7 +1015,34 @@ fluid::TbBatch fill_batch(const fluid_ctx* c, const Batch& B, int first, int las
         bt.div[0] = c->ptr(B.sv[0].x0);
         bt.div_scale = B.ds->scale;
     }
-    return bt;
+    // something differs from member to member (fluid_*_members): the constants above, once per (solve, member), in a table
+    if (per_member && c->members > 1) {
+        const int M = c->members;
+        std::vector<fluid::TbMemberK> rec((size_t)bt.count * M);
+        for (int j = first; j < last; ++j) {
+            const int q = j - first;
+            const FieldState& x0 = c->field[B.sv[j].x0];
+            const std::vector<float>& dtv = c->field[B.sv[first].x0].src_dtv;     // (batch_plan: the same for all solves)
+            for (int m = 0; m < M; ++m) {
+                const DivPlan& p = B.mplan[j].empty() ? B.plan[j] : B.mplan[j][m];
+                fluid::TbMemberK& r = rec[(size_t)q * M + m];
+                r.yd = p.yd;
+                r.alpha = B.sv[j].malpha ? B.sv[j].malpha[m] : B.sv[j].alpha;
+                r.beta = p.arg;
+                r.hi = p.hi;
+                r.lo = p.lo;
+                r.x0_inc = x0.pend_incv.empty() ? bt.x0_inc[q] : (x0.pend && !addsrc && !divsrc ? x0.pend_incv[m] : -0.0f);
+                r.div_scale = addsrc && !dtv.empty() ? dtv[m] : bt.div_scale;
+                r.tile_thr = p.tile_thr;
+                r.pad = 0;
+            }
+        }
+        const void* dev = nullptr;
+        TRY(member_consts(c, rec.data(), rec.size() * sizeof rec[0], &dev));
+        bt.mk = static_cast<const fluid::TbMemberK*>(dev);
+    }
+    *out = bt;
+    return FLUID_OK;
 }
 
 // strip height of the two edge windows (ghost columns cost ~1.6x per row: shorter strips there keep the launch balanced)
@@ -994,9 +1172,12 @@ int batch_sweep(fluid_ctx* c, Batch& B)
             TRY(xchg_join(c));
             for (int j = 0; j < B.count; ++j) TRY(materialize(c, B.cur[j], /*keep_scale=*/true));
             for (int j = 0; j < B.count; ++j) TRY(settle(c, sv[j].x0, /*keep_scale=*/true));
-            for (int j = 0; j < B.count; ++j)
+            for (int j = 0; j < B.count; ++j) {
+                const float2* mab = nullptr;
+                TRY(member_pairs(c, sv[j].malpha, sv[j].mbeta, &mab));
                 fluid::launch_jacobi(c->stream, c->st, v, c->ptr(B.cur[j]), c->ptr(sv[j].x0), c->ptr(B.nxt[j]), c->pitch, c->n, lo, hi,
-                                     sv[j].alpha, sv[j].beta, sv[j].b, c->mb());
+                                     sv[j].alpha, sv[j].beta, sv[j].b, c->mb(), mab);
+            }
             if (c->timing) {
                 c->launches += B.count;
                 c->field_launches += (long long)B.count * c->members;
@@ -1006,7 +1187,9 @@ int batch_sweep(fluid_ctx* c, Batch& B)
             for (int first = 0, last; first < B.count; first = last) {
                 last = B.same_mode ? B.count : first + 1;
                 const bool divsrc = B.ds != nullptr && k == 0, addsrc = B.add_src && k == 0;
-                TRY(launch_fused(c, fill_batch(c, B, first, last, divsrc, addsrc), T, B.plan[first].mode, divsrc, addsrc, lo, hi));
+                fluid::TbBatch bt;
+                TRY(fill_batch(c, B, first, last, divsrc, addsrc, &bt));
+                TRY(launch_fused(c, bt, T, B.plan[first].mode, divsrc, addsrc, lo, hi));
                 if (c->timing) {
                     c->launches += 1;
                     c->field_launches += (long long)(last - first) * c->members;
@@ -1040,9 +1223,9 @@ int op_diffuse_batch(fluid_ctx* c, const Solve* sv, int count, int iters, int fi
     return timing_end(c, stop, iters * count * c->members);
 }
 
-int op_diffuse(fluid_ctx* c, int b, int x, int x0, float alpha, float beta, int iters, int final_reach = 0, const DivSource* ds = nullptr)
+int op_diffuse(fluid_ctx* c, int b, int x, int x0, MVal alpha, MVal beta, int iters, int final_reach = 0, const DivSource* ds = nullptr)
 {
-    const Solve one{b, x, x0, alpha, beta};
+    const Solve one{b, x, x0, alpha.at(0), beta.at(0), alpha.m, beta.m};
     return op_diffuse_batch(c, &one, 1, iters, final_reach, ds);
 }
 
@@ -1112,28 +1295,42 @@ int advect_bounded(fluid_ctx* c, int slot, std::initializer_list<int> sources, f
     return fetched ? run() : FLUID_OK;
 }
 
-int op_advect(fluid_ctx* c, int b, int d, int d0, int u, int v, float dt)
+// dt0 = dt * N of every member (nullptr: a scalar dt)
+int member_dt0(fluid_ctx* c, MVal dt, const float** dev)
+{
+    std::vector<float> dt0;
+    if (dt.m)
+        for (int m = 0; m < c->members; ++m) dt0.push_back(dt.m[m] * (float)c->n);
+    return member_floats(c, dt0, dev);
+}
+
+int op_advect(fluid_ctx* c, int b, int d, int d0, int u, int v, MVal dt)
 {
     if (d == d0 || d == u || d == v) return fail(FLUID_E_INVALID, "advect: output must not alias an input");
-    const float dt0 = dt * (float)c->n;
+    const float dt0 = dt.at(0) * (float)c->n;
     TRY(materialize(c, {d0, u, v}));
+    const float* mdt0 = nullptr;
+    TRY(member_dt0(c, dt, &mdt0));
     TIMED(c, FLUID_TIME_ADVECTION,
-          fluid::launch_advect(c->stream, c->st, c->ptr(d), c->ptr(d0), c->ptr(u), c->ptr(v), c->pitch, c->n, c->own0, c->own1, dt0, b, c->mb()));
+          fluid::launch_advect(c->stream, c->st, c->ptr(d), c->ptr(d0), c->ptr(u), c->ptr(v), c->pitch, c->n, c->own0, c->own1, dt0, b, c->mb(),
+                               mdt0));
     wrote(c, d, 0);
     return FLUID_OK;
 }
 
 // two advections along the same velocity (u, v) in one launch; results identical to two op_advect calls
-int op_advect2(fluid_ctx* c, int ba, int da, int d0a, int bb, int db, int d0b, int u, int v, float dt)
+int op_advect2(fluid_ctx* c, int ba, int da, int d0a, int bb, int db, int d0b, int u, int v, MVal dt)
 {
     for (int d : {da, db})
         if (d == d0a || d == d0b || d == u || d == v) return fail(FLUID_E_INVALID, "advect: output must not alias an input");
     if (da == db) return fail(FLUID_E_INVALID, "advect: outputs must be distinct");
-    const float dt0 = dt * (float)c->n;
+    const float dt0 = dt.at(0) * (float)c->n;
     TRY(materialize(c, {d0a, d0b, u, v}));
+    const float* mdt0 = nullptr;
+    TRY(member_dt0(c, dt, &mdt0));
     TIMED(c, FLUID_TIME_ADVECTION,
           fluid::launch_advect2(c->stream, c->st, c->ptr(da), c->ptr(d0a), ba, c->ptr(db), c->ptr(d0b), bb, c->ptr(u), c->ptr(v), c->pitch,
-                                c->n, c->own0, c->own1, dt0, c->mb()));
+                                c->n, c->own0, c->own1, dt0, c->mb(), mdt0));
     wrote(c, da, 0);
     wrote(c, db, 0);
     return FLUID_OK;
@@ -1187,7 +1384,7 @@ int op_subtract_gradient(fluid_ctx* c, int u, int v, int p, bool with_max = fals
 // the gradient subtraction of a projection and the advection of `d` (from d0, wall rule b) along the projected velocity,
 // in one launch: results identical to op_subtract_gradient followed by op_advect.  One GPU only (on slabs the advection
 // waits for a reduction over the velocity it follows).
-int op_gradient_advect(fluid_ctx* c, int u, int v, int p, int b, int d, int d0, float dt)
+int op_gradient_advect(fluid_ctx* c, int u, int v, int p, int b, int d, int d0, MVal dt)
 {
     if (p == u || p == v || u == v) return fail(FLUID_E_INVALID, "subtract_gradient: fields must be distinct");
     if (d == d0 || d == u || d == v || d == p || d0 == u || d0 == v)
@@ -1196,9 +1393,11 @@ int op_gradient_advect(fluid_ctx* c, int u, int v, int p, int b, int d, int d0, 
     const float h = 1.0f / (float)c->n;
     TRY(materialize(c, {u, v, d0}));
     TRY(materialize(c, p, /*keep_scale=*/true));
+    const float* mdt0 = nullptr;
+    TRY(member_dt0(c, dt, &mdt0));
     TIMED(c, FLUID_TIME_PROJECTION,
           fluid::launch_gradient_advect(c->stream, c->st, c->ptr(u), c->ptr(v), c->ptr(p), c->ptr(d), c->ptr(d0), c->pitch, c->n, c->own0,
-                                        c->own1, h, dt * (float)c->n, b, 1.0f / c->field[p].fscale, c->mb()));
+                                        c->own1, h, dt.at(0) * (float)c->n, b, 1.0f / c->field[p].fscale, c->mb(), mdt0));
     wrote(c, u, 0);
     wrote(c, v, 0);
     wrote(c, d, 0);
@@ -1216,13 +1415,28 @@ void coefficients(int n, float dt, float coef, float* alpha, float* beta)
     *beta = 1.0f + four_a;
 }
 
+// alpha, beta of a diffusion with a scalar or per-member dt and coefficient: coefficients() per member, the same function
+struct Coef {
+    float alpha, beta;
+    std::vector<float> malpha, mbeta;
+    Coef(const fluid_ctx* c, MVal dt, MVal coef)
+    {
+        coefficients(c->n, dt.at(0), coef.at(0), &alpha, &beta);
+        if (!dt.m && !coef.m) return;
+        malpha.resize(c->members);
+        mbeta.resize(c->members);
+        for (int m = 0; m < c->members; ++m) coefficients(c->n, dt.at(m), coef.at(m), &malpha[m], &mbeta[m]);
+    }
+    Solve solve(int b, int x, int x0) const { return {b, x, x0, alpha, beta, malpha.empty() ? nullptr : malpha.data(), malpha.empty() ? nullptr : mbeta.data()}; }
+};
+
 // divergence -> pressure solve -> gradient subtraction (FluidSequential.c:213-223
 // and :238-240).  On slabs: ONE exchange (u, v, iters+2 rows) covers the divergence,
 // every sweep of the solve and the gradient's one-row halo of p.
 // `then_advect` (one GPU): d, d0, b, dt of an advection along (u, v) to run in the same launch as the gradient subtraction
 struct AdvectAfter {
     int b, d, d0;
-    float dt;
+    MVal dt;
 };
 
 // can the divergence be computed inside the first launch of the pressure solve that follows it?  The fused kernel, a first
@@ -1272,36 +1486,35 @@ int project(fluid_ctx* c, int u, int v, int p, int div, int iters, const AdvectA
 
 // FluidSequential.c:189-241 with the SWAPs resolved into field roles:
 // after :201/:209 the diffused velocity lives in the *_prev buffers.
-int vel_step(fluid_ctx* c, float dt, float visc, int iters)
+int vel_step(fluid_ctx* c, MVal dt, MVal visc, int iters)
 {
     const int U = FLUID_U, V = FLUID_V, U0 = FLUID_U_PREV, V0 = FLUID_V_PREV;
-    float alpha, beta;
     TRY(op_add_source(c, U, U0, dt, /*defer=*/true));
     TRY(op_add_source(c, V, V0, dt, /*defer=*/true));
-    coefficients(c->n, dt, visc, &alpha, &beta);
+    const Coef cv(c, dt, visc);
     // one exchange feeds both solves: right-hand sides iters-1 rows out, first guesses iters rows
     const int h = std::min(iters, c->halo);
     TRY(need(c, {U, V, U0, V0}, h, /*async=*/true));
-    const Solve uv[2] = {{1, U0, U, alpha, beta}, {2, V0, V, alpha, beta}};
+    const Solve uv[2] = {cv.solve(1, U0, U), cv.solve(2, V0, V)};
     TRY(op_diffuse_batch(c, uv, 2, iters));
     TRY(xchg_join(c));
     TRY(project(c, U0, V0, /*p=*/U, /*div=*/V, iters, nullptr, /*with_max=*/true));
-    const float dt0 = dt * (float)c->n;
+    const float dt0 = dt.at(0) * (float)c->n;      // (slabs only: one member)
     TRY(vmax_begin(c, U0, V0, /*have_max=*/true));
     TRY(advect_bounded(c, 0, {U0, V0}, dt0, [&] { return op_advect2(c, 1, U, U0, 2, V, V0, U0, V0, dt); }));
     return project(c, U, V, /*p=*/U0, /*div=*/V0, iters);
 }
 
 // FluidSequential.c:176-186
-int dens_step(fluid_ctx* c, float dt, float diff, int iters)
+int dens_step(fluid_ctx* c, MVal dt, MVal diff, int iters)
 {
     const int X = FLUID_DENS, X0 = FLUID_DENS_PREV;
-    float alpha, beta;
     TRY(op_add_source(c, X, X0, dt, /*defer=*/true));
-    coefficients(c->n, dt, diff, &alpha, &beta);
-    TRY(op_diffuse(c, 0, X0, X, alpha, beta, iters));
+    const Coef cd(c, dt, diff);
+    const Solve one = cd.solve(0, X0, X);
+    TRY(op_diffuse_batch(c, &one, 1, iters));
     TRY(vmax_begin(c, FLUID_U, FLUID_V));
-    return advect_bounded(c, 1, {X0}, dt * (float)c->n, [&] { return op_advect(c, 0, X, X0, FLUID_U, FLUID_V, dt); });
+    return advect_bounded(c, 1, {X0}, dt.at(0) * (float)c->n, [&] { return op_advect(c, 0, X, X0, FLUID_U, FLUID_V, dt); });
 }
 
 // One loop body of the reference's main (FluidSequential.c:305-306).  The density's
@@ -1309,7 +1522,7 @@ int dens_step(fluid_ctx* c, float dt, float diff, int iters)
 // diffusions are independent of one another and of everything in between, so they
 // run as ONE batch (one exchange on slabs, three times the waves per launch); the
 // arithmetic per cell and the final contents of all six fields are unchanged.
-int full_step(fluid_ctx* c, float dt, float diff, float visc, int iters)
+int full_step(fluid_ctx* c, MVal dt, MVal diff, MVal visc, int iters)
 {
     const int U = FLUID_U, V = FLUID_V, D = FLUID_DENS, U0 = FLUID_U_PREV, V0 = FLUID_V_PREV, D0 = FLUID_DENS_PREV;
     TRY(op_add_source(c, U, U0, dt, /*defer=*/true));
@@ -1318,11 +1531,9 @@ int full_step(fluid_ctx* c, float dt, float diff, float visc, int iters)
     // right-hand sides and first guesses together (zeroed sources are valid everywhere and skipped); async: the first launch
     // of the diffusion runs its interior strips while the rows travel (op_diffuse_batch)
     TRY(need(c, {U, V, D, U0, V0, D0}, std::min(iters, c->halo), /*async=*/true));
-    float av, bv, ad, bd;
-    coefficients(c->n, dt, visc, &av, &bv);
-    coefficients(c->n, dt, diff, &ad, &bd);
-    const float dt0 = dt * (float)c->n;
-    const Solve all[3] = {{1, U0, U, av, bv}, {2, V0, V, av, bv}, {0, D0, D, ad, bd}};
+    const Coef cv(c, dt, visc), cd(c, dt, diff);
+    const float dt0 = dt.at(0) * (float)c->n;      // (slabs only: one member)
+    const Solve all[3] = {cv.solve(1, U0, U), cv.solve(2, V0, V), cd.solve(0, D0, D)};
     if (c->nranks == 1) {
         TRY(op_diffuse_batch(c, all, 3, iters));
         TRY(project(c, U0, V0, /*p=*/U, /*div=*/V, iters));
@@ -1640,6 +1851,10 @@ int fluid_destroy(fluid_ctx* c)
     c->rccl = nullptr;
     if (c->h_scalar) (void)hipHostFree(c->h_scalar);
     if (c->tiles) (void)hipFree(c->tiles);
+    for (auto& b : c->consts.live) (void)hipEventDestroy(b.copied);
+    for (hipEvent_t ev : c->consts.free_events) (void)hipEventDestroy(ev);
+    if (c->consts.dev) (void)hipFree(c->consts.dev);
+    if (c->consts.host) (void)hipHostFree(c->consts.host);
     if (c->d_partials) (void)hipFree(c->d_partials);
     if (c->scalar_ready) (void)hipEventDestroy(c->scalar_ready);
     if (c->own_arena && c->arena) (void)hipFree(c->arena);
@@ -1978,6 +2193,117 @@ int fluid_step(fluid_ctx* c, float dt, float diff, float visc, int iters, int ns
         if (!(use_sources && z == 0)) TRY(zero_sources(c));
         TRY(full_step(c, dt, diff, visc, iters));
     }
+    HIP_TRY(hipGetLastError());
+    return FLUID_OK;
+}
+
+// ---- one value per member (ensembles) -------------------------------------------
+// Null arrays, a null context and non-finite entries are found here, before anything else happens: nothing is launched and
+// neither a field nor what the library still owes one changes.  On a context with one member (row slabs included) the
+// callers below hand element 0 to the scalar entry point.
+struct MemberArg {
+    const char* name;
+    const float* v;
+};
+
+static int check_member_args(const fluid_ctx* c, const char* call, std::initializer_list<MemberArg> args)
+{
+    for (const MemberArg& a : args)
+        if (!a.v) return fail(FLUID_E_INVALID, "%s: null array `%s`", call, a.name);
+    if (!c) return fail(FLUID_E_INVALID, "%s: null context", call);
+    for (const MemberArg& a : args)
+        for (int m = 0; m < c->members; ++m)
+            if (!std::isfinite(a.v[m])) return fail(FLUID_E_INVALID, "%s: member %d: %s is not finite (%g)", call, m, a.name, (double)a.v[m]);
+    return FLUID_OK;
+}
+
+int fluid_step_members(fluid_ctx* c, const float* dt, const float* diff, const float* visc, int iters, int nsteps, int use_sources)
+{
+    TRY(check_member_args(c, "fluid_step_members", {{"dt", dt}, {"diff", diff}, {"visc", visc}}));
+    if (c->members == 1) return fluid_step(c, dt[0], diff[0], visc[0], iters, nsteps, use_sources);
+    if (iters < 0 || (iters & 1)) return fail(FLUID_E_INVALID, "sweep count must be even and >= 0 (got %d)", iters);
+    if (nsteps < 0) return fail(FLUID_E_INVALID, "nsteps < 0");
+    TRY(ensure_consts(c));
+    for (int z = 0; z < nsteps; ++z) {
+        if (!(use_sources && z == 0)) TRY(zero_sources(c));
+        TRY(full_step(c, MVal(dt[0], dt), MVal(diff[0], diff), MVal(visc[0], visc), iters));
+    }
+    HIP_TRY(hipGetLastError());
+    return FLUID_OK;
+}
+
+int fluid_vel_step_members(fluid_ctx* c, const float* dt, const float* visc, int iters)
+{
+    TRY(check_member_args(c, "fluid_vel_step_members", {{"dt", dt}, {"visc", visc}}));
+    if (c->members == 1) return fluid_vel_step(c, dt[0], visc[0], iters);
+    if (iters < 0 || (iters & 1)) return fail(FLUID_E_INVALID, "sweep count must be even and >= 0 (got %d)", iters);
+    TRY(ensure_consts(c));
+    TRY(vel_step(c, MVal(dt[0], dt), MVal(visc[0], visc), iters));
+    HIP_TRY(hipGetLastError());
+    return FLUID_OK;
+}
+
+int fluid_dens_step_members(fluid_ctx* c, const float* dt, const float* diff, int iters)
+{
+    TRY(check_member_args(c, "fluid_dens_step_members", {{"dt", dt}, {"diff", diff}}));
+    if (c->members == 1) return fluid_dens_step(c, dt[0], diff[0], iters);
+    if (iters < 0 || (iters & 1)) return fail(FLUID_E_INVALID, "sweep count must be even and >= 0 (got %d)", iters);
+    TRY(ensure_consts(c));
+    TRY(dens_step(c, MVal(dt[0], dt), MVal(diff[0], diff), iters));
+    HIP_TRY(hipGetLastError());
+    return FLUID_OK;
+}
+
+int fluid_op_add_source_members(fluid_ctx* c, int x, int s, const float* dt)
+{
+    TRY(check_member_args(c, "fluid_op_add_source_members", {{"dt", dt}}));
+    if (c->members == 1) return fluid_op_add_source(c, x, s, dt[0]);
+    TRY(check_fields(c, {x, s}));
+    if (x == s) return fail(FLUID_E_INVALID, "add_source: x and s must differ");
+    TRY(ensure_consts(c));
+    TRY(op_add_source(c, x, s, MVal(dt[0], dt)));
+    HIP_TRY(hipGetLastError());
+    return FLUID_OK;
+}
+
+int fluid_op_jacobi_sweep_members(fluid_ctx* c, int b, int x, int x0, int out, const float* alpha, const float* beta)
+{
+    TRY(check_member_args(c, "fluid_op_jacobi_sweep_members", {{"alpha", alpha}, {"beta", beta}}));
+    if (c->members == 1) return fluid_op_jacobi_sweep(c, b, x, x0, out, alpha[0], beta[0]);
+    TRY(check_fields(c, {x, x0, out}));
+    if (b < 0 || b > 2) return fail(FLUID_E_INVALID, "b must be 0, 1 or 2");
+    if (out == x || out == x0) return fail(FLUID_E_INVALID, "jacobi_sweep: out must not alias an input");
+    TRY(ensure_consts(c));
+    TRY(materialize(c, {x, x0}));
+    const float2* mab = nullptr;
+    TRY(member_pairs(c, alpha, beta, &mab));
+    const int v1 = c->variant == fluid::JACOBI_TB ? fluid::JACOBI_STREAM : c->variant;   // one sweep: nothing to block
+    fluid::launch_jacobi(c->stream, c->st, v1, c->ptr(x), c->ptr(x0), c->ptr(out), c->pitch, c->n, c->own0, c->own1, alpha[0], beta[0], b,
+                         c->mb(), mab);
+    wrote(c, out, 0);
+    HIP_TRY(hipGetLastError());
+    return FLUID_OK;
+}
+
+int fluid_op_diffuse_members(fluid_ctx* c, int b, int x, int x0, const float* alpha, const float* beta, int iters)
+{
+    TRY(check_member_args(c, "fluid_op_diffuse_members", {{"alpha", alpha}, {"beta", beta}}));
+    if (c->members == 1) return fluid_op_diffuse(c, b, x, x0, alpha[0], beta[0], iters);
+    TRY(check_fields(c, {x, x0}));
+    if (b < 0 || b > 2) return fail(FLUID_E_INVALID, "b must be 0, 1 or 2");
+    TRY(ensure_consts(c));
+    return op_diffuse(c, b, x, x0, MVal(alpha[0], alpha), MVal(beta[0], beta), iters);
+}
+
+int fluid_op_advect_members(fluid_ctx* c, int b, int d, int d0, int u, int v, const float* dt)
+{
+    TRY(check_member_args(c, "fluid_op_advect_members", {{"dt", dt}}));
+    if (c->members == 1) return fluid_op_advect(c, b, d, d0, u, v, dt[0]);
+    TRY(check_fields(c, {d, d0, u, v}));
+    if (b < 0 || b > 2) return fail(FLUID_E_INVALID, "b must be 0, 1 or 2");
+    if (d == d0 || d == u || d == v) return fail(FLUID_E_INVALID, "advect: output must not alias an input");
+    TRY(ensure_consts(c));
+    TRY(op_advect(c, b, d, d0, u, v, MVal(dt[0], dt)));    // (an ensemble is one GPU: no bound to agree on)
     HIP_TRY(hipGetLastError());
     return FLUID_OK;
 }

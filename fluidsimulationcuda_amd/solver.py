@@ -31,12 +31,37 @@ def _host(a, n):
     return a
 
 
+def member_values(members, **params):
+    """Scalars or one value per ensemble member, for the physical parameters of a call (dt, diff, visc, alpha, beta).
+
+    All scalars: returns None -- the caller uses the scalar entry point, as ever.  Otherwise every parameter is
+    broadcast to a C-contiguous float32 array of length `members` (a dict in the order given), for the `_members`
+    entry point.  A sequence of any other length raises ValueError; nothing here touches the library."""
+    if all(np.ndim(v) == 0 for v in params.values()):
+        return None
+    out = {}
+    for name, v in params.items():
+        a = np.asarray(v, dtype=np.float32)
+        if a.ndim == 0:
+            a = np.full(members, a, dtype=np.float32)
+        elif a.ndim != 1 or a.shape[0] != members:
+            raise ValueError("%s: expected a scalar or %d values (one per member), got shape %s" % (name, members, a.shape))
+        out[name] = np.ascontiguousarray(a, dtype=np.float32)
+    return out
+
+
+def _mf(a):
+    return a.ctypes.data_as(capi._MF)
+
+
 class FluidSolver:
     """Six resident fields + scratch on one GPU (or one row slab of several).
 
     `members=M` makes it an ensemble: M independent simulations of the same size that go through every call together, in
     the same kernel launches.  Member m's fields are moved with upload(member=m, ...) / download(field, member=m), or all
-    at once as (M, N+2, N+2) arrays with upload_members / download_members."""
+    at once as (M, N+2, N+2) arrays with upload_members / download_members.  dt, diff, visc (alpha, beta) of step,
+    vel_step, dens_step, add_source, diffuse, jacobi_sweep and advect take a scalar for everybody or a sequence with
+    one value per member (a parameter study): same launches either way."""
 
     def __init__(self, n, rank=0, nranks=1, halo=0, jacobi=capi.JACOBI_TB, stream=None,
                  arena_ptr=None, arena_bytes=0, params=None, storage=capi.STORAGE_F32, members=1):
@@ -146,16 +171,33 @@ class FluidSolver:
         capi.check(capi.lib().fluid_op_set_bnd(self._h, b, _fid(x)))
 
     def add_source(self, x, s, dt=DT):
-        capi.check(capi.lib().fluid_op_add_source(self._h, _fid(x), _fid(s), dt))
+        mv = member_values(self.members, dt=dt)
+        if mv is None:
+            capi.check(capi.lib().fluid_op_add_source(self._h, _fid(x), _fid(s), dt))
+        else:
+            capi.check(capi.lib().fluid_op_add_source_members(self._h, _fid(x), _fid(s), _mf(mv["dt"])))
 
     def jacobi_sweep(self, b, x, x0, out, alpha, beta):
-        capi.check(capi.lib().fluid_op_jacobi_sweep(self._h, b, _fid(x), _fid(x0), _fid(out), alpha, beta))
+        mv = member_values(self.members, alpha=alpha, beta=beta)
+        if mv is None:
+            capi.check(capi.lib().fluid_op_jacobi_sweep(self._h, b, _fid(x), _fid(x0), _fid(out), alpha, beta))
+        else:
+            capi.check(capi.lib().fluid_op_jacobi_sweep_members(self._h, b, _fid(x), _fid(x0), _fid(out), _mf(mv["alpha"]),
+                                                                _mf(mv["beta"])))
 
     def diffuse(self, b, x, x0, alpha, beta, iters=ITERS):
-        capi.check(capi.lib().fluid_op_diffuse(self._h, b, _fid(x), _fid(x0), alpha, beta, iters))
+        mv = member_values(self.members, alpha=alpha, beta=beta)
+        if mv is None:
+            capi.check(capi.lib().fluid_op_diffuse(self._h, b, _fid(x), _fid(x0), alpha, beta, iters))
+        else:
+            capi.check(capi.lib().fluid_op_diffuse_members(self._h, b, _fid(x), _fid(x0), _mf(mv["alpha"]), _mf(mv["beta"]), iters))
 
     def advect(self, b, d, d0, u, v, dt=DT):
-        capi.check(capi.lib().fluid_op_advect(self._h, b, _fid(d), _fid(d0), _fid(u), _fid(v), dt))
+        mv = member_values(self.members, dt=dt)
+        if mv is None:
+            capi.check(capi.lib().fluid_op_advect(self._h, b, _fid(d), _fid(d0), _fid(u), _fid(v), dt))
+        else:
+            capi.check(capi.lib().fluid_op_advect_members(self._h, b, _fid(d), _fid(d0), _fid(u), _fid(v), _mf(mv["dt"])))
 
     def computeDivergenceAndPressure(self, u, v, p, div):
         capi.check(capi.lib().fluid_op_divergence(self._h, _fid(u), _fid(v), _fid(p), _fid(div)))
@@ -165,15 +207,28 @@ class FluidSolver:
 
     def vel_step(self, visc=VIS, dt=DT, iters=ITERS):
         """vel_step(u, v, u_prev, v_prev, visc) on the resident fields."""
-        capi.check(capi.lib().fluid_vel_step(self._h, dt, visc, iters))
+        mv = member_values(self.members, dt=dt, visc=visc)
+        if mv is None:
+            capi.check(capi.lib().fluid_vel_step(self._h, dt, visc, iters))
+        else:
+            capi.check(capi.lib().fluid_vel_step_members(self._h, _mf(mv["dt"]), _mf(mv["visc"]), iters))
 
     def dens_step(self, diff=DIFF, dt=DT, iters=ITERS):
         """dens_step(dens, dens_prev, u, v, diff) on the resident fields."""
-        capi.check(capi.lib().fluid_dens_step(self._h, dt, diff, iters))
+        mv = member_values(self.members, dt=dt, diff=diff)
+        if mv is None:
+            capi.check(capi.lib().fluid_dens_step(self._h, dt, diff, iters))
+        else:
+            capi.check(capi.lib().fluid_dens_step_members(self._h, _mf(mv["dt"]), _mf(mv["diff"]), iters))
 
     def step(self, nsteps=1, use_sources=False, dt=DT, diff=DIFF, visc=VIS, iters=ITERS):
         """nsteps bodies of the reference's main loop (FluidSequential.c:289-312)."""
-        capi.check(capi.lib().fluid_step(self._h, dt, diff, visc, iters, nsteps, 1 if use_sources else 0))
+        mv = member_values(self.members, dt=dt, diff=diff, visc=visc)
+        if mv is None:
+            capi.check(capi.lib().fluid_step(self._h, dt, diff, visc, iters, nsteps, 1 if use_sources else 0))
+        else:
+            capi.check(capi.lib().fluid_step_members(self._h, _mf(mv["dt"]), _mf(mv["diff"]), _mf(mv["visc"]), iters, nsteps,
+                                                     1 if use_sources else 0))
 
     # -- diagnostics / tuning
     def residual(self, x, x0, alpha, beta):

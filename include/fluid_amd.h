@@ -173,8 +173,9 @@ int fluid_destroy(fluid_ctx *ctx);
 int fluid_synchronize(fluid_ctx *ctx);
 
 /* ---- ensembles: M independent simulations of the same size in one context ---------------------------------
- * Every member has its own twelve fields; all members share N, the storage type, every fluid_set_param knob and the
- * scalar arguments of each call.  One call to fluid_step / fluid_vel_step / fluid_dens_step / fluid_op_* / fluid_fill
+ * Every member has its own twelve fields; all members share N, the storage type and every fluid_set_param knob, and --
+ * through the classic calls -- the scalar arguments of each call (the _members calls below give each member its own dt,
+ * diff and visc).  One call to fluid_step / fluid_vel_step / fluid_dens_step / fluid_op_* / fluid_fill
  * does to every member what it does to a one-member context, in the SAME kernel launches (the member index rides in the
  * launch grid), and member m ends up with exactly the bits a one-member context given m's arrays would hold.
  * `members` in [1, 21845]; cfg->nranks must be 1 when members > 1; cfg->arena, if given, holds
@@ -194,6 +195,31 @@ int fluid_members(fluid_ctx *ctx, int *members);
  * library still owes the field (zeros by definition, a deferred add_source) in ALL members, then replaces this one. */
 int fluid_upload_member(fluid_ctx *ctx, int member, int field, const float *host);
 int fluid_download_member(fluid_ctx *ctx, int member, int field, float *host);
+/* One value PER MEMBER where the calls further down take a scalar (a parameter study in one ensemble): every array is host
+ * memory with fluid_members(ctx) entries that the library has finished with when the call returns.  Member m ends up with
+ * exactly the bits a one-member context would hold after the same calls with dt[m], diff[m], visc[m] (alpha[m], beta[m]) as
+ * its scalars, and a call issues the SAME launches as its scalar twin: the constants travel in a table in device memory
+ * (library-owned, outside the arena, allocated at the first such call) that each wave indexes by its member.  Tables are
+ * copied on the context's stream from a ring of pinned slots, and one whose contents are already in the ring is not copied
+ * again: calls may follow one another with different values without a wait, a loop with the same values uploads nothing.
+ * alpha / beta are formed per member by the same arithmetic as fluid_coefficients.  A solve whose members' betas call for
+ * different division modes (FLUID_PARAM_TB_FAST_DIVISION) runs in the most general mode proven for all of them -- exact
+ * like every mode, only slower.  Each DISTINCT beta is proven on the device once per process (about 2.7 ms and one stream
+ * synchronise each): the first step of M distinct viscosities and M distinct diffusivities pays about 2 M proofs.
+ * A null context or array, or an entry that is not finite: FLUID_E_INVALID (the message names the call and the member),
+ * nothing launched, nothing changed.  Every finite value is accepted (dt <= 0, coefficients 0, betas <= 0 included).
+ * With one member (row slabs included) a _members call is the scalar call with element 0.  fluid_residual keeps scalar
+ * coefficients; fluid_op_diffuse_tol and the exchange calls stay unavailable on ensembles. */
+int fluid_step_members(fluid_ctx *ctx, const float *dt, const float *diff, const float *visc, int iters,
+                       int nsteps, int use_sources);
+int fluid_vel_step_members(fluid_ctx *ctx, const float *dt, const float *visc, int iters);
+int fluid_dens_step_members(fluid_ctx *ctx, const float *dt, const float *diff, int iters);
+int fluid_op_add_source_members(fluid_ctx *ctx, int x, int s, const float *dt);
+int fluid_op_jacobi_sweep_members(fluid_ctx *ctx, int b, int x, int x0, int out,
+                                  const float *alpha, const float *beta);
+int fluid_op_diffuse_members(fluid_ctx *ctx, int b, int x, int x0, const float *alpha, const float *beta,
+                             int iters);
+int fluid_op_advect_members(fluid_ctx *ctx, int b, int d, int d0, int u, int v, const float *dt);
 
 /* Interior rows [*row_lo, *row_hi) owned by this context's slab (1..N+1 for one GPU). */
 int fluid_owned_rows(fluid_ctx *ctx, int *row_lo, int *row_hi);

@@ -9,9 +9,15 @@ wall time between fluid_synchronize pairs, the median of --blocks blocks.  "deca
 pair.  "sourced": every step sits between its own pair, with the uploads outside it (a block is the sum of --steps such
 steps), so it carries one host round trip per step that "decay" does not.  One process, one context at a time.
 
+--member-params picks the kind of call: "scalar" (default) -- fluid_step with one dt, diff, visc for everybody; "constant" --
+fluid_step_members with arrays that hold those same values; "ladder" -- fluid_step_members with member m's own visc and
+diff, a geometric ladder around the defaults from x 1/2 to x 2 (dt shared; the ladder is written into the JSON).  The
+division proofs of the ladder's betas (one per distinct beta and process) run in the untimed steps.
+
 Prints a table and writes JSON (--out): ms per ensemble step, ms per member-step, member-steps per second, the gain over
 M one-member steps (the M = 1 row of the same run), and the strip heights the tuner kept for each launch shape.
-    python tools/ensemble_timing.py [--sizes 64,256] [--members 1,16] [--out profiles/ensemble_timing.json] [--commit ID]"""
+    python tools/ensemble_timing.py [--sizes 64,256] [--members 1,16] [--member-params ladder]
+                                    [--out profiles/ensemble_timing.json] [--commit ID]"""
 import argparse
 import json
 import os
@@ -53,9 +59,27 @@ class TunerLog:
             sys.stderr.write(rest + "\n")
 
 
+def ladder(members):
+    """x 2^-1 ... x 2^+1 in equal ratios (one member: x 1)"""
+    if members == 1:
+        return np.ones(1)
+    return 2.0 ** (2.0 * np.arange(members) / (members - 1) - 1.0)
+
+
+def member_params(members, kind):
+    """keyword arguments of FluidSolver.step for this kind of call, and what goes into the JSON"""
+    if kind == "scalar":
+        return {}, None
+    factor = ladder(members) if kind == "ladder" else np.ones(members)
+    kw = {"dt": np.full(members, F.solver.DT, np.float32), "diff": (F.solver.DIFF * factor).astype(np.float32),
+          "visc": (F.solver.VIS * factor).astype(np.float32)}
+    return kw, {k: [float(x) for x in v] for k, v in kw.items()}
+
+
 def run(n, members, workload, args):
     fields = [initialize_parameters(n, seed=1 + m) for m in range(members)]
     sourced = workload == "sourced"
+    kw, recorded = member_params(members, args.member_params)
 
     def inject(s):
         for m, f in enumerate(fields):
@@ -64,12 +88,12 @@ def run(n, members, workload, args):
     with TunerLog() as log, F.FluidSolver(n, members=members) as s:
         for m, f in enumerate(fields):
             s.upload(member=m, **f)
-        s.step(1, use_sources=True)
+        s.step(1, use_sources=True, **kw)
         tune_steps = 0
         while tune_steps < args.max_tune and (tune_steps < 2 or s.autotune_pending() > 0):
             if sourced:
                 inject(s)
-            s.step(1, use_sources=sourced)
+            s.step(1, use_sources=sourced, **kw)
             tune_steps += 1
         s.synchronize()
         pending = s.autotune_pending()
@@ -81,19 +105,20 @@ def run(n, members, workload, args):
                     inject(s)
                     s.synchronize()
                     t0 = time.perf_counter()
-                    s.step(1, use_sources=True)
+                    s.step(1, use_sources=True, **kw)
                     s.synchronize()
                     t += time.perf_counter() - t0
             else:
                 s.synchronize()
                 t0 = time.perf_counter()
-                s.step(args.steps)
+                s.step(args.steps, **kw)
                 s.synchronize()
                 t = time.perf_counter() - t0
             blocks.append(t / args.steps * 1e3)
         absmax = s.absmax_velocity()
     ms = float(np.median(blocks))
-    return {"n": n, "grid": n + 2, "members": members, "workload": workload, "ms_per_ensemble_step": ms,
+    return {"n": n, "grid": n + 2, "members": members, "workload": workload, "member_params": args.member_params,
+            "member_values": recorded, "ms_per_ensemble_step": ms,
             "ms_per_member_step": ms / members, "member_steps_per_s": members / (ms * 1e-3), "blocks_ms": blocks,
             "tune_steps": tune_steps, "shapes_still_open": pending, "absmax_velocity_after": absmax, "strip_heights": log.kept}
 
@@ -108,6 +133,8 @@ def main():
     ap.add_argument("--max-tune", type=int, default=80)
     ap.add_argument("--max-gib", type=float, default=24.0, help="largest arena (12 fields x members) that still counts as comfortable")
     ap.add_argument("--max-upload-gib", type=float, default=1.0, help="'sourced' uploads 3 fields x members per step: skipped beyond this")
+    ap.add_argument("--member-params", default="scalar", choices=["scalar", "constant", "ladder"],
+                    help="scalar: fluid_step; constant / ladder: fluid_step_members with the defaults / a x1/2..x2 ladder of visc and diff")
     ap.add_argument("--out", default="")
     ap.add_argument("--commit", default="")
     args = ap.parse_args()
@@ -137,7 +164,7 @@ def main():
                       "tuned in %2d steps (%d open), strip heights kept: %s"
                       % (n, members, workload, r["ms_per_ensemble_step"], r["ms_per_member_step"], r["member_steps_per_s"],
                          r.get("gain_over_one_member_steps", float("nan")), r["tune_steps"], r["shapes_still_open"], heights), flush=True)
-    out = {"tool": "tools/ensemble_timing.py", "commit": args.commit, "steps_per_block": args.steps, "blocks": args.blocks,
+    out = {"tool": "tools/ensemble_timing.py", "commit": args.commit, "member_params": args.member_params, "steps_per_block": args.steps, "blocks": args.blocks,
            "dt": F.solver.DT, "diff": F.solver.DIFF, "visc": F.solver.VIS, "iters": F.solver.ITERS, "rows": rows, "skipped": skipped}
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
