@@ -105,6 +105,11 @@ SIGNATURES = {
     "fluid_op_subtract_gradient": [_ctx, _i, _i, _i],
     "fluid_residual": [_ctx, _i, _i, _f, _f, C.POINTER(_f)],
     "fluid_absmax_velocity": [_ctx, _i, _i, C.POINTER(_f)],
+    "fluid_residual_members": [_ctx, _i, _i, _MF, _MF, _MF],
+    "fluid_absmax_velocity_members": [_ctx, _i, _i, _MF],
+    "fluid_member_moments": [_ctx, _i, C.POINTER(C.c_double), C.POINTER(C.c_double)],
+    "fluid_ensemble_stats": [_ctx, _i, _MF, _MF],
+    "fluid_ensemble_stats_ptr": [_ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)],
     "fluid_set_jacobi_variant": [_ctx, _i],
     "fluid_division_mode": [_ctx, _f, _f, C.POINTER(_i)],
     "fluid_autotune_pending": [_ctx, C.POINTER(_i)],

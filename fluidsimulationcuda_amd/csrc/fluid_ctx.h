@@ -68,6 +68,18 @@ struct ConstRing {
     long long uploads = 0;
 };
 
+// What the ensemble diagnostics (fluid_*_members maxima, fluid_member_moments, fluid_ensemble_stats) need beyond the
+// fields: library-owned, outside the arena, each part allocated at the first call that needs it (fluid_solver.hip:
+// ensure_member_results, ensure_stats) and freed in fluid_destroy.
+struct EnsembleReduce {
+    unsigned int* d_max = nullptr;        // one result word per member (k_residual / k_absmax2 with a result stride of 1)
+    double2* d_moments = nullptr;         // one {sum, sum of squares} per member
+    double2* d_partials = nullptr;        // members x moment_blocks() per-block pairs
+    char* host = nullptr;                 // pinned twin of the larger of the two result arrays
+    float *d_mean = nullptr, *d_var = nullptr;   // the two statistics fields, field_floats floats each, pads zero
+    bool have_stats = false;              // a fluid_ensemble_stats has filled them
+};
+
 struct fluid_ctx {
     int n = 0, w = 0, pitch = 0;
     size_t field_floats = 0;
@@ -99,6 +111,7 @@ struct fluid_ctx {
     unsigned int* d_scalar = nullptr;     // device word for the reductions
     float* d_partials = nullptr;          // slabs: per-block maxima of the gradient subtraction (launch_subtract_gradient)
     ConstRing consts;                     // tables of per-member constants (fluid_*_members)
+    EnsembleReduce red;                   // results and scratch of the ensemble diagnostics
     unsigned int* tiles = nullptr;        // 3 x members x tile_rows x tile_pitch words: |x0| minima per tile for division mode 3
     unsigned int* h_scalar = nullptr;     // pinned host mirror
     hipEvent_t scalar_ready = nullptr;    // recorded behind the scalar's device-to-host copy

@@ -141,10 +141,20 @@ void launch_subtract_gradient(hipStream_t s, int st, void* u, void* v, const voi
 void launch_gradient_advect(hipStream_t s, int st, void* u, void* v, const void* p, void* d, const void* d0, int pitch, int n,
                             int row_lo, int row_hi, float h, float dt0, int b, float pinv = 1.0f, Members mb = {},
                             const float* mdt0 = nullptr);
-// (absmax2, residual: the maximum over all members -- every block ends in an atomicMax on the one word)
+// absmax2, residual: every block ends in an atomicMax on its member's result word, result[member * rstride] -- rstride 0:
+// the maximum over all members in the one word; 1: one word per member.  The caller zeroes the word(s) first.
 void launch_absmax2(hipStream_t s, int st, const void* u, const void* v, int pitch, int n, int row_lo, int row_hi,
-                    unsigned int* result, Members mb = {});
+                    unsigned int* result, Members mb = {}, int rstride = 0);
 void launch_residual(hipStream_t s, int st, const void* x, const void* x0, int pitch, int n, int row_lo, int row_hi,
-                     float alpha, float beta, unsigned int* result, Members mb = {});
+                     float alpha, float beta, unsigned int* result, Members mb = {}, int rstride = 0, const float2* mab = nullptr);
+// Per member, the sum of x and of x * x over the interior cells, in double: out[member] = {sum, sum of squares}.  Two
+// launches whatever the member count: moment_blocks(n, members) blocks per member each leave their pair in `partials`
+// (members * moment_blocks(n, members) pairs of scratch), a second kernel adds each member's in a fixed order.
+constexpr int kMomentBlocks = 4096;      // blocks of the whole launch: a few rounds of 256 CUs x 8 resident blocks
+int moment_blocks(int n, int members);
+void launch_member_moments(hipStream_t s, int st, const void* x, int pitch, int n, Members mb, double2* partials, double2* out);
+// Per cell over the members (every row and column, ghosts included): mean and population variance as float fields in
+// the layout of a field; their pad columns are not written.  One launch; the members are walked inside the kernel.
+void launch_ensemble_stats(hipStream_t s, int st, const void* x, int pitch, int n, Members mb, float* mean, float* var);
 
 }  // namespace fluid

@@ -1626,11 +1626,14 @@ __device__ __forceinline__ void block_max_to(unsigned int* __restrict__ result, 
 }
 
 // one workgroup per group of rows, whole float4 vectors (columns beyond 1..n masked out)
+// rstride (here and in k_residual): words between two members' results -- 0: every member into the one word (the maximum
+// over the ensemble), 1: member m into word m
 template <typename S>
 __global__ __launch_bounds__(256) void k_absmax2(const S* __restrict__ u, const S* __restrict__ v, int pitch, int n,
-                                                 int row_lo, int row_hi, unsigned int* __restrict__ result, size_t ms)
+                                                 int row_lo, int row_hi, unsigned int* __restrict__ result, size_t ms, int rstride)
 {
     u += blockIdx.y * ms; v += blockIdx.y * ms;
+    result += blockIdx.y * (unsigned)rstride;
     const size_t P = (size_t)pitch;
     const int nvec = (n + 3) >> 2;
     float m = 0.0f;
@@ -1651,18 +1654,188 @@ __global__ __launch_bounds__(256) void k_absmax2(const S* __restrict__ u, const 
 template <typename S>
 __global__ __launch_bounds__(256) void k_residual(const S* __restrict__ x, const S* __restrict__ x0, int pitch, int n,
                                                   int row_lo, int row_hi, float alpha, float beta,
-                                                  unsigned int* __restrict__ result, size_t ms)
+                                                  unsigned int* __restrict__ result, size_t ms, int rstride,
+                                                  const float2* __restrict__ mab)
 {
+    if (mab) { alpha = mab[blockIdx.y].x; beta = mab[blockIdx.y].y; }      // this member's own coefficients (wave-uniform)
     x += blockIdx.y * ms; x0 += blockIdx.y * ms;
+    result += blockIdx.y * (unsigned)rstride;
     const size_t P = (size_t)pitch;
     float m = 0.0f;
     for (int i = row_lo + blockIdx.x; i < row_hi; i += gridDim.x)
+        // (kept rolled, as hipcc had it before the coefficient table existed: with the table's load ahead of the loop it unrolls
+        // it for fp32 storage to 193 registers and 2 waves per SIMD, where the kernel used to have 33 and 8)
+#pragma unroll 1
         for (int j = 1 + threadIdx.x; j <= n; j += 256) {
             const size_t c = (size_t)i * P + XOFF + j;
             const float nb = ld1(x + c - 1) + ld1(x + c + 1) + ld1(x + c - P) + ld1(x + c + P);
             m = fmaxf(m, fabsf(beta * ld1(x + c) - alpha * nb - ld1(x0 + c)));
         }
     block_max_to(result, m);
+}
+
+// ---------------------------------------------------------------------------
+// ensemble reductions (diagnostics; include/fluid_amd.h "ensemble diagnostics").  Nothing here feeds back into a field.
+// ---------------------------------------------------------------------------
+// Per member, over the interior cells: the sum of x and of x*x in double (a stored value widens exactly, and the square
+// of a float or half is exact in double).  Grid (blocks, members); a block strides over the rows as k_absmax2 does, whole
+// 4-element vectors with the columns beyond n masked.  Two accumulators per lane, a 64-lane butterfly on doubles, the
+// four waves combined through LDS, and ONE plain store of the block's pair into partials[member * gridDim.x + block]:
+// no floating-point atomics, so the order of every addition is fixed by (n, members, grid) alone and the result is the
+// same bits run after run.  k_fold_moments adds a member's partials.
+__device__ __forceinline__ double wave_sum(double s)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s = s + __shfl_xor(s, off, 64);
+    return s;
+}
+
+template <typename S>
+__global__ __launch_bounds__(256) void k_member_moments(const S* __restrict__ x, int pitch, int n, size_t ms,
+                                                        double2* __restrict__ partials)
+{
+    x += blockIdx.y * ms;
+    const size_t P = (size_t)pitch;
+    const int nvec = (n + 3) >> 2;
+    double s = 0.0, q = 0.0;
+    for (int i = 1 + blockIdx.x; i <= n; i += gridDim.x)
+        for (int k = threadIdx.x; k < nvec; k += 256) {
+            const float4 a = ld4(x + (size_t)i * P + XOFF + 1 + 4 * (size_t)k);
+            const int last = n - (1 + 4 * k);            // components 0..last are columns <= n
+            const double d0 = (double)a.x, d1 = (double)a.y, d2 = (double)a.z, d3 = (double)a.w;
+            s = s + d0; q = q + d0 * d0;
+            if (last >= 1) { s = s + d1; q = q + d1 * d1; }
+            if (last >= 2) { s = s + d2; q = q + d2 * d2; }
+            if (last >= 3) { s = s + d3; q = q + d3 * d3; }
+        }
+    __shared__ double part[4][2];
+    s = wave_sum(s);
+    q = wave_sum(q);
+    if ((threadIdx.x & 63) == 0) { part[threadIdx.x >> 6][0] = s; part[threadIdx.x >> 6][1] = q; }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        partials[(size_t)blockIdx.y * gridDim.x + blockIdx.x] =
+            make_double2(((part[0][0] + part[1][0]) + part[2][0]) + part[3][0], ((part[0][1] + part[1][1]) + part[2][1]) + part[3][1]);
+}
+
+// one wave per member: lane l adds partials l, l + 64, ... in index order, then the butterfly
+__global__ __launch_bounds__(64) void k_fold_moments(const double2* __restrict__ partials, int count, double2* __restrict__ out)
+{
+    const double2* p = partials + (size_t)blockIdx.x * count;
+    double s = 0.0, q = 0.0;
+    for (int k = threadIdx.x; k < count; k += 64) { s = s + p[k].x; q = q + p[k].y; }
+    s = wave_sum(s);
+    q = wave_sum(q);
+    if (threadIdx.x == 0) out[blockIdx.x] = make_double2(s, q);
+}
+
+// Across the members, per cell (ghost cells included): mean and population variance as float fields in the layout of a
+// field, by the two-pass definition of include/fluid_amd.h -- all in double, member order, the first member's value (not
+// 0.0) as the start of both chains.  One lane per VW = 4 (fp16: 8) consecutive columns of a row, vector v of a row covering
+// columns 1 + VW * (v - 1) .. VW * v: vector 0 holds ghost column 0 alone, the last one may end at ghost column n + 1.  A
+// vector that lies within columns 1 .. n + 1 moves as whole 16-byte accesses; the (at most two) others of a row touch
+// their valid columns one by one, so pads are neither read nor written.  The accumulators are dependent chains, the
+// loads are not: kStatsUnroll members' vectors are loaded before they are added.
+constexpr int kStatsUnroll = 4;
+
+template <typename S> struct StatsVec { static constexpr int VW = 16 / (int)sizeof(S); };
+
+template <typename S, bool FULL>
+__device__ __forceinline__ void stats_load(const S* __restrict__ p, int valid, double (&d)[StatsVec<S>::VW])
+{
+    constexpr int VW = StatsVec<S>::VW;
+    if constexpr (FULL) {
+        if constexpr (sizeof(S) == 4) {
+            const float4 a = *reinterpret_cast<const float4*>(p);
+            d[0] = (double)a.x; d[1] = (double)a.y; d[2] = (double)a.z; d[3] = (double)a.w;
+        } else {
+            typedef half_t half8_t __attribute__((ext_vector_type(8)));
+            const half8_t h = *reinterpret_cast<const half8_t*>(p);
+#pragma unroll
+            for (int e = 0; e < VW; ++e) d[e] = (double)(float)h[e];
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < VW; ++e) d[e] = ((valid >> e) & 1) ? (double)(float)p[e] : 0.0;
+    }
+}
+
+template <typename S, bool FULL>
+__device__ __forceinline__ void stats_cell(const S* __restrict__ x, size_t ms, int members, size_t at, int valid,
+                                           float* __restrict__ mean, float* __restrict__ var)
+{
+    constexpr int VW = StatsVec<S>::VW;
+    const double dm = (double)members;
+    double s[VW], q[VW], mu[VW], d[kStatsUnroll][VW];
+    stats_load<S, FULL>(x + at, valid, s);
+    int m = 1;
+    for (; m + kStatsUnroll <= members; m += kStatsUnroll) {
+#pragma unroll
+        for (int r = 0; r < kStatsUnroll; ++r) stats_load<S, FULL>(x + (size_t)(m + r) * ms + at, valid, d[r]);
+#pragma unroll
+        for (int r = 0; r < kStatsUnroll; ++r)
+#pragma unroll
+            for (int e = 0; e < VW; ++e) s[e] = s[e] + d[r][e];
+    }
+    for (; m < members; ++m) {
+        stats_load<S, FULL>(x + (size_t)m * ms + at, valid, d[0]);
+#pragma unroll
+        for (int e = 0; e < VW; ++e) s[e] = s[e] + d[0][e];
+    }
+#pragma unroll
+    for (int e = 0; e < VW; ++e) mu[e] = s[e] / dm;
+    stats_load<S, FULL>(x + at, valid, d[0]);
+#pragma unroll
+    for (int e = 0; e < VW; ++e) { const double t = d[0][e] - mu[e]; q[e] = t * t; }
+    m = 1;
+    for (; m + kStatsUnroll <= members; m += kStatsUnroll) {
+#pragma unroll
+        for (int r = 0; r < kStatsUnroll; ++r) stats_load<S, FULL>(x + (size_t)(m + r) * ms + at, valid, d[r]);
+#pragma unroll
+        for (int r = 0; r < kStatsUnroll; ++r)
+#pragma unroll
+            for (int e = 0; e < VW; ++e) { const double t = d[r][e] - mu[e]; q[e] = q[e] + t * t; }
+    }
+    for (; m < members; ++m) {
+        stats_load<S, FULL>(x + (size_t)m * ms + at, valid, d[0]);
+#pragma unroll
+        for (int e = 0; e < VW; ++e) { const double t = d[0][e] - mu[e]; q[e] = q[e] + t * t; }
+    }
+    if constexpr (FULL) {
+#pragma unroll
+        for (int e = 0; e < VW; e += 4) {
+            *reinterpret_cast<float4*>(mean + at + e) = make_float4((float)mu[e], (float)mu[e + 1], (float)mu[e + 2], (float)mu[e + 3]);
+            *reinterpret_cast<float4*>(var + at + e) =
+                make_float4((float)(q[e] / dm), (float)(q[e + 1] / dm), (float)(q[e + 2] / dm), (float)(q[e + 3] / dm));
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < VW; ++e)
+            if ((valid >> e) & 1) {
+                mean[at + e] = (float)mu[e];
+                var[at + e] = (float)(q[e] / dm);
+            }
+    }
+}
+
+// total = (n + 2) * vecs work items, vecs = vectors per row (launch_ensemble_stats)
+template <typename S>
+__global__ __launch_bounds__(256) void k_ensemble_stats(const S* __restrict__ x, int pitch, int n, size_t ms, int members, int vecs,
+                                                        float* __restrict__ mean, float* __restrict__ var)
+{
+    constexpr int VW = StatsVec<S>::VW;
+    const unsigned t = blockIdx.x * 256u + threadIdx.x;          // (n + 2) * vecs < 2^32 for every N the library accepts
+    if (t >= (unsigned)(n + 2) * (unsigned)vecs) return;
+    const int row = (int)(t / (unsigned)vecs), v = (int)(t % (unsigned)vecs);
+    const int c0 = 1 + VW * (v - 1);                     // first column of this lane's vector (vector 0: 1 - VW)
+    int valid = 0;
+#pragma unroll
+    for (int e = 0; e < VW; ++e)
+        if (c0 + e >= 0 && c0 + e <= n + 1) valid |= 1 << e;
+    // XOFF + c0 = 64 + VW * (v - 1) is a multiple of VW and never negative: vector 0 starts in the left pad, which it skips
+    const size_t at = (size_t)row * (size_t)pitch + (size_t)(XOFF + c0);
+    if (valid == (1 << VW) - 1) stats_cell<S, true>(x, ms, members, at, valid, mean, var);
+    else stats_cell<S, false>(x, ms, members, at, valid, mean, var);
 }
 
 // ---------------------------------------------------------------------------
@@ -1882,21 +2055,45 @@ void launch_gradient_advect(hipStream_t s, int st, void* u, void* v, const void*
 }
 
 void launch_absmax2(hipStream_t s, int st, const void* u, const void* v, int pitch, int n, int row_lo, int row_hi,
-                    unsigned int* result, Members mb)
+                    unsigned int* result, Members mb, int rstride)
 {
     if (row_hi <= row_lo) return;
     const unsigned blocks = (unsigned)(row_hi - row_lo) < 1024u ? (unsigned)(row_hi - row_lo) : 1024u;
     FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_absmax2<S>, dim3(blocks, mb.count), dim3(256), 0, s, (const S*)u, (const S*)v, pitch,
-                                            n, row_lo, row_hi, result, mb.stride));
+                                            n, row_lo, row_hi, result, mb.stride, rstride));
 }
 
 void launch_residual(hipStream_t s, int st, const void* x, const void* x0, int pitch, int n, int row_lo, int row_hi,
-                     float alpha, float beta, unsigned int* result, Members mb)
+                     float alpha, float beta, unsigned int* result, Members mb, int rstride, const float2* mab)
 {
     if (row_hi <= row_lo) return;
     const unsigned blocks = (unsigned)(row_hi - row_lo) < 1024u ? (unsigned)(row_hi - row_lo) : 1024u;
     FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_residual<S>, dim3(blocks, mb.count), dim3(256), 0, s, (const S*)x, (const S*)x0, pitch,
-                                            n, row_lo, row_hi, alpha, beta, result, mb.stride));
+                                            n, row_lo, row_hi, alpha, beta, result, mb.stride, rstride, mab));
+}
+
+// sized from the whole launch: blocks x members is a few rounds of the chip whatever the split between the two, so an
+// ensemble of small grids fills the GPU as one large grid does; at least one block per member, at most one per row
+int moment_blocks(int n, int members)
+{
+    return std::max(1, std::min(n, kMomentBlocks / std::max(1, members)));
+}
+
+void launch_member_moments(hipStream_t s, int st, const void* x, int pitch, int n, Members mb, double2* partials, double2* out)
+{
+    const int blocks = moment_blocks(n, mb.count);
+    FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_member_moments<S>, dim3(blocks, mb.count), dim3(256), 0, s, (const S*)x, pitch, n, mb.stride,
+                                            partials));
+    hipLaunchKernelGGL(k_fold_moments, dim3(mb.count), dim3(64), 0, s, partials, blocks, out);
+}
+
+void launch_ensemble_stats(hipStream_t s, int st, const void* x, int pitch, int n, Members mb, float* mean, float* var)
+{
+    const int vw = 16 / (int)storage_bytes(st);
+    const int vecs = 1 + (n + 1 + vw - 1) / vw;          // vector 0: ghost column 0; the others: columns 1 .. n + 1
+    const unsigned total = (unsigned)(n + 2) * (unsigned)vecs;
+    FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_ensemble_stats<S>, dim3(cdiv(total, 256)), dim3(256), 0, s, (const S*)x, pitch, n, mb.stride,
+                                            mb.count, vecs, mean, var));
 }
 
 }  // namespace fluid

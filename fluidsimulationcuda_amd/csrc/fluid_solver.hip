@@ -1855,6 +1855,12 @@ int fluid_destroy(fluid_ctx* c)
     for (hipEvent_t ev : c->consts.free_events) (void)hipEventDestroy(ev);
     if (c->consts.dev) (void)hipFree(c->consts.dev);
     if (c->consts.host) (void)hipHostFree(c->consts.host);
+    if (c->red.d_max) (void)hipFree(c->red.d_max);
+    if (c->red.d_moments) (void)hipFree(c->red.d_moments);
+    if (c->red.d_partials) (void)hipFree(c->red.d_partials);
+    if (c->red.host) (void)hipHostFree(c->red.host);
+    if (c->red.d_mean) (void)hipFree(c->red.d_mean);
+    if (c->red.d_var) (void)hipFree(c->red.d_var);
     if (c->d_partials) (void)hipFree(c->d_partials);
     if (c->scalar_ready) (void)hipEventDestroy(c->scalar_ready);
     if (c->own_arena && c->arena) (void)hipFree(c->arena);
@@ -2415,6 +2421,157 @@ int fluid_absmax_velocity(fluid_ctx* c, int u, int v, float* out)
     fluid::launch_absmax2(c->stream, c->st, c->ptr(u), c->ptr(v), c->pitch, c->n, c->own0, c->own1, c->d_scalar, c->mb());
     TRY(reduce_to_host(c, out));
     return exchange(c, FLUID_XCHG_MAX, {}, 0, out);
+}
+
+// ---- ensemble diagnostics -----------------------------------------------------
+// Results and scratch are library-owned and outside the arena (fluid_ctx.h: EnsembleReduce), allocated by the first call
+// that needs them.  An allocation that fails leaves the context as it was: what it had begun is freed again.
+static int ensure_member_results(fluid_ctx* c)
+{
+    EnsembleReduce& r = c->red;
+    if (r.d_max) return FLUID_OK;
+    const size_t m = (size_t)c->members;
+    const size_t parts = m * (size_t)fluid::moment_blocks(c->n, c->members);
+    unsigned int* d_max = nullptr;
+    double2 *d_mom = nullptr, *d_part = nullptr;
+    char* host = nullptr;
+    hipError_t e = hipMalloc((void**)&d_max, m * sizeof(unsigned));
+    if (e == hipSuccess) e = hipMalloc((void**)&d_mom, m * sizeof(double2));
+    if (e == hipSuccess) e = hipMalloc((void**)&d_part, parts * sizeof(double2));
+    if (e == hipSuccess) e = hipHostMalloc((void**)&host, m * sizeof(double2), hipHostMallocDefault);
+    if (e != hipSuccess) {
+        if (d_max) (void)hipFree(d_max);
+        if (d_mom) (void)hipFree(d_mom);
+        if (d_part) (void)hipFree(d_part);
+        (void)hipGetLastError();
+        return fail(e == hipErrorOutOfMemory ? FLUID_E_NOMEM : FLUID_E_HIP, "ensemble diagnostics: allocating the results of %d members: %s",
+                    c->members, hipGetErrorString(e));
+    }
+    r.d_max = d_max;
+    r.d_moments = d_mom;
+    r.d_partials = d_part;
+    r.host = host;
+    return FLUID_OK;
+}
+
+// the two statistics fields: zeroed once, so their pad columns (which no kernel writes) stay zero
+static int ensure_stats(fluid_ctx* c)
+{
+    EnsembleReduce& r = c->red;
+    if (r.d_mean) return FLUID_OK;
+    const size_t bytes = c->field_floats * sizeof(float);
+    float *mean = nullptr, *var = nullptr;
+    hipError_t e = hipMalloc((void**)&mean, bytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&var, bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(mean, 0, bytes, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(var, 0, bytes, c->stream);
+    if (e != hipSuccess) {
+        if (mean) (void)hipFree(mean);
+        if (var) (void)hipFree(var);
+        (void)hipGetLastError();
+        return fail(e == hipErrorOutOfMemory ? FLUID_E_NOMEM : FLUID_E_HIP, "fluid_ensemble_stats: allocating two fields of %zu bytes: %s", bytes,
+                    hipGetErrorString(e));
+    }
+    r.d_mean = mean;
+    r.d_var = var;
+    return FLUID_OK;
+}
+
+// the members' result words (non-negative floats) to the caller's array
+static int member_words_to_host(fluid_ctx* c, float* out)
+{
+    const size_t bytes = (size_t)c->members * sizeof(unsigned);
+    HIP_TRY(hipMemcpyAsync(c->red.host, c->red.d_max, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::memcpy(out, c->red.host, bytes);
+    return FLUID_OK;
+}
+
+int fluid_residual_members(fluid_ctx* c, int x, int x0, const float* alpha, const float* beta, float* out)
+{
+    TRY(check_member_args(c, "fluid_residual_members", {{"alpha", alpha}, {"beta", beta}}));
+    if (!out) return fail(FLUID_E_INVALID, "fluid_residual_members: null array `out`");
+    if (!c->valid_field(x) || !c->valid_field(x0)) return fail(FLUID_E_INVALID, "fluid_residual_members: bad field id %d", c->valid_field(x) ? x0 : x);
+    if (c->members == 1) return fluid_residual(c, x, x0, alpha[0], beta[0], out);
+    TRY(ensure_consts(c));
+    TRY(ensure_member_results(c));
+    TRY(materialize(c, {x, x0}));
+    const float2* mab = nullptr;
+    TRY(member_pairs(c, alpha, beta, &mab));
+    HIP_TRY(hipMemsetAsync(c->red.d_max, 0, (size_t)c->members * sizeof(unsigned), c->stream));
+    fluid::launch_residual(c->stream, c->st, c->ptr(x), c->ptr(x0), c->pitch, c->n, c->own0, c->own1, alpha[0], beta[0], c->red.d_max,
+                           c->mb(), /*rstride=*/1, mab);
+    HIP_TRY(hipGetLastError());
+    return member_words_to_host(c, out);
+}
+
+int fluid_absmax_velocity_members(fluid_ctx* c, int u, int v, float* out)
+{
+    if (!c) return fail(FLUID_E_INVALID, "fluid_absmax_velocity_members: null context");
+    if (!out) return fail(FLUID_E_INVALID, "fluid_absmax_velocity_members: null array `out`");
+    if (!c->valid_field(u) || !c->valid_field(v)) return fail(FLUID_E_INVALID, "fluid_absmax_velocity_members: bad field id %d", c->valid_field(u) ? v : u);
+    if (c->members == 1) return fluid_absmax_velocity(c, u, v, out);
+    TRY(ensure_member_results(c));
+    TRY(materialize(c, {u, v}));
+    HIP_TRY(hipMemsetAsync(c->red.d_max, 0, (size_t)c->members * sizeof(unsigned), c->stream));
+    fluid::launch_absmax2(c->stream, c->st, c->ptr(u), c->ptr(v), c->pitch, c->n, c->own0, c->own1, c->red.d_max, c->mb(), /*rstride=*/1);
+    HIP_TRY(hipGetLastError());
+    return member_words_to_host(c, out);
+}
+
+// a sum over the rows of other ranks would need an exchange kind the callback contract does not have
+static int refuse_slabs(const fluid_ctx* c, const char* call)
+{
+    if (c->nranks > 1) return fail(FLUID_E_INVALID, "%s: not available on row slabs (this context is rank %d of %d)", call, c->rank, c->nranks);
+    return FLUID_OK;
+}
+
+int fluid_member_moments(fluid_ctx* c, int field, double* sum, double* sumsq)
+{
+    if (!c) return fail(FLUID_E_INVALID, "fluid_member_moments: null context");
+    if (!sum && !sumsq) return fail(FLUID_E_INVALID, "fluid_member_moments: `sum` and `sumsq` are both null");
+    if (!c->valid_field(field)) return fail(FLUID_E_INVALID, "fluid_member_moments: bad field id %d", field);
+    TRY(refuse_slabs(c, "fluid_member_moments"));
+    TRY(ensure_member_results(c));
+    TRY(materialize(c, field));
+    fluid::launch_member_moments(c->stream, c->st, c->ptr(field), c->pitch, c->n, c->mb(), c->red.d_partials, c->red.d_moments);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(c->red.host, c->red.d_moments, (size_t)c->members * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const double2* h = reinterpret_cast<const double2*>(c->red.host);
+    for (int m = 0; m < c->members; ++m) {
+        if (sum) sum[m] = h[m].x;
+        if (sumsq) sumsq[m] = h[m].y;
+    }
+    return FLUID_OK;
+}
+
+int fluid_ensemble_stats(fluid_ctx* c, int field, float* mean, float* variance)
+{
+    if (!c) return fail(FLUID_E_INVALID, "fluid_ensemble_stats: null context");
+    if (!c->valid_field(field)) return fail(FLUID_E_INVALID, "fluid_ensemble_stats: bad field id %d", field);
+    TRY(refuse_slabs(c, "fluid_ensemble_stats"));
+    TRY(ensure_stats(c));
+    TRY(materialize(c, field));
+    fluid::launch_ensemble_stats(c->stream, c->st, c->ptr(field), c->pitch, c->n, c->mb(), c->red.d_mean, c->red.d_var);
+    HIP_TRY(hipGetLastError());
+    c->red.have_stats = true;
+    if (!mean && !variance) return FLUID_OK;       // computed only: the results stay on the device (fluid_ensemble_stats_ptr)
+    const size_t hp = (size_t)c->w * sizeof(float), dp = (size_t)c->pitch * sizeof(float);
+    if (mean) HIP_TRY(hipMemcpy2DAsync(mean, hp, c->red.d_mean + XOFF, dp, hp, (size_t)c->w, hipMemcpyDeviceToHost, c->stream));
+    if (variance) HIP_TRY(hipMemcpy2DAsync(variance, hp, c->red.d_var + XOFF, dp, hp, (size_t)c->w, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return FLUID_OK;
+}
+
+int fluid_ensemble_stats_ptr(fluid_ctx* c, void** mean_dev, void** variance_dev)
+{
+    if (!c) return fail(FLUID_E_INVALID, "fluid_ensemble_stats_ptr: null context");
+    TRY(refuse_slabs(c, "fluid_ensemble_stats_ptr"));
+    if (!c->red.have_stats) return fail(FLUID_E_INVALID, "fluid_ensemble_stats_ptr: no fluid_ensemble_stats has run on this context yet");
+    if (mean_dev) *mean_dev = c->red.d_mean;
+    if (variance_dev) *variance_dev = c->red.d_var;
+    return FLUID_OK;
 }
 
 // ---- timing -------------------------------------------------------------------

@@ -241,6 +241,44 @@ class FluidSolver:
         capi.check(capi.lib().fluid_absmax_velocity(self._h, _fid(u), _fid(v), C.byref(out)))
         return out.value
 
+    # -- looking at an ensemble: one value per member, sums per member, statistics across the members
+    def residual_members(self, x, x0, alpha, beta):
+        """fluid_residual per member, each with its own coefficients (a scalar or one value per member each): a float32
+        array of `members` values."""
+        mv = member_values(self.members, alpha=alpha, beta=beta)
+        if mv is None:      # all scalars: broadcast here, this call always returns one value per member
+            mv = {"alpha": np.full(self.members, alpha, np.float32), "beta": np.full(self.members, beta, np.float32)}
+        out = np.empty(self.members, np.float32)
+        capi.check(capi.lib().fluid_residual_members(self._h, _fid(x), _fid(x0), _mf(mv["alpha"]), _mf(mv["beta"]), _mf(out)))
+        return out
+
+    def absmax_velocity_members(self, u="u", v="v"):
+        out = np.empty(self.members, np.float32)
+        capi.check(capi.lib().fluid_absmax_velocity_members(self._h, _fid(u), _fid(v), _mf(out)))
+        return out
+
+    def member_moments(self, field):
+        """(sum of x, sum of x*x) over each member's interior cells: two float64 arrays of `members` values."""
+        s, q = np.empty(self.members, np.float64), np.empty(self.members, np.float64)
+        dp = C.POINTER(C.c_double)
+        capi.check(capi.lib().fluid_member_moments(self._h, _fid(field), s.ctypes.data_as(dp), q.ctypes.data_as(dp)))
+        return s, q
+
+    def ensemble_stats(self, field, mean=True, variance=True):
+        """Per cell across the members: (mean, population variance) as (N+2, N+2) float32 arrays; None for the one not
+        asked for.  With neither, the statistics are only enqueued and stay on the device (ensemble_stats_ptr)."""
+        w = self.n + 2
+        mu = np.empty((w, w), np.float32) if mean else None
+        var = np.empty((w, w), np.float32) if variance else None
+        capi.check(capi.lib().fluid_ensemble_stats(self._h, _fid(field), _mf(mu) if mean else None, _mf(var) if variance else None))
+        return mu, var
+
+    def ensemble_stats_ptr(self):
+        """Device addresses (mean, variance) of the float fields the last ensemble_stats filled (layout of fluid_layout)."""
+        mu, var = C.c_void_p(), C.c_void_p()
+        capi.check(capi.lib().fluid_ensemble_stats_ptr(self._h, C.byref(mu), C.byref(var)))
+        return mu.value, var.value
+
     def set_jacobi_variant(self, variant):
         capi.check(capi.lib().fluid_set_jacobi_variant(self._h, variant))
 

@@ -184,7 +184,8 @@ int fluid_synchronize(fluid_ctx *ctx);
  * On a context with more than one member:
  *   - fluid_upload / fluid_download / fluid_upload_rows / fluid_download_rows return FLUID_E_INVALID (they would have to
  *     pick a member or broadcast silently): use the _member calls;
- *   - fluid_residual and fluid_absmax_velocity return the maximum over all members;
+ *   - fluid_residual and fluid_absmax_velocity return the maximum over all members (one value per member, sums and
+ *     statistics across the members: the ensemble diagnostics further down);
  *   - fluid_op_diffuse_tol (every member's sweep count would depend on the others), fluid_set_exchange,
  *     fluid_exchange_now and the fluid_exchange_rccl_* calls return FLUID_E_INVALID;
  *   - fluid_timing counts jacobi_field_launches, sweeps and pressure_sweeps once per member, jacobi_launches per launch. */
@@ -208,8 +209,9 @@ int fluid_download_member(fluid_ctx *ctx, int member, int field, float *host);
  * synchronise each): the first step of M distinct viscosities and M distinct diffusivities pays about 2 M proofs.
  * A null context or array, or an entry that is not finite: FLUID_E_INVALID (the message names the call and the member),
  * nothing launched, nothing changed.  Every finite value is accepted (dt <= 0, coefficients 0, betas <= 0 included).
- * With one member (row slabs included) a _members call is the scalar call with element 0.  fluid_residual keeps scalar
- * coefficients; fluid_op_diffuse_tol and the exchange calls stay unavailable on ensembles. */
+ * With one member (row slabs included) a _members call is the scalar call with element 0.  The residual per member, with
+ * each member's own coefficients, is fluid_residual_members (ensemble diagnostics, below); fluid_op_diffuse_tol and the
+ * exchange calls stay unavailable on ensembles. */
 int fluid_step_members(fluid_ctx *ctx, const float *dt, const float *diff, const float *visc, int iters,
                        int nsteps, int use_sources);
 int fluid_vel_step_members(fluid_ctx *ctx, const float *dt, const float *visc, int iters);
@@ -263,6 +265,54 @@ int fluid_op_subtract_gradient(fluid_ctx *ctx, int u, int v, int p);            
 int fluid_residual(fluid_ctx *ctx, int x, int x0, float alpha, float beta, float *out);
 /* max over owned interior cells of max(|u|,|v|) */
 int fluid_absmax_velocity(fluid_ctx *ctx, int u, int v, float *out);
+
+/* ---- ensemble diagnostics: looking at an ensemble without taking it apart ---------------------------------
+ * M = fluid_members(ctx); all arrays are host memory; every call is synchronous like fluid_residual unless said
+ * otherwise; none alters what a later download or step sees (a field's lazy state is settled first, as by
+ * fluid_residual, not lost).  The launch count of a call does not depend on M: one kernel per maxima call, two per
+ * moments call, one per statistics call.  Results and scratch are library-owned and outside the arena, allocated at the
+ * first call that needs them (the two statistics fields: 2 x field_floats floats) and freed by fluid_destroy; an
+ * allocation that fails is FLUID_E_NOMEM and leaves the context usable.
+ *
+ * Definitions:
+ * - fluid_residual_members, fluid_absmax_velocity_members: out[m] = what fluid_residual / fluid_absmax_velocity return
+ *   on a one-member context that holds member m's fields, with alpha[m], beta[m] as its coefficients: bit for bit.  The
+ *   arithmetic of the scalar calls (|beta*x - alpha*(((L+R)+U)+D) - x0| in float, fmaxf from 0, NaN cells skipped, never
+ *   NaN), one result word per member.  A member full of NaN or inf changes no other member's value.  With equal
+ *   coefficients for all members, max(out) == fluid_residual(...), exactly.
+ * - fluid_member_moments: per member, over the interior cells (rows and columns 1..N): sum[m] = sum of x, sumsq[m] = sum
+ *   of x*x, accumulated in double from the stored values widened exactly (x*x is exact in double).  No floating-point
+ *   atomics and a fixed order: per-block partial sums stored to a scratch buffer, folded by a second small kernel.  So
+ *   the result is the same bits call after call and process after process for the same data, N, M, storage type.
+ *   Exactness follows where it can: when every partial sum is representable (dyadic data) the result is the exact sum.
+ *   Either pointer may be null, not both.
+ * - fluid_ensemble_stats: across the members, per cell, ghost cells included: mean and population variance of a field,
+ *   as float fields.  Per cell, all in IEEE double with no contraction: s = (double)x_0; s += (double)x_m for
+ *   m = 1 .. M-1 in member order (starting from member 0's value, not from 0.0, so a cell that is -0 in every member has
+ *   mean -0); mean_d = s / (double)M; mean = (float)mean_d; d_m = (double)x_m - mean_d; q = d_0*d_0; q += d_m*d_m in
+ *   member order; variance = (float)(q / (double)M).  Two passes over the members on purpose: the one-pass form
+ *   sum(x^2) - (sum x)^2 / M loses the variance of a field whose spread is small against its mean.  M = 1: the mean is
+ *   the field, the variance +0 (NaN where the field is not finite).
+ *   mean / variance: host (N+2)^2 arrays in the reference's dense layout, or null.  Both null: the results are only
+ *   computed (enqueued on the context's stream, no wait) and stay on the device.
+ * - fluid_ensemble_stats_ptr: device addresses of the two library-owned result fields (always float, layout of
+ *   fluid_layout(): pitch, xoff; pad columns zero), holding the results of the last fluid_ensemble_stats until the next
+ *   one or fluid_destroy.  FLUID_E_INVALID before the first.
+ * - fp16 storage: every value is widened exactly; results stay float / double.  All calls see a field as
+ *   fluid_download_member would show it right after the call (the fp16 pressure scale and pending increments are settled
+ *   first, as for fluid_residual).
+ * Refusals, all FLUID_E_INVALID with a message that names the call (and the member for a bad entry), found before
+ * anything is launched or any state changes: null context, null output where one is required, bad field id, a
+ * non-finite alpha[m] / beta[m] (x == x0 is no error, as in fluid_residual).  On a context with one member the two
+ * _members maxima are the scalar calls with element 0, row slabs included.  fluid_member_moments, fluid_ensemble_stats
+ * and fluid_ensemble_stats_ptr are refused on row slabs (nranks > 1): a sum over ranks needs an exchange kind the
+ * callback contract does not have.  fluid_residual and fluid_absmax_velocity keep returning the maximum over the
+ * members. */
+int fluid_residual_members(fluid_ctx *ctx, int x, int x0, const float *alpha, const float *beta, float *out);
+int fluid_absmax_velocity_members(fluid_ctx *ctx, int u, int v, float *out);
+int fluid_member_moments(fluid_ctx *ctx, int field, double *sum, double *sumsq);
+int fluid_ensemble_stats(fluid_ctx *ctx, int field, float *mean, float *variance);
+int fluid_ensemble_stats_ptr(fluid_ctx *ctx, void **mean_dev, void **variance_dev);
 
 int fluid_set_jacobi_variant(fluid_ctx *ctx, int variant);
 /* How FLUID_JACOBI_TB divides by `beta` in a solve with these coefficients (diagnostic; runs the on-device proof
