@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/fluid_amd.h"
@@ -31,22 +32,50 @@ void rccl_release(RcclExchange* x);
         if (rc_ != FLUID_OK) return rc_; \
     } while (0)
 
+// A physical parameter of a call, or a value a field's record keeps from one: the same float for every member of the
+// context, or one float per member (the fluid_*_members calls; exactly `members` of them, copied from the caller's array).
+// at(0) is member 0's value either way -- what a launch passes by value beside a per-member table -- and that is arranged
+// by the constructors here and nowhere else.
+class MemberVal {
+    float s_;
+    std::vector<float> v_;      // empty: s_ holds for everybody
+    explicit MemberVal(std::vector<float>&& v) : s_(v[0]), v_(std::move(v)) {}
+
+public:
+    MemberVal(float v = 0.0f) : s_(v) {}
+    MemberVal(const float* per_member, int members) : s_(per_member[0]), v_(per_member, per_member + members) {}
+    bool uniform() const { return v_.empty(); }
+    float at(int m) const { return v_.empty() ? s_ : v_[(size_t)m]; }
+    const std::vector<float>& values() const { return v_; }      // one per member; empty when uniform
+    // floats compared by value (NaN differs from itself), and a uniform value differs from a per-member one
+    bool operator==(const MemberVal& o) const { return s_ == o.s_ && v_ == o.v_; }
+    // f(this member's value, b's) for every member: uniform if both are
+    template <class F>
+    MemberVal map(const MemberVal& b, F f) const
+    {
+        if (uniform() && b.uniform()) return MemberVal(f(s_, b.s_));
+        std::vector<float> r(uniform() ? b.v_.size() : v_.size());
+        for (size_t m = 0; m < r.size(); ++m) r[m] = f(at((int)m), b.at((int)m));
+        return MemberVal(std::move(r));
+    }
+    template <class F>
+    MemberVal map(F f) const { return map(MemberVal(), [&](float x, float) { return f(x); }); }
+};
+
 // What one field's buffer holds beyond its memory (fluid_solver.hip: "row-slab bookkeeping", "fields that are zero by
 // definition").  Two fields trade buffers by trading the whole record; only wrote() and mark_zero() reset one.
 // An ensemble keeps ONE record per field id too: every member goes through the same calls, so what is owed or known of a
-// field is the same for all of them, and `ptr` is member 0's copy (member m: m * field_floats elements behind it).
+// field is the same for all of them -- only the two amounts owed (pend_inc, src_dt) may be one per member, after a
+// fluid_*_members call -- and `ptr` is member 0's copy (member m: m * field_floats elements behind it).
 struct FieldState {
     void* ptr = nullptr;
     int reach = 0;            // rows past each inner slab edge that hold their owner's values (see "row-slab bookkeeping")
     bool zero = false;        // all +0 by definition; the memory is NOT (yet) zeroed
     bool pend = false;        // owes itself `+ pend_inc` in every cell (deferred add_source of a zero source)
-    float pend_inc = 0.0f;
+    MemberVal pend_inc;
     // add_source of a real source, deferred into the next diffusion's first launch (fluid_solver.hip: op_add_source)
     int src_of = 0;           // 0: nothing owed; else 1 + the id of the source field s: owes itself + src_dt * s
-    float src_dt = 0.0f;
-    // After a fluid_*_members call the two values above differ from member to member: one entry per member then (and the
-    // scalar holds member 0's); empty: the scalar holds for everybody.  Everything else in this record stays shared.
-    std::vector<float> pend_incv, src_dtv;
+    MemberVal src_dt;
     // fp16 storage: a projection's pressure is of the order h * |velocity| -- 1e-5 at 16384^2, fp16 subnormals -- so in a
     // step the divergence and the pressure are kept multiplied by a power of two (fluid_solver.hip: project): fscale (1:
     // plain values), undone exactly when the field is downloaded and by a pass over it for any reader that does not know
@@ -65,7 +94,6 @@ struct ConstRing {
     struct Blob { size_t off, len; unsigned long long hash; hipEvent_t copied; };
     std::vector<Blob> live;                 // tables in the ring, oldest first
     std::vector<hipEvent_t> free_events;
-    long long uploads = 0;
 };
 
 // What the ensemble diagnostics (fluid_*_members maxima, fluid_member_moments, fluid_ensemble_stats) need beyond the

@@ -81,15 +81,17 @@ int check_fields(const fluid_ctx* c, std::initializer_list<int> ids)
     return FLUID_OK;
 }
 
-// A call's physical parameter: one scalar for every member (the classic calls), or one value per member (the
-// fluid_*_members calls; `m` then points at fluid_members() floats the library owns for the duration of the call).
-struct MVal {
-    float s;
-    const float* m;
-    MVal(float v) : s(v), m(nullptr) {}
-    MVal(float v, const float* pm) : s(v), m(pm) {}
-    float at(int i) const { return m ? m[i] : s; }
-};
+int check_iters(int iters)
+{
+    if (iters < 0 || (iters & 1)) return fail(FLUID_E_INVALID, "sweep count must be even and >= 0 (got %d)", iters);
+    return FLUID_OK;
+}
+
+int check_b(int b)
+{
+    if (b < 0 || b > 2) return fail(FLUID_E_INVALID, "b must be 0, 1 or 2");
+    return FLUID_OK;
+}
 
 // ---- tables of per-member constants (fluid_ctx.h: ConstRing) -------------------------------------------------------
 constexpr size_t kConstAlign = 256, kConstSlots = 8, kConstBlobs = 64;
@@ -149,31 +151,30 @@ int member_consts(fluid_ctx* c, const void* data, size_t len, const void** dev)
     HIP_TRY(hipEventRecord(ev, c->stream));
     r.live.push_back({lo, len, hash, ev});
     r.head = hi;
-    r.uploads += 1;
     *dev = r.dev + lo;
     return FLUID_OK;
 }
 
-// the single-sweep kernels' {alpha, beta} per member (nullptr: the scalars hold)
-int member_pairs(fluid_ctx* c, const float* alpha, const float* beta, const float2** dev)
+// the single-sweep kernels' {alpha, beta} per member (nullptr: both uniform, the values the launch passes hold)
+int member_pairs(fluid_ctx* c, const MemberVal& alpha, const MemberVal& beta, const float2** dev)
 {
     *dev = nullptr;
-    if (!alpha || !beta) return FLUID_OK;
+    if (alpha.uniform() && beta.uniform()) return FLUID_OK;
     std::vector<float2> ab(c->members);
-    for (int m = 0; m < c->members; ++m) ab[m] = make_float2(alpha[m], beta[m]);
+    for (int m = 0; m < c->members; ++m) ab[m] = make_float2(alpha.at(m), beta.at(m));
     const void* p = nullptr;
     TRY(member_consts(c, ab.data(), ab.size() * sizeof ab[0], &p));
     *dev = static_cast<const float2*>(p);
     return FLUID_OK;
 }
 
-// a device array with one float per member, or nullptr when `v` is empty (the scalar holds for everybody)
-int member_floats(fluid_ctx* c, const std::vector<float>& v, const float** dev)
+// a device array with one float per member, or nullptr when `v` is uniform (the value the launch passes holds)
+int member_floats(fluid_ctx* c, const MemberVal& v, const float** dev)
 {
     *dev = nullptr;
-    if (v.empty()) return FLUID_OK;
+    if (v.uniform()) return FLUID_OK;
     const void* p = nullptr;
-    TRY(member_consts(c, v.data(), v.size() * sizeof(float), &p));
+    TRY(member_consts(c, v.values().data(), v.values().size() * sizeof(float), &p));
     *dev = static_cast<const float*>(p);
     return FLUID_OK;
 }
@@ -474,6 +475,16 @@ int unscale(fluid_ctx* c, int f)
     return FLUID_OK;
 }
 
+// x += amount * src on rows [lo, hi) (src null: x += amount), each member by its own amount
+int add_source_now(fluid_ctx* c, int x, const void* src, int lo, int hi, const MemberVal& amount)
+{
+    const float* per_member = nullptr;
+    TRY(member_floats(c, amount, &per_member));
+    TIMED(c, FLUID_TIME_SOURCE,
+          fluid::launch_add_source(c->stream, c->st, c->ptr(x), src, c->pitch, lo, hi, amount.at(0), c->mb(), per_member));
+    return FLUID_OK;
+}
+
 int settle(fluid_ctx* c, int f, bool keep_scale = false)
 {
     if (!keep_scale) TRY(unscale(c, f));
@@ -482,11 +493,8 @@ int settle(fluid_ctx* c, int f, bool keep_scale = false)
     const int reach = c->nranks > 1 ? std::min(c->field[f].reach, exchange_cap(c)) : 0;
     int lo, hi;
     rows_with_walls(c, reach, &lo, &hi);
-    const float inc = c->field[f].pend_inc;
-    const float* minc = nullptr;
-    TRY(member_floats(c, c->field[f].pend_incv, &minc));       // each member its own increment
+    TRY(add_source_now(c, f, nullptr, lo, hi, c->field[f].pend_inc));
     c->field[f].pend = false;
-    TIMED(c, FLUID_TIME_SOURCE, fluid::launch_add_source(c->stream, c->st, c->ptr(f), nullptr, c->pitch, lo, hi, inc, c->mb(), minc));
     return FLUID_OK;
 }
 
@@ -500,12 +508,8 @@ int settle_source(fluid_ctx* c, int f)
     const int reach = c->nranks > 1 ? std::min({c->field[f].reach, c->field[s].reach, exchange_cap(c)}) : 0;
     int lo, hi;
     rows_with_walls(c, reach, &lo, &hi);
-    const float* mdt = nullptr;
-    TRY(member_floats(c, c->field[f].src_dtv, &mdt));           // each member its own dt
-    c->field[f].src_of = 0;
-    TIMED(c, FLUID_TIME_SOURCE,
-          fluid::launch_add_source(c->stream, c->st, c->ptr(f), c->ptr(s), c->pitch, lo, hi, c->field[f].src_dt, c->mb(), mdt));
-    wrote(c, f, reach);
+    TRY(add_source_now(c, f, c->ptr(s), lo, hi, c->field[f].src_dt));
+    wrote(c, f, reach);                // (src_of = 0)
     return FLUID_OK;
 }
 
@@ -528,7 +532,7 @@ void mark_zero(fluid_ctx* c, int f) { wrote(c, f, kEverywhere); c->field[f].zero
 // there): with the fused Jacobi kernel a real source is not added now -- the first launch of the solve whose right-hand
 // side x is and whose first guess s is (FluidSequential.c:181, :201, :209: SWAP, then diffuse) reads both fields anyway,
 // forms x + dt*s as it loads them and stores the sum out of place (op_diffuse_batch).  Any other reader settles it first.
-int op_add_source(fluid_ctx* c, int x, int s, MVal dt, bool defer = false)
+int op_add_source(fluid_ctx* c, int x, int s, const MemberVal& dt, bool defer = false)
 {
     // pointwise: valid as far out as both operands are
     const int reach = c->nranks > 1 ? std::min({c->field[x].reach, c->field[s].reach, exchange_cap(c)}) : 0;
@@ -537,31 +541,22 @@ int op_add_source(fluid_ctx* c, int x, int s, MVal dt, bool defer = false)
     TRY(materialize(c, x));
     if (c->field[s].zero) {
         volatile float z = 0.0f;
-        const float inc = dt.at(0) * z;    // the reference's dt * s[i] with s[i] = +0 (sign and NaN rules included)
-        std::vector<float> incv;           // ... per member: +0 or -0 as each member's dt has it
-        if (dt.m)
-            for (int m = 0; m < c->members; ++m) incv.push_back(dt.m[m] * z);
+        // the reference's dt * s[i] with s[i] = +0 (sign and NaN rules included): +0 or -0 as each member's dt has it
+        const MemberVal inc = dt.map([&](float d) { return d * z; });
         if (c->variant == fluid::JACOBI_TB && c->defer_zero_source) {
             c->field[x].pend = true;             // (x was settled just above: one pending increment at a time)
             c->field[x].pend_inc = inc;
-            c->field[x].pend_incv = std::move(incv);
             return FLUID_OK;               // x's reach unchanged: nothing was written
         }
-        const float* minc = nullptr;
-        TRY(member_floats(c, incv, &minc));
-        TIMED(c, FLUID_TIME_SOURCE, fluid::launch_add_source(c->stream, c->st, c->ptr(x), nullptr, c->pitch, lo, hi, inc, c->mb(), minc));
+        TRY(add_source_now(c, x, nullptr, lo, hi, inc));
     } else {
         TRY(settle(c, s));                 // (a source that is itself owed something: never inside a step)
         if (defer && c->fuse_add_source && c->variant == fluid::JACOBI_TB && fluid::jacobi_tb_exists(-1, -1, c->tb_nv, fluid::TB_ADDSRC)) {
             c->field[x].src_of = 1 + s;
-            c->field[x].src_dt = dt.at(0);
-            c->field[x].src_dtv.assign(dt.m, dt.m + (dt.m ? c->members : 0));
+            c->field[x].src_dt = dt;
             return FLUID_OK;               // x's reach unchanged: nothing was written
         }
-        const float* mdt = nullptr;
-        if (dt.m) TRY(member_floats(c, std::vector<float>(dt.m, dt.m + c->members), &mdt));
-        TIMED(c, FLUID_TIME_SOURCE,
-              fluid::launch_add_source(c->stream, c->st, c->ptr(x), c->ptr(s), c->pitch, lo, hi, dt.at(0), c->mb(), mdt));
+        TRY(add_source_now(c, x, c->ptr(s), lo, hi, dt));
     }
     wrote(c, x, reach);
     return FLUID_OK;
@@ -796,10 +791,15 @@ int pick_sweeps(const fluid_ctx* c, int remaining, int room, const SweepShape& s
 // One Jacobi solve of the step: field x (first guess in, result out), right-hand
 // side x0, wall rule b.  Up to three such solves of the same length run as one
 // batch (u, v and density diffusion are independent of one another).
+// Its coefficients belong to the caller (a step function, op_diffuse) and outlive the batch; u and v of a step share one
+// object, which is how batch_plan knows that they share their division plans too.
+struct Coeffs {
+    MemberVal alpha, beta;
+};
+
 struct Solve {
     int b, x, x0;
-    float alpha, beta;
-    const float *malpha = nullptr, *mbeta = nullptr;     // fluid_*_members: one pair per member (alpha, beta above: member 0's)
+    const Coeffs* k;
 };
 
 // FluidSequential.c:85-104.  Results land in the fields `x`.  A sweep that writes
@@ -828,8 +828,7 @@ struct Batch {
     const int* scratch;        // each solve's ping-pong partner
     const int* sum;            // where x0 + dt*s of a deferred add_source lands
     int cur[3], nxt[3];        // the fields each solve's next launch reads its guess from / writes to
-    DivPlan plan[3];
-    std::vector<DivPlan> mplan[3];   // a solve with per-member coefficients: each member's constants, all of plan[k].mode
+    std::vector<DivPlan> plan[3];    // per solve: one entry, or with per-member coefficients one per member, all of one mode
     bool same_mode, all_mode4, add_src;   // add_src: the right-hand sides' deferred add_source rides in the first launch
     float out_scale[3];
     SweepShape shape;
@@ -845,26 +844,27 @@ unsigned* solve_tiles(const fluid_ctx* c, int slot) { return c->tiles + (size_t)
 // beta is planned as a solve of its own would be (division_mode: proof per distinct beta, cached per process), and the solve
 // takes the members' common mode if they agree -- the ordinary case -- and otherwise the most general one proven for every
 // member's beta: 2, else 0.  Every mode is exact, so only speed depends on the choice.
-void plan_members(fluid_ctx* c, const float* alpha, const float* beta, std::vector<DivPlan>& out)
+void plan_members(fluid_ctx* c, const Coeffs& k, std::vector<DivPlan>& out)
 {
     const int M = c->members;
+    const MemberVal &alpha = k.alpha, &beta = k.beta;
     out.resize(M);
     bool same = true;
     for (int m = 0; m < M; ++m) {
-        out[m] = (m > 0 && beta[m] == beta[m - 1] && alpha[m] == alpha[m - 1]) ? out[m - 1] : division_mode(c, beta[m], alpha[m]);
+        out[m] = (m > 0 && beta.at(m) == beta.at(m - 1) && alpha.at(m) == alpha.at(m - 1)) ? out[m - 1] : division_mode(c, beta.at(m), alpha.at(m));
         same = same && out[m].mode == out[0].mode;
     }
     if (same) return;
     bool all2 = true;
     for (int m = 0; m < M; ++m) {
-        out[m] = division_mode(c, beta[m], alpha[m], /*force=*/2);
+        out[m] = division_mode(c, beta.at(m), alpha.at(m), /*force=*/2);
         all2 = all2 && out[m].mode == 2;
     }
     if (all2) return;
     for (int m = 0; m < M; ++m) {
         out[m] = DivPlan{};
-        out[m].arg = beta[m];
-        out[m].yd = 1.0 / (double)beta[m];
+        out[m].arg = beta.at(m);
+        out[m].yd = 1.0 / (double)beta.at(m);
     }
 }
 
@@ -877,7 +877,7 @@ int batch_prepare(fluid_ctx* c, Batch& B)
     if (B.scratch_base < 0 || B.scratch_base + B.count > 3) return fail(FLUID_E_INVALID, "a batch holds 1 to 3 solves");
     B.scratch = kScratch + B.scratch_base;
     B.sum = kSum + B.scratch_base;
-    if (B.iters < 0 || (B.iters & 1)) return fail(FLUID_E_INVALID, "sweep count must be even and >= 0 (got %d)", B.iters);
+    TRY(check_iters(B.iters));
     if (B.count < 1 || B.count > 3) return fail(FLUID_E_INVALID, "a batch holds 1 to 3 solves");
     for (int k = 0; k < B.count; ++k) {
         if (sv[k].x == sv[k].x0 || sv[k].x >= FLUID_TMP0 || sv[k].x0 >= FLUID_TMP0)
@@ -921,15 +921,19 @@ int batch_plan(fluid_ctx* c, Batch& B)
     for (int k = 0; k < B.count; ++k) {
         B.cur[k] = sv[k].x;
         B.nxt[k] = B.scratch[k];
-        B.plan[k].arg = sv[k].beta;
-        if (c->variant == fluid::JACOBI_TB) B.plan[k] = division_mode(c, sv[k].beta, sv[k].alpha);
-        if (c->variant == fluid::JACOBI_TB && sv[k].mbeta) {
-            if (k > 0 && sv[k].mbeta == sv[k - 1].mbeta && sv[k].malpha == sv[k - 1].malpha) B.mplan[k] = B.mplan[k - 1];   // (u and v)
-            else plan_members(c, sv[k].malpha, sv[k].mbeta, B.mplan[k]);
-            B.plan[k] = B.mplan[k][0];            // (the mode is every member's; the constants are read per member)
+        const Coeffs& co = *sv[k].k;
+        if (k > 0 && sv[k].k == sv[k - 1].k) {
+            B.plan[k] = B.plan[k - 1];                               // (u and v)
+        } else if (c->variant != fluid::JACOBI_TB) {
+            B.plan[k].assign(1, DivPlan{});                          // (true division, by the kernels of one sweep)
+            B.plan[k][0].arg = co.beta.at(0);
+        } else if (co.alpha.uniform() && co.beta.uniform()) {
+            B.plan[k].assign(1, division_mode(c, co.beta.at(0), co.alpha.at(0)));
+        } else {
+            plan_members(c, co, B.plan[k]);
         }
-        B.same_mode = B.same_mode && B.plan[k].mode == B.plan[0].mode;
-        B.all_mode4 = B.all_mode4 && B.plan[k].mode == 4;
+        B.same_mode = B.same_mode && B.plan[k][0].mode == B.plan[0][0].mode;
+        B.all_mode4 = B.all_mode4 && B.plan[k][0].mode == 4;
     }
     B.shape = sweep_shape(c, B.count);
     // a deferred add_source (op_add_source) rides in the first launch if that is a fused one of a shape that exists with the
@@ -939,9 +943,9 @@ int batch_plan(fluid_ctx* c, Batch& B)
     bool add_src = x00.src_of != 0 && B.ds == nullptr && B.same_mode;
     for (int k = 0; k < B.count; ++k) {
         const FieldState &x = c->field[sv[k].x], &x0 = c->field[sv[k].x0];
-        add_src = add_src && x0.src_of == 1 + sv[k].x && x0.src_dt == x00.src_dt && x0.src_dtv == x00.src_dtv && !x.zero && !x.pend && !x.src_of;
+        add_src = add_src && x0.src_of == 1 + sv[k].x && x0.src_dt == x00.src_dt && !x.zero && !x.pend && !x.src_of;
     }
-    B.add_src = add_src && fluid::jacobi_tb_exists(pick_sweeps(c, B.iters, B.iters, B.shape, B.all_mode4), B.plan[0].mode, c->tb_nv, fluid::TB_ADDSRC);
+    B.add_src = add_src && fluid::jacobi_tb_exists(pick_sweeps(c, B.iters, B.iters, B.shape, B.all_mode4), B.plan[0][0].mode, c->tb_nv, fluid::TB_ADDSRC);
     if (!B.add_src)
         for (int k = 0; k < B.count; ++k)
             if (c->field[sv[k].x0].src_of) {
@@ -953,7 +957,7 @@ int batch_plan(fluid_ctx* c, Batch& B)
     fluid::TileBatch tb{};
     int m = 0, valid = kEverywhere;
     for (int k = 0; k < B.count; ++k)
-        if (B.plan[k].mode == 3) {
+        if (B.plan[k][0].mode == 3) {
             tb.field[m] = c->ptr(sv[k].x0);
             tb.tiles[m] = solve_tiles(c, B.scratch_base + k);
             valid = std::min(valid, c->nranks > 1 ? c->field[sv[k].x0].reach : kEverywhere);
@@ -977,66 +981,63 @@ int batch_reach(const fluid_ctx* c, const Batch& B)
     return r;
 }
 
+// The constants of (solve j, member m) in one fused launch.  x0_inc: what the launch adds to the right-hand side as it loads
+// it; div_scale: the scale of what the launch itself forms (fill_batch).
+fluid::TbMemberK solve_constants(const Batch& B, int j, int m, const MemberVal& x0_inc, const MemberVal& div_scale)
+{
+    const DivPlan& p = B.plan[j][B.plan[j].size() > 1 ? (size_t)m : 0];
+    return {p.yd, B.sv[j].k->alpha.at(m), p.arg, p.hi, p.lo, x0_inc.at(m), div_scale.at(m), p.tile_thr, /*pad=*/0};
+}
+
 // the fused kernel's arguments for solves [first, last); divsrc / addsrc: the launch forms (and stores) the right-hand sides
 int fill_batch(fluid_ctx* c, const Batch& B, int first, int last, bool divsrc, bool addsrc, fluid::TbBatch* out)
 {
+    static const MemberVal nothing_pending(-0.0f);                   // x + (-0) is x for every x
+    // ADDSRC: each member's dt (batch_plan: the same for all solves); DIVSRC: the divergence's factor
+    const MemberVal own_scale(divsrc ? B.ds->scale : 0.0f);
+    const MemberVal& div_scale = addsrc ? c->field[B.sv[first].x0].src_dt : own_scale;
+    const MemberVal* x0_inc[3];
     fluid::TbBatch bt{};
-    bool per_member = false;
+    bool per_member = !div_scale.uniform();
     for (int j = first; j < last; ++j) {
         const int q = j - first;
-        const DivPlan& p = B.plan[j];
         const FieldState& x0 = c->field[B.sv[j].x0];
+        // a pending increment rides in every launch of the solve but one that forms the right-hand side itself
+        x0_inc[q] = x0.pend && !addsrc && !divsrc ? &x0.pend_inc : &nothing_pending;
+        per_member = per_member || B.plan[j].size() > 1 || !x0_inc[q]->uniform();
+        const fluid::TbMemberK k0 = solve_constants(B, j, 0, *x0_inc[q], div_scale);
         bt.x[q] = c->ptr(B.cur[j]);
         bt.x0[q] = x0.ptr;
         bt.out[q] = c->ptr(B.nxt[j]);
-        bt.alpha[q] = B.sv[j].alpha;
-        bt.beta[q] = p.arg;
-        bt.yd[q] = p.yd;
-        bt.hi[q] = p.hi;
-        bt.lo[q] = p.lo;
-        bt.tiles[q] = p.mode == 3 ? solve_tiles(c, B.scratch_base + j) : nullptr;
-        bt.tile_thr[q] = p.tile_thr;
+        bt.alpha[q] = k0.alpha;
+        bt.beta[q] = k0.beta;
+        bt.yd[q] = k0.yd;
+        bt.hi[q] = k0.hi;
+        bt.lo[q] = k0.lo;
+        bt.tiles[q] = B.plan[j][0].mode == 3 ? solve_tiles(c, B.scratch_base + j) : nullptr;
+        bt.tile_thr[q] = k0.tile_thr;
         bt.b[q] = B.sv[j].b;
         bt.x_zero[q] = c->field[B.cur[j]].zero ? 1 : 0;
-        bt.x0_inc[q] = x0.pend && !addsrc && !divsrc ? x0.pend_inc : -0.0f;     // x + (-0) is x for every x
+        bt.x0_inc[q] = k0.x0_inc;
         if (addsrc) bt.div[q] = c->ptr(B.sum[j]);
-        per_member = per_member || !B.mplan[j].empty() || (x0.pend && !addsrc && !divsrc && !x0.pend_incv.empty()) ||
-                     (addsrc && !x0.src_dtv.empty());
     }
     bt.count = last - first;
     bt.members = c->members;
     bt.mstride = c->field_floats;
     bt.tile_mstride = tile_words(c);
     bt.tile_pitch = fluid::tile_pitch(c->n);
-    if (addsrc) bt.div_scale = c->field[B.sv[first].x0].src_dt;
+    bt.div_scale = div_scale.at(0);
     if (divsrc) {
         bt.x[0] = c->ptr(B.ds->u);
         bt.x0[0] = c->ptr(B.ds->v);
         bt.div[0] = c->ptr(B.sv[0].x0);
-        bt.div_scale = B.ds->scale;
     }
     // something differs from member to member (fluid_*_members): the constants above, once per (solve, member), in a table
     if (per_member && c->members > 1) {
         const int M = c->members;
         std::vector<fluid::TbMemberK> rec((size_t)bt.count * M);
-        for (int j = first; j < last; ++j) {
-            const int q = j - first;
-            const FieldState& x0 = c->field[B.sv[j].x0];
-            const std::vector<float>& dtv = c->field[B.sv[first].x0].src_dtv;     // (batch_plan: the same for all solves)
-            for (int m = 0; m < M; ++m) {
-                const DivPlan& p = B.mplan[j].empty() ? B.plan[j] : B.mplan[j][m];
-                fluid::TbMemberK& r = rec[(size_t)q * M + m];
-                r.yd = p.yd;
-                r.alpha = B.sv[j].malpha ? B.sv[j].malpha[m] : B.sv[j].alpha;
-                r.beta = p.arg;
-                r.hi = p.hi;
-                r.lo = p.lo;
-                r.x0_inc = x0.pend_incv.empty() ? bt.x0_inc[q] : (x0.pend && !addsrc && !divsrc ? x0.pend_incv[m] : -0.0f);
-                r.div_scale = addsrc && !dtv.empty() ? dtv[m] : bt.div_scale;
-                r.tile_thr = p.tile_thr;
-                r.pad = 0;
-            }
-        }
+        for (int j = first; j < last; ++j)
+            for (int m = 0; m < M; ++m) rec[(size_t)(j - first) * M + m] = solve_constants(B, j, m, *x0_inc[j - first], div_scale);
         const void* dev = nullptr;
         TRY(member_consts(c, rec.data(), rec.size() * sizeof rec[0], &dev));
         bt.mk = static_cast<const fluid::TbMemberK*>(dev);
@@ -1159,7 +1160,7 @@ int batch_sweep(fluid_ctx* c, Batch& B)
             r = batch_reach(c, B);
         }
         const int T = canonical ? wantT : pick_sweeps(c, remaining, std::min(r, remaining), B.shape, B.all_mode4);
-        if (B.add_src && k == 0 && !fluid::jacobi_tb_exists(T, B.plan[0].mode, c->tb_nv, fluid::TB_ADDSRC)) {
+        if (B.add_src && k == 0 && !fluid::jacobi_tb_exists(T, B.plan[0][0].mode, c->tb_nv, fluid::TB_ADDSRC)) {
             B.add_src = false;                   // a shallower first launch than planned (short reach): the kernel of its own after all
             TRY(xchg_join(c));
             for (int j = 0; j < B.count; ++j) TRY(settle_source(c, sv[j].x0));
@@ -1174,9 +1175,9 @@ int batch_sweep(fluid_ctx* c, Batch& B)
             for (int j = 0; j < B.count; ++j) TRY(settle(c, sv[j].x0, /*keep_scale=*/true));
             for (int j = 0; j < B.count; ++j) {
                 const float2* mab = nullptr;
-                TRY(member_pairs(c, sv[j].malpha, sv[j].mbeta, &mab));
+                TRY(member_pairs(c, sv[j].k->alpha, sv[j].k->beta, &mab));
                 fluid::launch_jacobi(c->stream, c->st, v, c->ptr(B.cur[j]), c->ptr(sv[j].x0), c->ptr(B.nxt[j]), c->pitch, c->n, lo, hi,
-                                     sv[j].alpha, sv[j].beta, sv[j].b, c->mb(), mab);
+                                     sv[j].k->alpha.at(0), sv[j].k->beta.at(0), sv[j].b, c->mb(), mab);
             }
             if (c->timing) {
                 c->launches += B.count;
@@ -1189,7 +1190,7 @@ int batch_sweep(fluid_ctx* c, Batch& B)
                 const bool divsrc = B.ds != nullptr && k == 0, addsrc = B.add_src && k == 0;
                 fluid::TbBatch bt;
                 TRY(fill_batch(c, B, first, last, divsrc, addsrc, &bt));
-                TRY(launch_fused(c, bt, T, B.plan[first].mode, divsrc, addsrc, lo, hi));
+                TRY(launch_fused(c, bt, T, B.plan[first][0].mode, divsrc, addsrc, lo, hi));
                 if (c->timing) {
                     c->launches += 1;
                     c->field_launches += (long long)(last - first) * c->members;
@@ -1223,9 +1224,9 @@ int op_diffuse_batch(fluid_ctx* c, const Solve* sv, int count, int iters, int fi
     return timing_end(c, stop, iters * count * c->members);
 }
 
-int op_diffuse(fluid_ctx* c, int b, int x, int x0, MVal alpha, MVal beta, int iters, int final_reach = 0, const DivSource* ds = nullptr)
+int op_diffuse(fluid_ctx* c, int b, int x, int x0, const Coeffs& k, int iters, int final_reach = 0, const DivSource* ds = nullptr)
 {
-    const Solve one{b, x, x0, alpha.at(0), beta.at(0), alpha.m, beta.m};
+    const Solve one{b, x, x0, &k};
     return op_diffuse_batch(c, &one, 1, iters, final_reach, ds);
 }
 
@@ -1295,16 +1296,13 @@ int advect_bounded(fluid_ctx* c, int slot, std::initializer_list<int> sources, f
     return fetched ? run() : FLUID_OK;
 }
 
-// dt0 = dt * N of every member (nullptr: a scalar dt)
-int member_dt0(fluid_ctx* c, MVal dt, const float** dev)
+// dt0 = dt * N of every member (nullptr: a uniform dt)
+int member_dt0(fluid_ctx* c, const MemberVal& dt, const float** dev)
 {
-    std::vector<float> dt0;
-    if (dt.m)
-        for (int m = 0; m < c->members; ++m) dt0.push_back(dt.m[m] * (float)c->n);
-    return member_floats(c, dt0, dev);
+    return member_floats(c, dt.map([&](float d) { return d * (float)c->n; }), dev);
 }
 
-int op_advect(fluid_ctx* c, int b, int d, int d0, int u, int v, MVal dt)
+int op_advect(fluid_ctx* c, int b, int d, int d0, int u, int v, const MemberVal& dt)
 {
     if (d == d0 || d == u || d == v) return fail(FLUID_E_INVALID, "advect: output must not alias an input");
     const float dt0 = dt.at(0) * (float)c->n;
@@ -1319,7 +1317,7 @@ int op_advect(fluid_ctx* c, int b, int d, int d0, int u, int v, MVal dt)
 }
 
 // two advections along the same velocity (u, v) in one launch; results identical to two op_advect calls
-int op_advect2(fluid_ctx* c, int ba, int da, int d0a, int bb, int db, int d0b, int u, int v, MVal dt)
+int op_advect2(fluid_ctx* c, int ba, int da, int d0a, int bb, int db, int d0b, int u, int v, const MemberVal& dt)
 {
     for (int d : {da, db})
         if (d == d0a || d == d0b || d == u || d == v) return fail(FLUID_E_INVALID, "advect: output must not alias an input");
@@ -1384,7 +1382,7 @@ int op_subtract_gradient(fluid_ctx* c, int u, int v, int p, bool with_max = fals
 // the gradient subtraction of a projection and the advection of `d` (from d0, wall rule b) along the projected velocity,
 // in one launch: results identical to op_subtract_gradient followed by op_advect.  One GPU only (on slabs the advection
 // waits for a reduction over the velocity it follows).
-int op_gradient_advect(fluid_ctx* c, int u, int v, int p, int b, int d, int d0, MVal dt)
+int op_gradient_advect(fluid_ctx* c, int u, int v, int p, int b, int d, int d0, const MemberVal& dt)
 {
     if (p == u || p == v || u == v) return fail(FLUID_E_INVALID, "subtract_gradient: fields must be distinct");
     if (d == d0 || d == u || d == v || d == p || d0 == u || d0 == v)
@@ -1415,20 +1413,18 @@ void coefficients(int n, float dt, float coef, float* alpha, float* beta)
     *beta = 1.0f + four_a;
 }
 
-// alpha, beta of a diffusion with a scalar or per-member dt and coefficient: coefficients() per member, the same function
-struct Coef {
-    float alpha, beta;
-    std::vector<float> malpha, mbeta;
-    Coef(const fluid_ctx* c, MVal dt, MVal coef)
-    {
-        coefficients(c->n, dt.at(0), coef.at(0), &alpha, &beta);
-        if (!dt.m && !coef.m) return;
-        malpha.resize(c->members);
-        mbeta.resize(c->members);
-        for (int m = 0; m < c->members; ++m) coefficients(c->n, dt.at(m), coef.at(m), &malpha[m], &mbeta[m]);
-    }
-    Solve solve(int b, int x, int x0) const { return {b, x, x0, alpha, beta, malpha.empty() ? nullptr : malpha.data(), malpha.empty() ? nullptr : mbeta.data()}; }
-};
+// alpha, beta of a diffusion with a uniform or per-member dt and coefficient: coefficients() per member, the same function
+Coeffs diffusion_coeffs(const fluid_ctx* c, const MemberVal& dt, const MemberVal& coef)
+{
+    auto part = [&](bool want_beta) {
+        return dt.map(coef, [&](float d, float k) {
+            float alpha, beta;
+            coefficients(c->n, d, k, &alpha, &beta);
+            return want_beta ? beta : alpha;
+        });
+    };
+    return {part(false), part(true)};
+}
 
 // divergence -> pressure solve -> gradient subtraction (FluidSequential.c:213-223
 // and :238-240).  On slabs: ONE exchange (u, v, iters+2 rows) covers the divergence,
@@ -1436,7 +1432,7 @@ struct Coef {
 // `then_advect` (one GPU): d, d0, b, dt of an advection along (u, v) to run in the same launch as the gradient subtraction
 struct AdvectAfter {
     int b, d, d0;
-    MVal dt;
+    const MemberVal& dt;
 };
 
 // can the divergence be computed inside the first launch of the pressure solve that follows it?  The fused kernel, a first
@@ -1472,7 +1468,8 @@ int project(fluid_ctx* c, int u, int v, int p, int div, int iters, const AdvectA
         TRY(op_divergence(c, u, v, p, div, std::min(iters, c->halo - 1), c->pscale));
     }
     c->in_pressure_solve = true;            // timing only: reported separately (fluid_timing::pressure_ms)
-    const int rc_solve = op_diffuse(c, 0, p, div, 1.0f, 4.0f, iters, /*final_reach=*/1, fused ? &ds : nullptr);
+    const Coeffs pressure{1.0f, 4.0f};
+    const int rc_solve = op_diffuse(c, 0, p, div, pressure, iters, /*final_reach=*/1, fused ? &ds : nullptr);
     c->in_pressure_solve = false;
     TRY(rc_solve);
     if (fused) {                            // (the first launch recorded the rows it stored)
@@ -1486,16 +1483,16 @@ int project(fluid_ctx* c, int u, int v, int p, int div, int iters, const AdvectA
 
 // FluidSequential.c:189-241 with the SWAPs resolved into field roles:
 // after :201/:209 the diffused velocity lives in the *_prev buffers.
-int vel_step(fluid_ctx* c, MVal dt, MVal visc, int iters)
+int vel_step(fluid_ctx* c, const MemberVal& dt, const MemberVal& visc, int iters)
 {
     const int U = FLUID_U, V = FLUID_V, U0 = FLUID_U_PREV, V0 = FLUID_V_PREV;
     TRY(op_add_source(c, U, U0, dt, /*defer=*/true));
     TRY(op_add_source(c, V, V0, dt, /*defer=*/true));
-    const Coef cv(c, dt, visc);
+    const Coeffs cv = diffusion_coeffs(c, dt, visc);
     // one exchange feeds both solves: right-hand sides iters-1 rows out, first guesses iters rows
     const int h = std::min(iters, c->halo);
     TRY(need(c, {U, V, U0, V0}, h, /*async=*/true));
-    const Solve uv[2] = {cv.solve(1, U0, U), cv.solve(2, V0, V)};
+    const Solve uv[2] = {{1, U0, U, &cv}, {2, V0, V, &cv}};
     TRY(op_diffuse_batch(c, uv, 2, iters));
     TRY(xchg_join(c));
     TRY(project(c, U0, V0, /*p=*/U, /*div=*/V, iters, nullptr, /*with_max=*/true));
@@ -1506,12 +1503,12 @@ int vel_step(fluid_ctx* c, MVal dt, MVal visc, int iters)
 }
 
 // FluidSequential.c:176-186
-int dens_step(fluid_ctx* c, MVal dt, MVal diff, int iters)
+int dens_step(fluid_ctx* c, const MemberVal& dt, const MemberVal& diff, int iters)
 {
     const int X = FLUID_DENS, X0 = FLUID_DENS_PREV;
     TRY(op_add_source(c, X, X0, dt, /*defer=*/true));
-    const Coef cd(c, dt, diff);
-    const Solve one = cd.solve(0, X0, X);
+    const Coeffs cd = diffusion_coeffs(c, dt, diff);
+    const Solve one{0, X0, X, &cd};
     TRY(op_diffuse_batch(c, &one, 1, iters));
     TRY(vmax_begin(c, FLUID_U, FLUID_V));
     return advect_bounded(c, 1, {X0}, dt.at(0) * (float)c->n, [&] { return op_advect(c, 0, X, X0, FLUID_U, FLUID_V, dt); });
@@ -1522,7 +1519,7 @@ int dens_step(fluid_ctx* c, MVal dt, MVal diff, int iters)
 // diffusions are independent of one another and of everything in between, so they
 // run as ONE batch (one exchange on slabs, three times the waves per launch); the
 // arithmetic per cell and the final contents of all six fields are unchanged.
-int full_step(fluid_ctx* c, MVal dt, MVal diff, MVal visc, int iters)
+int full_step(fluid_ctx* c, const MemberVal& dt, const MemberVal& diff, const MemberVal& visc, int iters)
 {
     const int U = FLUID_U, V = FLUID_V, D = FLUID_DENS, U0 = FLUID_U_PREV, V0 = FLUID_V_PREV, D0 = FLUID_DENS_PREV;
     TRY(op_add_source(c, U, U0, dt, /*defer=*/true));
@@ -1531,9 +1528,9 @@ int full_step(fluid_ctx* c, MVal dt, MVal diff, MVal visc, int iters)
     // right-hand sides and first guesses together (zeroed sources are valid everywhere and skipped); async: the first launch
     // of the diffusion runs its interior strips while the rows travel (op_diffuse_batch)
     TRY(need(c, {U, V, D, U0, V0, D0}, std::min(iters, c->halo), /*async=*/true));
-    const Coef cv(c, dt, visc), cd(c, dt, diff);
+    const Coeffs cv = diffusion_coeffs(c, dt, visc), cd = diffusion_coeffs(c, dt, diff);
     const float dt0 = dt.at(0) * (float)c->n;      // (slabs only: one member)
-    const Solve all[3] = {cv.solve(1, U0, U), cv.solve(2, V0, V), cd.solve(0, D0, D)};
+    const Solve all[3] = {{1, U0, U, &cv}, {2, V0, V, &cv}, {0, D0, D, &cd}};
     if (c->nranks == 1) {
         TRY(op_diffuse_batch(c, all, 3, iters));
         TRY(project(c, U0, V0, /*p=*/U, /*div=*/V, iters));
@@ -2172,41 +2169,12 @@ int fluid_exchange_now(fluid_ctx* c, int kind, const int* fields, int nfields, i
     return FLUID_OK;
 }
 
-int fluid_vel_step(fluid_ctx* c, float dt, float visc, int iters)
-{
-    TRY(check_ctx(c));
-    if (iters < 0 || (iters & 1)) return fail(FLUID_E_INVALID, "sweep count must be even and >= 0 (got %d)", iters);
-    TRY(vel_step(c, dt, visc, iters));
-    HIP_TRY(hipGetLastError());
-    return FLUID_OK;
-}
-
-int fluid_dens_step(fluid_ctx* c, float dt, float diff, int iters)
-{
-    TRY(check_ctx(c));
-    if (iters < 0 || (iters & 1)) return fail(FLUID_E_INVALID, "sweep count must be even and >= 0 (got %d)", iters);
-    TRY(dens_step(c, dt, diff, iters));
-    HIP_TRY(hipGetLastError());
-    return FLUID_OK;
-}
-
-int fluid_step(fluid_ctx* c, float dt, float diff, float visc, int iters, int nsteps, int use_sources)
-{
-    TRY(check_ctx(c));
-    if (iters < 0 || (iters & 1)) return fail(FLUID_E_INVALID, "sweep count must be even and >= 0 (got %d)", iters);
-    if (nsteps < 0) return fail(FLUID_E_INVALID, "nsteps < 0");
-    for (int z = 0; z < nsteps; ++z) {
-        if (!(use_sources && z == 0)) TRY(zero_sources(c));
-        TRY(full_step(c, dt, diff, visc, iters));
-    }
-    HIP_TRY(hipGetLastError());
-    return FLUID_OK;
-}
-
-// ---- one value per member (ensembles) -------------------------------------------
-// Null arrays, a null context and non-finite entries are found here, before anything else happens: nothing is launched and
-// neither a field nor what the library still owes one changes.  On a context with one member (row slabs included) the
-// callers below hand element 0 to the scalar entry point.
+// ---- calls whose physical parameters are one value for everybody or one per member (ensembles) ---------------------
+// One body per call, on MemberVal: it checks the context and the call's other arguments and does the work.  The scalar
+// entry point is that body.  The _members one first finds null arrays, a null context and non-finite entries, before
+// anything else happens (nothing is launched and neither a field nor what the library still owes one changes), hands
+// element 0 to the scalar entry point on a context with one member (row slabs included), and has the table ring in place
+// before the body runs.
 struct MemberArg {
     const char* name;
     const float* v;
@@ -2223,111 +2191,68 @@ static int check_member_args(const fluid_ctx* c, const char* call, std::initiali
     return FLUID_OK;
 }
 
-int fluid_step_members(fluid_ctx* c, const float* dt, const float* diff, const float* visc, int iters, int nsteps, int use_sources)
+static int vel_step_body(fluid_ctx* c, const MemberVal& dt, const MemberVal& visc, int iters)
 {
-    TRY(check_member_args(c, "fluid_step_members", {{"dt", dt}, {"diff", diff}, {"visc", visc}}));
-    if (c->members == 1) return fluid_step(c, dt[0], diff[0], visc[0], iters, nsteps, use_sources);
-    if (iters < 0 || (iters & 1)) return fail(FLUID_E_INVALID, "sweep count must be even and >= 0 (got %d)", iters);
-    if (nsteps < 0) return fail(FLUID_E_INVALID, "nsteps < 0");
-    TRY(ensure_consts(c));
-    for (int z = 0; z < nsteps; ++z) {
-        if (!(use_sources && z == 0)) TRY(zero_sources(c));
-        TRY(full_step(c, MVal(dt[0], dt), MVal(diff[0], diff), MVal(visc[0], visc), iters));
-    }
+    TRY(check_ctx(c));
+    TRY(check_iters(iters));
+    TRY(vel_step(c, dt, visc, iters));
     HIP_TRY(hipGetLastError());
     return FLUID_OK;
 }
+
+int fluid_vel_step(fluid_ctx* c, float dt, float visc, int iters) { return vel_step_body(c, dt, visc, iters); }
 
 int fluid_vel_step_members(fluid_ctx* c, const float* dt, const float* visc, int iters)
 {
     TRY(check_member_args(c, "fluid_vel_step_members", {{"dt", dt}, {"visc", visc}}));
     if (c->members == 1) return fluid_vel_step(c, dt[0], visc[0], iters);
-    if (iters < 0 || (iters & 1)) return fail(FLUID_E_INVALID, "sweep count must be even and >= 0 (got %d)", iters);
     TRY(ensure_consts(c));
-    TRY(vel_step(c, MVal(dt[0], dt), MVal(visc[0], visc), iters));
+    return vel_step_body(c, {dt, c->members}, {visc, c->members}, iters);
+}
+
+static int dens_step_body(fluid_ctx* c, const MemberVal& dt, const MemberVal& diff, int iters)
+{
+    TRY(check_ctx(c));
+    TRY(check_iters(iters));
+    TRY(dens_step(c, dt, diff, iters));
     HIP_TRY(hipGetLastError());
     return FLUID_OK;
 }
+
+int fluid_dens_step(fluid_ctx* c, float dt, float diff, int iters) { return dens_step_body(c, dt, diff, iters); }
 
 int fluid_dens_step_members(fluid_ctx* c, const float* dt, const float* diff, int iters)
 {
     TRY(check_member_args(c, "fluid_dens_step_members", {{"dt", dt}, {"diff", diff}}));
     if (c->members == 1) return fluid_dens_step(c, dt[0], diff[0], iters);
-    if (iters < 0 || (iters & 1)) return fail(FLUID_E_INVALID, "sweep count must be even and >= 0 (got %d)", iters);
     TRY(ensure_consts(c));
-    TRY(dens_step(c, MVal(dt[0], dt), MVal(diff[0], diff), iters));
-    HIP_TRY(hipGetLastError());
-    return FLUID_OK;
+    return dens_step_body(c, {dt, c->members}, {diff, c->members}, iters);
 }
 
-int fluid_op_add_source_members(fluid_ctx* c, int x, int s, const float* dt)
-{
-    TRY(check_member_args(c, "fluid_op_add_source_members", {{"dt", dt}}));
-    if (c->members == 1) return fluid_op_add_source(c, x, s, dt[0]);
-    TRY(check_fields(c, {x, s}));
-    if (x == s) return fail(FLUID_E_INVALID, "add_source: x and s must differ");
-    TRY(ensure_consts(c));
-    TRY(op_add_source(c, x, s, MVal(dt[0], dt)));
-    HIP_TRY(hipGetLastError());
-    return FLUID_OK;
-}
-
-int fluid_op_jacobi_sweep_members(fluid_ctx* c, int b, int x, int x0, int out, const float* alpha, const float* beta)
-{
-    TRY(check_member_args(c, "fluid_op_jacobi_sweep_members", {{"alpha", alpha}, {"beta", beta}}));
-    if (c->members == 1) return fluid_op_jacobi_sweep(c, b, x, x0, out, alpha[0], beta[0]);
-    TRY(check_fields(c, {x, x0, out}));
-    if (b < 0 || b > 2) return fail(FLUID_E_INVALID, "b must be 0, 1 or 2");
-    if (out == x || out == x0) return fail(FLUID_E_INVALID, "jacobi_sweep: out must not alias an input");
-    TRY(ensure_consts(c));
-    TRY(materialize(c, {x, x0}));
-    const float2* mab = nullptr;
-    TRY(member_pairs(c, alpha, beta, &mab));
-    const int v1 = c->variant == fluid::JACOBI_TB ? fluid::JACOBI_STREAM : c->variant;   // one sweep: nothing to block
-    fluid::launch_jacobi(c->stream, c->st, v1, c->ptr(x), c->ptr(x0), c->ptr(out), c->pitch, c->n, c->own0, c->own1, alpha[0], beta[0], b,
-                         c->mb(), mab);
-    wrote(c, out, 0);
-    HIP_TRY(hipGetLastError());
-    return FLUID_OK;
-}
-
-int fluid_op_diffuse_members(fluid_ctx* c, int b, int x, int x0, const float* alpha, const float* beta, int iters)
-{
-    TRY(check_member_args(c, "fluid_op_diffuse_members", {{"alpha", alpha}, {"beta", beta}}));
-    if (c->members == 1) return fluid_op_diffuse(c, b, x, x0, alpha[0], beta[0], iters);
-    TRY(check_fields(c, {x, x0}));
-    if (b < 0 || b > 2) return fail(FLUID_E_INVALID, "b must be 0, 1 or 2");
-    TRY(ensure_consts(c));
-    return op_diffuse(c, b, x, x0, MVal(alpha[0], alpha), MVal(beta[0], beta), iters);
-}
-
-int fluid_op_advect_members(fluid_ctx* c, int b, int d, int d0, int u, int v, const float* dt)
-{
-    TRY(check_member_args(c, "fluid_op_advect_members", {{"dt", dt}}));
-    if (c->members == 1) return fluid_op_advect(c, b, d, d0, u, v, dt[0]);
-    TRY(check_fields(c, {d, d0, u, v}));
-    if (b < 0 || b > 2) return fail(FLUID_E_INVALID, "b must be 0, 1 or 2");
-    if (d == d0 || d == u || d == v) return fail(FLUID_E_INVALID, "advect: output must not alias an input");
-    TRY(ensure_consts(c));
-    TRY(op_advect(c, b, d, d0, u, v, MVal(dt[0], dt)));    // (an ensemble is one GPU: no bound to agree on)
-    HIP_TRY(hipGetLastError());
-    return FLUID_OK;
-}
-
-// ---- operators ---------------------------------------------------------------
-int fluid_op_set_bnd(fluid_ctx* c, int b, int x)
+static int step_body(fluid_ctx* c, const MemberVal& dt, const MemberVal& diff, const MemberVal& visc, int iters, int nsteps, int use_sources)
 {
     TRY(check_ctx(c));
-    TRY(check_fields(c, {x}));
-    if (b < 0 || b > 2) return fail(FLUID_E_INVALID, "b must be 0, 1 or 2");
-    if (c->nranks != 1) return fail(FLUID_E_INVALID, "fluid_op_set_bnd is a whole-grid operator (1 GPU)");
-    TRY(materialize(c, x));
-    fluid::launch_set_bnd(c->stream, c->st, c->ptr(x), c->pitch, c->n, b, c->mb());
+    TRY(check_iters(iters));
+    if (nsteps < 0) return fail(FLUID_E_INVALID, "nsteps < 0");
+    for (int z = 0; z < nsteps; ++z) {
+        if (!(use_sources && z == 0)) TRY(zero_sources(c));
+        TRY(full_step(c, dt, diff, visc, iters));
+    }
     HIP_TRY(hipGetLastError());
     return FLUID_OK;
 }
 
-int fluid_op_add_source(fluid_ctx* c, int x, int s, float dt)
+int fluid_step(fluid_ctx* c, float dt, float diff, float visc, int iters, int nsteps, int use_sources) { return step_body(c, dt, diff, visc, iters, nsteps, use_sources); }
+
+int fluid_step_members(fluid_ctx* c, const float* dt, const float* diff, const float* visc, int iters, int nsteps, int use_sources)
+{
+    TRY(check_member_args(c, "fluid_step_members", {{"dt", dt}, {"diff", diff}, {"visc", visc}}));
+    if (c->members == 1) return fluid_step(c, dt[0], diff[0], visc[0], iters, nsteps, use_sources);
+    TRY(ensure_consts(c));
+    return step_body(c, {dt, c->members}, {diff, c->members}, {visc, c->members}, iters, nsteps, use_sources);
+}
+
+static int add_source_body(fluid_ctx* c, int x, int s, const MemberVal& dt)
 {
     TRY(check_ctx(c));
     TRY(check_fields(c, {x, s}));
@@ -2337,43 +2262,98 @@ int fluid_op_add_source(fluid_ctx* c, int x, int s, float dt)
     return FLUID_OK;
 }
 
-int fluid_op_jacobi_sweep(fluid_ctx* c, int b, int x, int x0, int out, float alpha, float beta)
+int fluid_op_add_source(fluid_ctx* c, int x, int s, float dt) { return add_source_body(c, x, s, dt); }
+
+int fluid_op_add_source_members(fluid_ctx* c, int x, int s, const float* dt)
+{
+    TRY(check_member_args(c, "fluid_op_add_source_members", {{"dt", dt}}));
+    if (c->members == 1) return fluid_op_add_source(c, x, s, dt[0]);
+    TRY(ensure_consts(c));
+    return add_source_body(c, x, s, {dt, c->members});
+}
+
+static int jacobi_sweep_body(fluid_ctx* c, int b, int x, int x0, int out, const MemberVal& alpha, const MemberVal& beta)
 {
     TRY(check_ctx(c));
     TRY(check_fields(c, {x, x0, out}));
-    if (b < 0 || b > 2) return fail(FLUID_E_INVALID, "b must be 0, 1 or 2");
+    TRY(check_b(b));
     if (out == x || out == x0) return fail(FLUID_E_INVALID, "jacobi_sweep: out must not alias an input");
     TRY(materialize(c, {x, x0}));
     TRY(need(c, {x}, 1));
+    const float2* mab = nullptr;
+    TRY(member_pairs(c, alpha, beta, &mab));
     const int v1 = c->variant == fluid::JACOBI_TB ? fluid::JACOBI_STREAM : c->variant;   // one sweep: nothing to block
-    fluid::launch_jacobi(c->stream, c->st, v1, c->ptr(x), c->ptr(x0), c->ptr(out), c->pitch, c->n, c->own0, c->own1, alpha, beta, b,
-                         c->mb());
+    fluid::launch_jacobi(c->stream, c->st, v1, c->ptr(x), c->ptr(x0), c->ptr(out), c->pitch, c->n, c->own0, c->own1, alpha.at(0), beta.at(0),
+                         b, c->mb(), mab);
     wrote(c, out, 0);
     HIP_TRY(hipGetLastError());
     return FLUID_OK;
 }
 
-int fluid_op_diffuse(fluid_ctx* c, int b, int x, int x0, float alpha, float beta, int iters)
+int fluid_op_jacobi_sweep(fluid_ctx* c, int b, int x, int x0, int out, float alpha, float beta) { return jacobi_sweep_body(c, b, x, x0, out, alpha, beta); }
+
+int fluid_op_jacobi_sweep_members(fluid_ctx* c, int b, int x, int x0, int out, const float* alpha, const float* beta)
+{
+    TRY(check_member_args(c, "fluid_op_jacobi_sweep_members", {{"alpha", alpha}, {"beta", beta}}));
+    if (c->members == 1) return fluid_op_jacobi_sweep(c, b, x, x0, out, alpha[0], beta[0]);
+    TRY(ensure_consts(c));
+    return jacobi_sweep_body(c, b, x, x0, out, {alpha, c->members}, {beta, c->members});
+}
+
+static int diffuse_body(fluid_ctx* c, int b, int x, int x0, const Coeffs& k, int iters)
 {
     TRY(check_ctx(c));
     TRY(check_fields(c, {x, x0}));
-    if (b < 0 || b > 2) return fail(FLUID_E_INVALID, "b must be 0, 1 or 2");
-    return op_diffuse(c, b, x, x0, alpha, beta, iters);
+    TRY(check_b(b));
+    return op_diffuse(c, b, x, x0, k, iters);
 }
 
-int fluid_op_advect(fluid_ctx* c, int b, int d, int d0, int u, int v, float dt)
+int fluid_op_diffuse(fluid_ctx* c, int b, int x, int x0, float alpha, float beta, int iters) { return diffuse_body(c, b, x, x0, {alpha, beta}, iters); }
+
+int fluid_op_diffuse_members(fluid_ctx* c, int b, int x, int x0, const float* alpha, const float* beta, int iters)
+{
+    TRY(check_member_args(c, "fluid_op_diffuse_members", {{"alpha", alpha}, {"beta", beta}}));
+    if (c->members == 1) return fluid_op_diffuse(c, b, x, x0, alpha[0], beta[0], iters);
+    TRY(ensure_consts(c));
+    return diffuse_body(c, b, x, x0, {{alpha, c->members}, {beta, c->members}}, iters);
+}
+
+static int advect_body(fluid_ctx* c, int b, int d, int d0, int u, int v, const MemberVal& dt)
 {
     TRY(check_ctx(c));
     TRY(check_fields(c, {d, d0, u, v}));
-    if (b < 0 || b > 2) return fail(FLUID_E_INVALID, "b must be 0, 1 or 2");
+    TRY(check_b(b));
     if (d == d0 || d == u || d == v) return fail(FLUID_E_INVALID, "advect: output must not alias an input");
     if (c->nranks > 1) {                  // on this call's bound alone (no early guess: it would change the exchanges issued)
         float vmax = 0.f;
         bool fetched = false;
         TRY(vmax_begin(c, u, v));
-        TRY(advect_rows(c, {d0}, dt * (float)c->n, 0, &vmax, &fetched));
+        TRY(advect_rows(c, {d0}, dt.at(0) * (float)c->n, 0, &vmax, &fetched));     // (slabs: one member)
     }
     TRY(op_advect(c, b, d, d0, u, v, dt));
+    HIP_TRY(hipGetLastError());
+    return FLUID_OK;
+}
+
+int fluid_op_advect(fluid_ctx* c, int b, int d, int d0, int u, int v, float dt) { return advect_body(c, b, d, d0, u, v, dt); }
+
+int fluid_op_advect_members(fluid_ctx* c, int b, int d, int d0, int u, int v, const float* dt)
+{
+    TRY(check_member_args(c, "fluid_op_advect_members", {{"dt", dt}}));
+    if (c->members == 1) return fluid_op_advect(c, b, d, d0, u, v, dt[0]);
+    TRY(ensure_consts(c));
+    return advect_body(c, b, d, d0, u, v, {dt, c->members});
+}
+
+// ---- operators ---------------------------------------------------------------
+int fluid_op_set_bnd(fluid_ctx* c, int b, int x)
+{
+    TRY(check_ctx(c));
+    TRY(check_fields(c, {x}));
+    TRY(check_b(b));
+    if (c->nranks != 1) return fail(FLUID_E_INVALID, "fluid_op_set_bnd is a whole-grid operator (1 GPU)");
+    TRY(materialize(c, x));
+    fluid::launch_set_bnd(c->stream, c->st, c->ptr(x), c->pitch, c->n, b, c->mb());
     HIP_TRY(hipGetLastError());
     return FLUID_OK;
 }
@@ -2497,7 +2477,7 @@ int fluid_residual_members(fluid_ctx* c, int x, int x0, const float* alpha, cons
     TRY(ensure_member_results(c));
     TRY(materialize(c, {x, x0}));
     const float2* mab = nullptr;
-    TRY(member_pairs(c, alpha, beta, &mab));
+    TRY(member_pairs(c, {alpha, c->members}, {beta, c->members}, &mab));
     HIP_TRY(hipMemsetAsync(c->red.d_max, 0, (size_t)c->members * sizeof(unsigned), c->stream));
     fluid::launch_residual(c->stream, c->st, c->ptr(x), c->ptr(x0), c->pitch, c->n, c->own0, c->own1, alpha[0], beta[0], c->red.d_max,
                            c->mb(), /*rstride=*/1, mab);
@@ -2622,7 +2602,7 @@ int fluid_op_diffuse_tol(fluid_ctx* c, int b, int x, int x0, float alpha, float 
     // (a residual-terminated solve would make every member's sweep count depend on the others)
     TRY(fluid_detail::refuse_ensemble(c, "fluid_op_diffuse_tol"));
     TRY(check_fields(c, {x, x0}));
-    if (b < 0 || b > 2) return fail(FLUID_E_INVALID, "b must be 0, 1 or 2");
+    TRY(check_b(b));
     if (check_every < 2 || (check_every & 1) || max_iters < 0 || !(tol >= 0.f))
         return fail(FLUID_E_INVALID, "diffuse_tol: check_every must be even and >= 2, max_iters >= 0, tol >= 0");
     int done = 0;
@@ -2631,7 +2611,7 @@ int fluid_op_diffuse_tol(fluid_ctx* c, int b, int x, int x0, float alpha, float 
     while (res > tol && done < max_iters) {
         const int blk = std::min(check_every, (max_iters - done) & ~1);
         if (blk <= 0) break;
-        TRY(op_diffuse(c, b, x, x0, alpha, beta, blk));
+        TRY(op_diffuse(c, b, x, x0, {alpha, beta}, blk));
         done += blk;
         TRY(fluid_residual(c, x, x0, alpha, beta, &res));
     }
@@ -2664,7 +2644,7 @@ int step_src(int N, float dt, float diff, float visc, int iters, float* u, float
              float* v_prev, float* dens_prev)
 {
     if (!u || !v || !dens || !u_prev || !v_prev || !dens_prev) return fail(FLUID_E_INVALID, "step_src: null field");
-    if (iters < 0 || (iters & 1)) return fail(FLUID_E_INVALID, "sweep count must be even and >= 0 (got %d)", iters);
+    TRY(check_iters(iters));
     fluid_ctx* c;
     TRY(cached_ctx(N, &c));
     float* host[6] = {u, v, dens, u_prev, v_prev, dens_prev};

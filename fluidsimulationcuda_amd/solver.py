@@ -170,34 +170,27 @@ class FluidSolver:
     def set_bnd(self, b, x):
         capi.check(capi.lib().fluid_op_set_bnd(self._h, b, _fid(x)))
 
-    def add_source(self, x, s, dt=DT):
-        mv = member_values(self.members, dt=dt)
+    def _call(self, name, before, params, after=()):
+        """fluid_<name>(handle, *before, <params>, *after) when every parameter is a scalar; as soon as one is a sequence,
+        fluid_<name>_members with each parameter as an array of one value per member (member_values)"""
+        mv = member_values(self.members, **params)
         if mv is None:
-            capi.check(capi.lib().fluid_op_add_source(self._h, _fid(x), _fid(s), dt))
+            fn, values = getattr(capi.lib(), "fluid_" + name), params.values()
         else:
-            capi.check(capi.lib().fluid_op_add_source_members(self._h, _fid(x), _fid(s), _mf(mv["dt"])))
+            fn, values = getattr(capi.lib(), "fluid_" + name + "_members"), [_mf(a) for a in mv.values()]
+        capi.check(fn(self._h, *before, *values, *after))
+
+    def add_source(self, x, s, dt=DT):
+        self._call("op_add_source", (_fid(x), _fid(s)), dict(dt=dt))
 
     def jacobi_sweep(self, b, x, x0, out, alpha, beta):
-        mv = member_values(self.members, alpha=alpha, beta=beta)
-        if mv is None:
-            capi.check(capi.lib().fluid_op_jacobi_sweep(self._h, b, _fid(x), _fid(x0), _fid(out), alpha, beta))
-        else:
-            capi.check(capi.lib().fluid_op_jacobi_sweep_members(self._h, b, _fid(x), _fid(x0), _fid(out), _mf(mv["alpha"]),
-                                                                _mf(mv["beta"])))
+        self._call("op_jacobi_sweep", (b, _fid(x), _fid(x0), _fid(out)), dict(alpha=alpha, beta=beta))
 
     def diffuse(self, b, x, x0, alpha, beta, iters=ITERS):
-        mv = member_values(self.members, alpha=alpha, beta=beta)
-        if mv is None:
-            capi.check(capi.lib().fluid_op_diffuse(self._h, b, _fid(x), _fid(x0), alpha, beta, iters))
-        else:
-            capi.check(capi.lib().fluid_op_diffuse_members(self._h, b, _fid(x), _fid(x0), _mf(mv["alpha"]), _mf(mv["beta"]), iters))
+        self._call("op_diffuse", (b, _fid(x), _fid(x0)), dict(alpha=alpha, beta=beta), (iters,))
 
     def advect(self, b, d, d0, u, v, dt=DT):
-        mv = member_values(self.members, dt=dt)
-        if mv is None:
-            capi.check(capi.lib().fluid_op_advect(self._h, b, _fid(d), _fid(d0), _fid(u), _fid(v), dt))
-        else:
-            capi.check(capi.lib().fluid_op_advect_members(self._h, b, _fid(d), _fid(d0), _fid(u), _fid(v), _mf(mv["dt"])))
+        self._call("op_advect", (b, _fid(d), _fid(d0), _fid(u), _fid(v)), dict(dt=dt))
 
     def computeDivergenceAndPressure(self, u, v, p, div):
         capi.check(capi.lib().fluid_op_divergence(self._h, _fid(u), _fid(v), _fid(p), _fid(div)))
@@ -207,28 +200,15 @@ class FluidSolver:
 
     def vel_step(self, visc=VIS, dt=DT, iters=ITERS):
         """vel_step(u, v, u_prev, v_prev, visc) on the resident fields."""
-        mv = member_values(self.members, dt=dt, visc=visc)
-        if mv is None:
-            capi.check(capi.lib().fluid_vel_step(self._h, dt, visc, iters))
-        else:
-            capi.check(capi.lib().fluid_vel_step_members(self._h, _mf(mv["dt"]), _mf(mv["visc"]), iters))
+        self._call("vel_step", (), dict(dt=dt, visc=visc), (iters,))
 
     def dens_step(self, diff=DIFF, dt=DT, iters=ITERS):
         """dens_step(dens, dens_prev, u, v, diff) on the resident fields."""
-        mv = member_values(self.members, dt=dt, diff=diff)
-        if mv is None:
-            capi.check(capi.lib().fluid_dens_step(self._h, dt, diff, iters))
-        else:
-            capi.check(capi.lib().fluid_dens_step_members(self._h, _mf(mv["dt"]), _mf(mv["diff"]), iters))
+        self._call("dens_step", (), dict(dt=dt, diff=diff), (iters,))
 
     def step(self, nsteps=1, use_sources=False, dt=DT, diff=DIFF, visc=VIS, iters=ITERS):
         """nsteps bodies of the reference's main loop (FluidSequential.c:289-312)."""
-        mv = member_values(self.members, dt=dt, diff=diff, visc=visc)
-        if mv is None:
-            capi.check(capi.lib().fluid_step(self._h, dt, diff, visc, iters, nsteps, 1 if use_sources else 0))
-        else:
-            capi.check(capi.lib().fluid_step_members(self._h, _mf(mv["dt"]), _mf(mv["diff"]), _mf(mv["visc"]), iters, nsteps,
-                                                     1 if use_sources else 0))
+        self._call("step", (), dict(dt=dt, diff=diff, visc=visc), (iters, nsteps, 1 if use_sources else 0))
 
     # -- diagnostics / tuning
     def residual(self, x, x0, alpha, beta):

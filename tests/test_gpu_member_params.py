@@ -341,6 +341,60 @@ def test_member_upload_against_per_member_operator_marks(oracle):
             compare_all(s, models, "upload of member 1's %s" % target)
 
 
+@pytest.mark.parametrize("variant", [3, 0])
+def test_scalar_and_member_calls_interleave(oracle, variant):
+    """Scalar and per-member calls on the same ensemble, crossing where one kind leaves something owed and the other takes it
+    over: (a) a per-member pending increment consumed by a scalar solve, and one settled by a reader and then overwritten by
+    a scalar writer; (b) the mirror image -- uniform increments consumed by per-member solves -- and then a per-member step
+    followed by a scalar one, so that what the per-member step left per member must not outlive the scalar step's marks.
+    The fields are all -0 (dens_prev: stale memory behind the zero mark), so each increment's sign shows."""
+    n, members, iters = 30, 3, 8
+    a, b = oracle.coefficients(n, 0.016, 0.1)
+    dts = np.array([0.016, -0.5, -0.0], F32)
+    ma, mb = [a, a, 1.0], [b, b, 4.0]
+    P = (dts, np.array([0.1, 0.05, 0.2], F32), np.array([0.0025, 0.3, 0.01], F32))
+
+    def fresh():
+        fields = [{k: np.full((n + 2, n + 2), -0.0, F32) for k in NAMES} for _ in range(members)]
+        for f in fields:
+            f["dens_prev"][...] = 0.75
+        return fields, [Model(oracle, f) for f in fields]
+
+    def operators(s, models, dt, dt5, alpha, beta):
+        """dt, dt5, alpha, beta: a scalar or one value per member each"""
+        s.computeDivergenceAndPressure("u", "v", "dens_prev", "v_prev")
+        s.add_source("dens", "dens_prev", dt)
+        s.diffuse(0, "u_prev", "dens", alpha, beta, iters)
+        s.add_source("v", "dens_prev", dt)
+        s.add_source("v", "u", dt5)
+        s.jacobi_sweep(1, "v", "u", "dens", alpha, beta)
+        for m, mod in enumerate(models):
+            f = mod.f
+            d, d5, al, be = (float(np.broadcast_to(np.asarray(x, F32), (members,))[m]) for x in (dt, dt5, alpha, beta))
+            oracle.divergence(f["u"], f["v"], f["dens_prev"], f["v_prev"])
+            oracle.add_source(f["dens"], f["dens_prev"], d)
+            oracle.diffuse(0, f["u_prev"], f["dens"], al, be, iters)
+            oracle.add_source(f["v"], f["dens_prev"], d)
+            oracle.add_source(f["v"], f["u"], d5)
+            oracle.jacobi_sweep(1, f["v"], f["u"], f["dens"], al, be)
+
+    fields, models = fresh()
+    with solver(n, members, variant=variant) as s:
+        upload_all(s, fields)
+        operators(s, models, dts, 0.25, a, b)
+        compare_all(s, models, "(a) per-member state, scalar consumers, variant %d" % variant)
+    fields, models = fresh()
+    with solver(n, members, variant=variant) as s:
+        upload_all(s, fields)
+        operators(s, models, 0.016, dts, ma, mb)
+        compare_all(s, models, "(b) uniform state, per-member consumers, variant %d" % variant)
+        run_members(s, models, P, iters, "(b) then a per-member step", sequence=(("step", False),))
+        s.step(1, dt=0.016, diff=0.1, visc=0.0025, iters=iters)
+        for mod in models:
+            mod.step(False, 0.016, 0.1, 0.0025, iters)
+        compare_all(s, models, "(b) then a scalar step, variant %d" % variant)
+
+
 # ---- 7. isolation -------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("variant", [3, 0])
 def test_a_member_that_divides_by_zero_stays_alone(oracle, variant):
