@@ -54,6 +54,13 @@ class Timing(C.Structure):
                 ("pressure_ms", C.c_double), ("pressure_sweeps", C.c_longlong)]
 
 
+class RunPlan(C.Structure):
+    """fluid_run_plan: a run of nsteps steps with optional forcing (sources) and optional recording (snapshots)"""
+    _fields_ = [("iters", C.c_int), ("nsteps", C.c_int), ("use_sources", C.c_int), ("sources", C.c_void_p),
+                ("every", C.c_int), ("fields", C.POINTER(C.c_int)), ("nfields", C.c_int),
+                ("snapshots", C.c_void_p), ("capacity", C.c_size_t)]
+
+
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int,
                           C.POINTER(C.c_float))
 
@@ -110,6 +117,12 @@ SIGNATURES = {
     "fluid_member_moments": [_ctx, _i, C.POINTER(C.c_double), C.POINTER(C.c_double)],
     "fluid_ensemble_stats": [_ctx, _i, _MF, _MF],
     "fluid_ensemble_stats_ptr": [_ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)],
+    "fluid_pack_members": [_ctx, _i, _i, _i, C.c_void_p, C.c_size_t],
+    "fluid_unpack_members": [_ctx, _i, _i, _i, C.c_void_p, C.c_size_t],
+    "fluid_download_members": [_ctx, _i, _MF],
+    "fluid_upload_members": [_ctx, _i, _MF],
+    "fluid_run": [_ctx, _f, _f, _f, C.POINTER(RunPlan), C.POINTER(_i)],
+    "fluid_run_members": [_ctx, _MF, _MF, _MF, C.POINTER(RunPlan), C.POINTER(_i)],
     "fluid_set_jacobi_variant": [_ctx, _i],
     "fluid_division_mode": [_ctx, _f, _f, C.POINTER(_i)],
     "fluid_autotune_pending": [_ctx, C.POINTER(_i)],

@@ -108,6 +108,14 @@ struct EnsembleReduce {
     bool have_stats = false;              // a fluid_ensemble_stats has filled them
 };
 
+// The bulk host copies (fluid_download_members / fluid_upload_members) go through a dense float staging buffer on the
+// device: library-owned, outside the arena, allocated by the first such call and freed in fluid_destroy (fluid_solver.hip:
+// ensure_stage).  It holds `members` whole members; a call moves its members group by group in stream order.
+struct MemberStage {
+    float* dev = nullptr;
+    int members = 0;
+};
+
 struct fluid_ctx {
     int n = 0, w = 0, pitch = 0;
     size_t field_floats = 0;
@@ -140,6 +148,7 @@ struct fluid_ctx {
     float* d_partials = nullptr;          // slabs: per-block maxima of the gradient subtraction (launch_subtract_gradient)
     ConstRing consts;                     // tables of per-member constants (fluid_*_members)
     EnsembleReduce red;                   // results and scratch of the ensemble diagnostics
+    MemberStage stage;                    // device staging of the bulk host copies
     unsigned int* tiles = nullptr;        // 3 x members x tile_rows x tile_pitch words: |x0| minima per tile for division mode 3
     unsigned int* h_scalar = nullptr;     // pinned host mirror
     hipEvent_t scalar_ready = nullptr;    // recorded behind the scalar's device-to-host copy

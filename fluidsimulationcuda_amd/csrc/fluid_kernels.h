@@ -156,5 +156,10 @@ void launch_member_moments(hipStream_t s, int st, const void* x, int pitch, int 
 // Per cell over the members (every row and column, ghosts included): mean and population variance as float fields in
 // the layout of a field; their pad columns are not written.  One launch; the members are walked inside the kernel.
 void launch_ensemble_stats(hipStream_t s, int st, const void* x, int pitch, int n, Members mb, float* mean, float* var);
+// All mb.count members of a field (x: the first of them) <-> a dense float array, member m of it m * dstride floats behind
+// `dense`, each the (n + 2)^2 row-major array with its ghost ring.  One launch each; pad columns are not touched.
+// pack: dense = widen(x) * inv (fp16 storage; fp32 copies the words); unpack: x = narrow(dense), to nearest even.
+void launch_pack_members(hipStream_t s, int st, const void* x, int pitch, int n, Members mb, float inv, float* dense, size_t dstride);
+void launch_unpack_members(hipStream_t s, int st, void* x, int pitch, int n, Members mb, const float* dense, size_t dstride);
 
 }  // namespace fluid

@@ -1839,6 +1839,113 @@ __global__ __launch_bounds__(256) void k_ensemble_stats(const S* __restrict__ x,
 }
 
 // ---------------------------------------------------------------------------
+// moving whole ensembles: all members of a field <-> a dense float array (include/fluid_amd.h "moving ensembles").
+// The dense side is one member after the other, each the reference's (n + 2)^2 row-major array, member m starting
+// m * dstride floats behind `dense`: always float, aligned to 4 bytes only, and the offset of a row within 16 bytes
+// changes from row to row when (n + 2) % 4 != 0.  The field side is cut into the vectors of k_ensemble_stats: one lane
+// per VW = 4 (fp16: 8) columns, vector v of a row covering columns 1 + VW * (v - 1) .. VW * v, so a field-side access is
+// 16 aligned bytes; vector 0 is ghost column 0 alone, and it and the last vector(s) of a row touch their valid columns
+// one by one on both sides: pad columns are neither read as data nor written.  On the dense side a whole vector is VW / 4
+// accesses of 16 bytes that promise 4-byte alignment only (global memory takes them; consecutive lanes, consecutive
+// bytes of the row).  Grid (blocks over the (n + 2) * vecs vectors of a member, members): the member base on both sides
+// is 64-bit scalar arithmetic per block -- members * dstride * 4 may pass 4 GiB -- and the offsets within a member have
+// the index type I (narrow_index).  No LDS, no atomics.
+// pack: dense = widen(x) * inv for fp16 storage (inv = 1 / FieldState::fscale, a power of two: the multiplication a
+// download does on the host, exact); fp32 storage moves the words as they are.  unpack: x = narrow(dense), one
+// round-to-nearest-even behind the empty-asm fence (st1).
+// ---------------------------------------------------------------------------
+typedef float dense4_t __attribute__((ext_vector_type(4), aligned(4)));
+
+template <typename S, typename I>
+__device__ __forceinline__ bool member_vector(int pitch, int n, int vecs, I* at, I* dat, int* valid)
+{
+    constexpr int VW = StatsVec<S>::VW;
+    const unsigned t = blockIdx.x * 256u + threadIdx.x;          // (n + 2) * vecs < 2^32 for every N the library accepts
+    if (t >= (unsigned)(n + 2) * (unsigned)vecs) return false;
+    const int row = (int)(t / (unsigned)vecs), v = (int)(t % (unsigned)vecs);
+    const int c0 = 1 + VW * (v - 1);                     // first column of this lane's vector (vector 0: 1 - VW)
+    int ok = 0;
+#pragma unroll
+    for (int e = 0; e < VW; ++e)
+        if (c0 + e >= 0 && c0 + e <= n + 1) ok |= 1 << e;
+    *valid = ok;
+    // element 0 of the vector on either side; for vector 0 that lies before the row (only element VW - 1 is touched)
+    *at = (I)row * (I)pitch + (I)(XOFF + c0);
+    *dat = (I)row * (I)(n + 2) + (I)c0;        // (wraps for vector 0 of row 0: c0 < 0; adding e = VW - 1 wraps it back)
+    return true;
+}
+
+template <typename S, typename I>
+__global__ __launch_bounds__(256) void k_pack_members(const S* __restrict__ x, int pitch, int n, size_t ms, int vecs, float inv,
+                                                      float* __restrict__ dense, size_t dstride)
+{
+    constexpr int VW = StatsVec<S>::VW;
+    I at, dat;
+    int valid;
+    if (!member_vector<S, I>(pitch, n, vecs, &at, &dat, &valid)) return;
+    x += blockIdx.y * ms;
+    dense += blockIdx.y * dstride;
+    if (valid == (1 << VW) - 1) {
+        float f[VW];
+        if constexpr (sizeof(S) == 4) {
+            const float4 a = *reinterpret_cast<const float4*>(x + at);
+            f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w;
+        } else {
+            typedef half_t half8_t __attribute__((ext_vector_type(8)));
+            const half8_t h = *reinterpret_cast<const half8_t*>(x + at);
+#pragma unroll
+            for (int e = 0; e < VW; ++e) f[e] = keep_f32((float)h[e]) * inv;
+        }
+#pragma unroll
+        for (int e = 0; e < VW; e += 4) {
+            dense4_t d;
+            d.x = f[e]; d.y = f[e + 1]; d.z = f[e + 2]; d.w = f[e + 3];
+            *reinterpret_cast<dense4_t*>(dense + (I)(dat + (I)e)) = d;
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < VW; ++e)
+            if ((valid >> e) & 1) {
+                if constexpr (sizeof(S) == 4) dense[(I)(dat + (I)e)] = x[(I)(at + (I)e)];
+                else dense[(I)(dat + (I)e)] = ld1(x + (I)(at + (I)e)) * inv;
+            }
+    }
+}
+
+template <typename S, typename I>
+__global__ __launch_bounds__(256) void k_unpack_members(S* __restrict__ x, int pitch, int n, size_t ms, int vecs,
+                                                        const float* __restrict__ dense, size_t dstride)
+{
+    constexpr int VW = StatsVec<S>::VW;
+    I at, dat;
+    int valid;
+    if (!member_vector<S, I>(pitch, n, vecs, &at, &dat, &valid)) return;
+    x += blockIdx.y * ms;
+    dense += blockIdx.y * dstride;
+    if (valid == (1 << VW) - 1) {
+        float f[VW];
+#pragma unroll
+        for (int e = 0; e < VW; e += 4) {
+            const dense4_t d = *reinterpret_cast<const dense4_t*>(dense + (I)(dat + (I)e));
+            f[e] = d.x; f[e + 1] = d.y; f[e + 2] = d.z; f[e + 3] = d.w;
+        }
+        if constexpr (sizeof(S) == 4) {
+            *reinterpret_cast<float4*>(x + at) = make_float4(f[0], f[1], f[2], f[3]);
+        } else {
+            typedef half_t half8_t __attribute__((ext_vector_type(8)));
+            half8_t h;
+#pragma unroll
+            for (int e = 0; e < VW; ++e) h[e] = (half_t)keep_f32(f[e]);
+            *reinterpret_cast<half8_t*>(x + at) = h;
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < VW; ++e)
+            if ((valid >> e) & 1) st1(x + (I)(at + (I)e), dense[(I)(dat + (I)e)]);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // launch wrappers (host).  Shapes are validated by the caller (fluid_solver).
 // `st` selects the field storage type the untyped pointers refer to.
 // ---------------------------------------------------------------------------
@@ -2094,6 +2201,29 @@ void launch_ensemble_stats(hipStream_t s, int st, const void* x, int pitch, int 
     const unsigned total = (unsigned)(n + 2) * (unsigned)vecs;
     FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_ensemble_stats<S>, dim3(cdiv(total, 256)), dim3(256), 0, s, (const S*)x, pitch, n, mb.stride,
                                             mb.count, vecs, mean, var));
+}
+
+// vectors per row of the scheme of k_ensemble_stats / k_pack_members: ghost column 0, then columns 1 .. n + 1 in whole vectors
+static inline int row_vectors(int st, int n)
+{
+    const int vw = 16 / (int)storage_bytes(st);
+    return 1 + (n + 1 + vw - 1) / vw;
+}
+
+void launch_pack_members(hipStream_t s, int st, const void* x, int pitch, int n, Members mb, float inv, float* dense, size_t dstride)
+{
+    const int vecs = row_vectors(st, n);
+    const dim3 grid(cdiv((unsigned)(n + 2) * (unsigned)vecs, 256), mb.count);
+    FLUID_BY_STORAGE_INDEX(st, pitch, n, hipLaunchKernelGGL((k_pack_members<S, I>), grid, dim3(256), 0, s, (const S*)x, pitch, n, mb.stride,
+                                                            vecs, inv, dense, dstride));
+}
+
+void launch_unpack_members(hipStream_t s, int st, void* x, int pitch, int n, Members mb, const float* dense, size_t dstride)
+{
+    const int vecs = row_vectors(st, n);
+    const dim3 grid(cdiv((unsigned)(n + 2) * (unsigned)vecs, 256), mb.count);
+    FLUID_BY_STORAGE_INDEX(st, pitch, n, hipLaunchKernelGGL((k_unpack_members<S, I>), grid, dim3(256), 0, s, (S*)x, pitch, n, mb.stride, vecs,
+                                                            dense, dstride));
 }
 
 }  // namespace fluid

@@ -1858,6 +1858,7 @@ int fluid_destroy(fluid_ctx* c)
     if (c->red.host) (void)hipHostFree(c->red.host);
     if (c->red.d_mean) (void)hipFree(c->red.d_mean);
     if (c->red.d_var) (void)hipFree(c->red.d_var);
+    if (c->stage.dev) (void)hipFree(c->stage.dev);
     if (c->d_partials) (void)hipFree(c->d_partials);
     if (c->scalar_ready) (void)hipEventDestroy(c->scalar_ready);
     if (c->own_arena && c->arena) (void)hipFree(c->arena);
@@ -2552,6 +2553,241 @@ int fluid_ensemble_stats_ptr(fluid_ctx* c, void** mean_dev, void** variance_dev)
     if (mean_dev) *mean_dev = c->red.d_mean;
     if (variance_dev) *variance_dev = c->red.d_var;
     return FLUID_OK;
+}
+
+// ---- moving whole ensembles: device pack / unpack, bulk host copies, recorded runs ----------------------------
+// (include/fluid_amd.h "moving ensembles".)  One launch moves all members of a field -- or a range of them -- between the
+// library's layout and a dense float array on the device; the bulk host copies and fluid_run are built on it.  The
+// launches belong to none of the timing categories.  Every refusal is found before anything is launched or changed.
+static size_t member_cells(const fluid_ctx* c) { return (size_t)c->w * (size_t)c->w; }
+
+// bytes from the first float of member 0 to the end of member count - 1 in a dense array; false: not representable
+static bool dense_span(size_t cells, int count, size_t stride, size_t* bytes)
+{
+    size_t b = 0;
+    if (count < 1) { *bytes = 0; return true; }
+    if (__builtin_mul_overflow((size_t)(count - 1), stride, &b) || __builtin_add_overflow(b, cells, &b) ||
+        __builtin_mul_overflow(b, sizeof(float), &b))
+        return false;
+    *bytes = b;
+    return true;
+}
+
+// `p` is device memory of the context's device and the `bytes` behind it lie inside one allocation: asked on the host,
+// so that a wrong pointer never reaches a kernel
+static int check_device_span(const fluid_ctx* c, const char* call, const char* name, const void* p, size_t bytes)
+{
+    hipPointerAttribute_t a, own;
+    std::memset(&a, 0, sizeof a);
+    std::memset(&own, 0, sizeof own);
+    hipError_t e = hipPointerGetAttributes(&a, p);
+    if (e != hipSuccess || a.type != hipMemoryTypeDevice) {
+        (void)hipGetLastError();
+        return fail(FLUID_E_INVALID, "%s: `%s` (%p) is not device memory", call, name, p);
+    }
+    e = hipPointerGetAttributes(&own, c->arena);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(FLUID_E_HIP, "%s: hipPointerGetAttributes(arena): %s", call, hipGetErrorString(e));
+    }
+    if (a.device != own.device)
+        return fail(FLUID_E_INVALID, "%s: `%s` (%p) is memory of device %d, this context's fields are on device %d", call, name, p, a.device,
+                    own.device);
+    void* base = nullptr;
+    size_t size = 0;
+    e = hipMemGetAddressRange(reinterpret_cast<hipDeviceptr_t*>(&base), &size, reinterpret_cast<hipDeviceptr_t>(const_cast<void*>(p)));
+    if (e != hipSuccess || !base) {
+        (void)hipGetLastError();
+        return fail(FLUID_E_INVALID, "%s: `%s` (%p): no device allocation found around it", call, name, p);
+    }
+    const size_t off = (size_t)(static_cast<const char*>(p) - static_cast<const char*>(base));
+    if (off > size || bytes > size - off)
+        return fail(FLUID_E_INVALID, "%s: `%s` (%p) needs %zu bytes, its allocation ends %zu bytes behind it", call, name, p, bytes,
+                    off > size ? (size_t)0 : size - off);
+    if (((uintptr_t)p & 3u) != 0) return fail(FLUID_E_INVALID, "%s: `%s` (%p) is not aligned to 4 bytes", call, name, p);
+    return FLUID_OK;
+}
+
+// first / count / member_stride as a pack or unpack call means them (0: to the end; 0: dense), and the device array behind them
+static int check_member_move(const fluid_ctx* c, const char* call, int field, int first, int* count, const void* dev, size_t* stride)
+{
+    if (!c->valid_field(field)) return fail(FLUID_E_INVALID, "%s: bad field id %d", call, field);
+    TRY(refuse_slabs(c, call));
+    if (first < 0 || first > c->members || *count < 0 || *count > c->members - first)
+        return fail(FLUID_E_INVALID, "%s: first %d, count %d outside the %d members of this context", call, first, *count, c->members);
+    if (*count == 0) *count = c->members - first;
+    const size_t cells = member_cells(c);
+    if (*stride == 0) *stride = cells;
+    if (*stride < cells) return fail(FLUID_E_INVALID, "%s: member_stride %zu is below (N + 2)^2 = %zu", call, *stride, cells);
+    size_t bytes = 0;
+    if (!dense_span(cells, *count, *stride, &bytes)) return fail(FLUID_E_INVALID, "%s: member_stride %zu is too large", call, *stride);
+    return check_device_span(c, call, "the dense array", dev, bytes);
+}
+
+// as fluid_download_member sees the field: the lazy state settled, a scale kept and divided back on the way out
+static int pack_range(fluid_ctx* c, int field, int first, int count, float* dst, size_t stride)
+{
+    if (count == 0) return FLUID_OK;
+    const float inv = c->st != fluid::STORAGE_F32 ? 1.0f / c->field[field].fscale : 1.0f;
+    TRY(materialize(c, field, /*keep_scale=*/inv != 1.0f));
+    const char* x = static_cast<const char*>(c->ptr(field)) + (size_t)first * c->field_bytes;
+    fluid::launch_pack_members(c->stream, c->st, x, c->pitch, c->n, {count, c->field_floats}, inv, dst, stride);
+    HIP_TRY(hipGetLastError());
+    return FLUID_OK;
+}
+
+// the launch alone: what it means for the field's record is the caller's business (unpack_range, fluid_upload_members)
+static int unpack_launch(fluid_ctx* c, int field, int first, int count, const float* src, size_t stride)
+{
+    char* x = static_cast<char*>(c->ptr(field)) + (size_t)first * c->field_bytes;
+    fluid::launch_unpack_members(c->stream, c->st, x, c->pitch, c->n, {count, c->field_floats}, src, stride);
+    HIP_TRY(hipGetLastError());
+    return FLUID_OK;
+}
+
+// All members: the field is replaced -- nothing is settled first, whatever it owed itself is dropped (wrote).  A proper
+// sub-range: the field is settled for all members first, as by fluid_upload_member (the marks are shared, and the members
+// outside the range must end up holding what the marks stood for), then the range is overwritten.
+static int unpack_range(fluid_ctx* c, int field, int first, int count, const float* src, size_t stride)
+{
+    if (count == 0) return FLUID_OK;
+    const bool all = first == 0 && count == c->members;
+    if (!all) TRY(materialize(c, field));
+    TRY(unpack_launch(c, field, first, count, src, stride));
+    if (all) wrote(c, field, kEverywhere);
+    return FLUID_OK;
+}
+
+int fluid_pack_members(fluid_ctx* c, int field, int first, int count, void* dst_dev, size_t member_stride)
+{
+    if (!dst_dev) return fail(FLUID_E_INVALID, "fluid_pack_members: null device pointer `dst_dev`");
+    if (!c) return fail(FLUID_E_INVALID, "fluid_pack_members: null context");
+    TRY(check_member_move(c, "fluid_pack_members", field, first, &count, dst_dev, &member_stride));
+    return pack_range(c, field, first, count, static_cast<float*>(dst_dev), member_stride);
+}
+
+int fluid_unpack_members(fluid_ctx* c, int field, int first, int count, const void* src_dev, size_t member_stride)
+{
+    if (!src_dev) return fail(FLUID_E_INVALID, "fluid_unpack_members: null device pointer `src_dev`");
+    if (!c) return fail(FLUID_E_INVALID, "fluid_unpack_members: null context");
+    TRY(check_member_move(c, "fluid_unpack_members", field, first, &count, src_dev, &member_stride));
+    return unpack_range(c, field, first, count, static_cast<const float*>(src_dev), member_stride);
+}
+
+// The staging buffer of the bulk host copies: g = max(1, min(M, 64 MiB / member bytes)) dense members.  The 64 MiB is a
+// choice, not a measurement -- a buffer that fits the Infinity Cache beside the fields a group is packed from;
+// tools/ensemble_io_timing.py records what the bulk copies cost with it.
+static int ensure_stage(fluid_ctx* c, const char* call)
+{
+    if (c->stage.dev) return FLUID_OK;
+    const size_t member_bytes = member_cells(c) * sizeof(float);
+    const int g = (int)std::max<size_t>(1, std::min<size_t>((size_t)c->members, ((size_t)64 << 20) / member_bytes));
+    float* dev = nullptr;
+    const hipError_t e = hipMalloc((void**)&dev, (size_t)g * member_bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(e == hipErrorOutOfMemory ? FLUID_E_NOMEM : FLUID_E_HIP, "%s: allocating a staging buffer of %zu bytes: %s", call,
+                    (size_t)g * member_bytes, hipGetErrorString(e));
+    }
+    c->stage.dev = dev;
+    c->stage.members = g;
+    return FLUID_OK;
+}
+
+int fluid_download_members(fluid_ctx* c, int field, float* host)
+{
+    if (!host) return fail(FLUID_E_INVALID, "fluid_download_members: null host pointer");
+    if (!c) return fail(FLUID_E_INVALID, "fluid_download_members: null context");
+    if (!c->valid_field(field)) return fail(FLUID_E_INVALID, "fluid_download_members: bad field id %d", field);
+    TRY(refuse_slabs(c, "fluid_download_members"));
+    TRY(ensure_stage(c, "fluid_download_members"));
+    const size_t cells = member_cells(c);
+    for (int first = 0; first < c->members; first += c->stage.members) {      // groups in stream order: the buffer is reused
+        const int count = std::min(c->stage.members, c->members - first);
+        TRY(pack_range(c, field, first, count, c->stage.dev, cells));
+        HIP_TRY(hipMemcpyAsync(host + (size_t)first * cells, c->stage.dev, (size_t)count * cells * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return FLUID_OK;
+}
+
+int fluid_upload_members(fluid_ctx* c, int field, const float* host)
+{
+    if (!host) return fail(FLUID_E_INVALID, "fluid_upload_members: null host pointer");
+    if (!c) return fail(FLUID_E_INVALID, "fluid_upload_members: null context");
+    if (!c->valid_field(field)) return fail(FLUID_E_INVALID, "fluid_upload_members: bad field id %d", field);
+    TRY(refuse_slabs(c, "fluid_upload_members"));
+    TRY(ensure_stage(c, "fluid_upload_members"));
+    const size_t cells = member_cells(c);
+    for (int first = 0; first < c->members; first += c->stage.members) {
+        const int count = std::min(c->stage.members, c->members - first);
+        HIP_TRY(hipMemcpyAsync(c->stage.dev, host + (size_t)first * cells, (size_t)count * cells * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        TRY(unpack_launch(c, field, first, count, c->stage.dev, cells));
+    }
+    wrote(c, field, kEverywhere);              // every member was replaced: an unpack of all members, in groups
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return FLUID_OK;
+}
+
+// fluid_run / fluid_run_members: one body (see "calls whose physical parameters are one value for everybody or one per
+// member").  Defined as the loop of existing calls it replaces: per step the three source blocks unpacked and a step that
+// consumes them, or fluid_step's rule; after every `every`-th step each listed field packed into its snapshot slot.
+static int run_body(fluid_ctx* c, const char* call, const MemberVal& dt, const MemberVal& diff, const MemberVal& visc, const fluid_run_plan* p,
+                    int* snapshots_written)
+{
+    TRY(refuse_slabs(c, call));
+    if (p->iters < 0 || (p->iters & 1)) return fail(FLUID_E_INVALID, "%s: sweep count must be even and >= 0 (got %d)", call, p->iters);
+    if (p->nsteps < 0) return fail(FLUID_E_INVALID, "%s: nsteps < 0", call);
+    if (p->every < 0) return fail(FLUID_E_INVALID, "%s: every < 0", call);
+    const size_t cells = member_cells(c), block = (size_t)c->members * cells;
+    const int snapshots = p->every ? p->nsteps / p->every : 0;
+    if (p->every > 0) {
+        if (p->nfields < 1 || p->nfields > FLUID_NFIELDS) return fail(FLUID_E_INVALID, "%s: nfields %d outside [1, %d]", call, p->nfields, FLUID_NFIELDS);
+        if (!p->fields) return fail(FLUID_E_INVALID, "%s: null `fields`", call);
+        if (!p->snapshots) return fail(FLUID_E_INVALID, "%s: null device pointer `snapshots`", call);
+        for (int k = 0; k < p->nfields; ++k)
+            if (!c->valid_field(p->fields[k])) return fail(FLUID_E_INVALID, "%s: bad field id %d", call, p->fields[k]);
+        const size_t need = (size_t)snapshots * (size_t)p->nfields * block;
+        if (p->capacity < need)
+            return fail(FLUID_E_INVALID, "%s: capacity %zu floats is below the %zu of %d snapshots x %d fields x %d members", call, p->capacity, need,
+                        snapshots, p->nfields, c->members);
+        TRY(check_device_span(c, call, "snapshots", p->snapshots, need * sizeof(float)));
+    }
+    if (p->sources) TRY(check_device_span(c, call, "sources", p->sources, 3 * block * sizeof(float)));
+    const float* src = static_cast<const float*>(p->sources);
+    float* snap = static_cast<float*>(p->snapshots);
+    for (int z = 0; z < p->nsteps; ++z) {
+        if (src) {
+            for (int k = 0; k < 3; ++k) TRY(unpack_range(c, FLUID_U_PREV + k, 0, c->members, src + (size_t)k * block, cells));
+        } else if (!(p->use_sources && z == 0)) {
+            TRY(zero_sources(c));
+        }
+        TRY(full_step(c, dt, diff, visc, p->iters));
+        if (p->every && (z + 1) % p->every == 0)
+            for (int k = 0; k < p->nfields; ++k) {
+                TRY(pack_range(c, p->fields[k], 0, c->members, snap, cells));
+                snap += block;
+            }
+    }
+    HIP_TRY(hipGetLastError());
+    if (snapshots_written) *snapshots_written = snapshots;
+    return FLUID_OK;
+}
+
+int fluid_run(fluid_ctx* c, float dt, float diff, float visc, const fluid_run_plan* plan, int* snapshots_written)
+{
+    if (!plan) return fail(FLUID_E_INVALID, "fluid_run: null plan");
+    if (!c) return fail(FLUID_E_INVALID, "fluid_run: null context");
+    return run_body(c, "fluid_run", dt, diff, visc, plan, snapshots_written);
+}
+
+int fluid_run_members(fluid_ctx* c, const float* dt, const float* diff, const float* visc, const fluid_run_plan* plan, int* snapshots_written)
+{
+    if (!plan) return fail(FLUID_E_INVALID, "fluid_run_members: null plan");
+    TRY(check_member_args(c, "fluid_run_members", {{"dt", dt}, {"diff", diff}, {"visc", visc}}));
+    if (c->members == 1) return run_body(c, "fluid_run_members", dt[0], diff[0], visc[0], plan, snapshots_written);
+    TRY(ensure_consts(c));
+    return run_body(c, "fluid_run_members", {dt, c->members}, {diff, c->members}, {visc, c->members}, plan, snapshots_written);
 }
 
 // ---- timing -------------------------------------------------------------------

@@ -7,6 +7,7 @@ advect, computeDivergenceAndPressure, lastProject, dens_step, vel_step
 the arrays resident on the MI355X and addressed by name.
 """
 import ctypes as C
+import sys
 
 import numpy as np
 
@@ -52,6 +53,29 @@ def member_values(members, **params):
 
 def _mf(a):
     return a.ctypes.data_as(capi._MF)
+
+
+def device_address(buf):
+    """The device address of a buffer: anything with data_ptr() (a torch tensor), a __cuda_array_interface__, or a plain
+    integer address."""
+    if hasattr(buf, "data_ptr"):
+        return int(buf.data_ptr())
+    cai = getattr(buf, "__cuda_array_interface__", None)
+    if cai is not None:
+        return int(cai["data"][0])
+    if isinstance(buf, (int, np.integer)):
+        return int(buf)
+    raise TypeError("a device buffer needs data_ptr(), a __cuda_array_interface__ or an integer address, got %s" % type(buf).__name__)
+
+
+def device_floats(buf, default):
+    """How many floats lie behind a device buffer, where it says so (a plain address: `default`, the caller vouches)."""
+    if hasattr(buf, "numel") and hasattr(buf, "element_size"):
+        return int(buf.numel()) * int(buf.element_size()) // 4
+    cai = getattr(buf, "__cuda_array_interface__", None)
+    if cai is not None:
+        return int(np.prod(cai["shape"], dtype=np.int64)) * np.dtype(cai["typestr"]).itemsize // 4
+    return int(default)
 
 
 class FluidSolver:
@@ -116,8 +140,7 @@ class FluidSolver:
             arr = np.ascontiguousarray(arr, dtype=np.float32)
             if arr.shape != (self.members, self.n + 2, self.n + 2):
                 raise ValueError("field must have shape (%d, %d, %d), got %s" % (self.members, self.n + 2, self.n + 2, arr.shape))
-            for m in range(self.members):
-                capi.check(capi.lib().fluid_upload_member(self._h, m, _fid(name), arr[m]))
+            capi.check(capi.lib().fluid_upload_members(self._h, _fid(name), _mf(arr)))
 
     def download_members(self, field, out=None):
         """All members of a field as one (members, N+2, N+2) array."""
@@ -125,9 +148,77 @@ class FluidSolver:
             out = np.empty((self.members, self.n + 2, self.n + 2), dtype=np.float32)
         if out.dtype != np.float32 or not out.flags.c_contiguous or out.shape != (self.members, self.n + 2, self.n + 2):
             raise ValueError("out must be C-contiguous float32 of shape (%d, %d, %d)" % (self.members, self.n + 2, self.n + 2))
-        for m in range(self.members):
-            capi.check(capi.lib().fluid_download_member(self._h, m, _fid(field), out[m]))
+        capi.check(capi.lib().fluid_download_members(self._h, _fid(field), _mf(out)))
         return out
+
+    # -- whole ensembles on the device: dense float arrays, member after member, each (N+2, N+2) with its ghost ring
+    def _handover(self, wait):
+        """wait=True: everything torch's current stream holds is done before the library enqueues (a no-op without torch
+        or without a device buffer made by it)."""
+        if wait:
+            torch = sys.modules.get("torch")
+            if torch is not None and torch.cuda.is_available():
+                torch.cuda.current_stream().synchronize()
+
+    def pack(self, field, out=None, first=0, count=0, member_stride=0, wait=True):
+        """Members [first, first + count) of a field (count=0: to the end) into a dense device array, in one launch.
+
+        `out`: a device buffer -- anything with data_ptr(), a __cuda_array_interface__, or an integer address; None: a
+        (count, N+2, N+2) float32 torch tensor is allocated (member_stride must then be 0).  wait=True makes the hand-over
+        safe both ways: torch's current stream is waited for before the launch is enqueued, the context's stream after
+        it.  wait=False only enqueues: for a caller who shares a stream with the library (the constructor's stream=)."""
+        w = self.n + 2
+        n = int(count) if count else self.members - int(first)
+        if out is None:
+            if member_stride not in (0, w * w):
+                raise ValueError("out=None allocates a dense tensor: member_stride must be 0")
+            import torch
+            out = torch.empty((max(n, 0), w, w), dtype=torch.float32, device="cuda")
+        self._handover(wait)
+        capi.check(capi.lib().fluid_pack_members(self._h, _fid(field), int(first), int(count), device_address(out), int(member_stride)))
+        if wait:
+            self.synchronize()
+        return out
+
+    def unpack(self, field, src, first=0, count=0, member_stride=0, wait=True):
+        """A dense device array into members [first, first + count) of a field, in one launch: all members replace the
+        field, a sub-range settles it first and overwrites those members.  `src`, `wait`: as for pack."""
+        self._handover(wait)
+        capi.check(capi.lib().fluid_unpack_members(self._h, _fid(field), int(first), int(count), device_address(src), int(member_stride)))
+        if wait:
+            self.synchronize()
+
+    def run(self, nsteps, every=0, fields=(), sources=None, out=None, dt=DT, diff=DIFF, visc=VIS, iters=ITERS, use_sources=False,
+            wait=True):
+        """nsteps steps without the host in the loop.  `sources`: a dense device array (3, members, N+2, N+2) -- u_prev,
+        v_prev, dens_prev -- put back before EVERY step (a forced run); None: step()'s rule.  every > 0: after every
+        `every`-th step the listed fields are recorded into `out`, a dense device array (snapshots, len(fields), members,
+        N+2, N+2) (None: a torch tensor of that shape is allocated).  Returns (out, snapshots written); out is None when
+        nothing is recorded.  dt / diff / visc: a scalar or one value per member, like step.  `wait`: as for pack."""
+        w = self.n + 2
+        ids = [_fid(f) for f in fields]
+        every, nsteps = int(every), int(nsteps)
+        count = nsteps // every if every > 0 and nsteps > 0 else 0
+        capacity = 0
+        if every > 0:
+            if out is None:
+                import torch
+                out = torch.empty((count, len(ids), self.members, w, w), dtype=torch.float32, device="cuda")
+            capacity = device_floats(out, count * len(ids) * self.members * w * w)
+        plan = capi.RunPlan(iters=int(iters), nsteps=nsteps, use_sources=1 if use_sources else 0,
+                            sources=device_address(sources) if sources is not None else None, every=every,
+                            fields=(C.c_int * len(ids))(*ids) if ids else None, nfields=len(ids),
+                            snapshots=device_address(out) if every > 0 else None, capacity=capacity)
+        written = C.c_int()
+        mv = member_values(self.members, dt=dt, diff=diff, visc=visc)
+        self._handover(wait)
+        if mv is None:
+            capi.check(capi.lib().fluid_run(self._h, dt, diff, visc, C.byref(plan), C.byref(written)))
+        else:
+            capi.check(capi.lib().fluid_run_members(self._h, *[_mf(a) for a in mv.values()], C.byref(plan), C.byref(written)))
+        if wait:
+            self.synchronize()
+        return (out if every > 0 else None), written.value
 
     def member_count(self):
         m = C.c_int()

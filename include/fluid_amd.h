@@ -314,6 +314,61 @@ int fluid_member_moments(fluid_ctx *ctx, int field, double *sum, double *sumsq);
 int fluid_ensemble_stats(fluid_ctx *ctx, int field, float *mean, float *variance);
 int fluid_ensemble_stats_ptr(fluid_ctx *ctx, void **mean_dev, void **variance_dev);
 
+/* ---- moving ensembles: device pack / unpack, bulk host copies, recorded runs -------------------------------
+ * M = fluid_members(ctx), W = N + 2.  A DENSE array is always float, one member after the other, each member the
+ * reference's W*W row-major array with its ghost ring; member m starts m * member_stride floats behind the base pointer.
+ * Dense device arrays need 4-byte alignment only.  All six calls work on a one-member, one-GPU context with M = 1.
+ *
+ * - fluid_pack_members / fluid_unpack_members: members [first, first + count) of one field <-> a dense DEVICE array, one
+ *   kernel launch whatever the count, enqueued on the context's stream, no wait.  count = 0: from `first` to the end.
+ *   member_stride = 0: W*W; any other value must be at least W*W (the floats between two members are not touched).
+ *   pack writes what fluid_download_member would show right after the call, bit for bit: whatever the library still owes
+ *   the field is settled first (zeros by definition, a pending increment, a deferred source), and with fp16 storage the
+ *   values are widened exactly and the pressure scale is divided back in float, exactly.  Nothing a later step or download
+ *   sees is altered.  unpack stores narrow(dense): with fp16 storage one rounding to nearest even, the same bits
+ *   fluid_upload_member's host conversion stores.  An unpack of ALL members replaces the field: nothing is settled first,
+ *   whatever the field still owed itself is dropped.  An unpack of a proper sub-range first settles the field for all
+ *   members, as fluid_upload_member does, then overwrites the range.  The pad columns of the device layout are neither
+ *   read nor written.  The dense memory belongs to the library until the stream has run the launch (fluid_synchronize,
+ *   or work of the caller's ordered behind it on the stream given to fluid_create_ex).
+ * - fluid_download_members / fluid_upload_members: all members <-> a host array of M*W*W floats, synchronous, ONE wait.
+ *   They go through a library-owned dense staging buffer on the device (outside the arena: fluid_arena_bytes_ensemble is
+ *   unchanged; allocated by the first such call, freed by fluid_destroy; a failed allocation is FLUID_E_NOMEM and leaves
+ *   the context usable) of g = max(1, min(M, 64 MiB / (W*W*4))) members, ceil(M / g) groups in stream order.  Results are
+ *   those of M fluid_download_member / fluid_upload_member calls, bit for bit.
+ * - fluid_run / fluid_run_members: plan->nsteps steps without the host in the loop, defined as this sequence of existing
+ *   calls, bit for bit in every field of every member.  Per step, with plan->sources set: fluid_unpack_members of its three
+ *   blocks into U_PREV, V_PREV, DENS_PREV, then fluid_step_members(.., iters, 1, 1) -- a forced run: fluid_step alone zeroes
+ *   the sources of every step but the first; without: fluid_step_members with use_sources for the first step only.  After
+ *   every `every`-th step: fluid_pack_members of each listed field into its slot of `snapshots`.  No wait anywhere.
+ *   *snapshots_written (may be null) = every ? nsteps / every : 0.  fluid_run_members gives each member its own dt, diff,
+ *   visc (host arrays of M values, as for fluid_step_members).
+ * Refusals, all FLUID_E_INVALID with a message that names the call, found before anything is launched or any state
+ * changes, null pointers before the device is touched: null context, device or host pointer, or plan; bad field id;
+ * first / count outside [0, M]; a stride below W*W; odd or negative iters; negative nsteps or every; every > 0 with
+ * nfields outside [1, 12], null fields / snapshots, or a capacity below snapshots * nfields * M * W*W floats; a non-finite
+ * dt[m] / diff[m] / visc[m] (the member is named); a device pointer that is not device memory of the context's device, or
+ * whose needed extent does not lie inside one allocation (asked of the runtime on the host: a wrong pointer never reaches
+ * a kernel).  On row slabs (nranks > 1) all six calls are refused, as the moments are.
+ * The launches belong to none of the fluid_timing categories. */
+int fluid_pack_members(fluid_ctx *ctx, int field, int first, int count, void *dst_dev, size_t member_stride);
+int fluid_unpack_members(fluid_ctx *ctx, int field, int first, int count, const void *src_dev, size_t member_stride);
+int fluid_download_members(fluid_ctx *ctx, int field, float *host);
+int fluid_upload_members(fluid_ctx *ctx, int field, const float *host);
+typedef struct fluid_run_plan {
+    int iters, nsteps, use_sources;
+    const void *sources;   /* device, dense [3][M][W*W]: u_prev, v_prev, dens_prev, written before EVERY step, which consumes
+                              them (use_sources is then taken as 1 for every step); NULL: fluid_step's rule */
+    int every;             /* a snapshot after every `every`-th step; 0: none */
+    const int *fields;     /* what a snapshot holds: nfields field ids (host memory) */
+    int nfields;
+    void *snapshots;       /* device, dense [snapshot][field][member][W*W] */
+    size_t capacity;       /* floats behind `snapshots` */
+} fluid_run_plan;
+int fluid_run(fluid_ctx *ctx, float dt, float diff, float visc, const fluid_run_plan *plan, int *snapshots_written);
+int fluid_run_members(fluid_ctx *ctx, const float *dt, const float *diff, const float *visc, const fluid_run_plan *plan,
+                      int *snapshots_written);
+
 int fluid_set_jacobi_variant(fluid_ctx *ctx, int variant);
 /* How FLUID_JACOBI_TB divides by `beta` in a solve with these coefficients (diagnostic; runs the on-device proof
  * if this beta has not been seen): 0 true division, 2 double-precision reciprocal, 3 two-term float reciprocal
