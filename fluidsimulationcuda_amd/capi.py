@@ -123,6 +123,11 @@ SIGNATURES = {
     "fluid_upload_members": [_ctx, _i, _MF],
     "fluid_run": [_ctx, _f, _f, _f, C.POINTER(RunPlan), C.POINTER(_i)],
     "fluid_run_members": [_ctx, _MF, _MF, _MF, C.POINTER(RunPlan), C.POINTER(_i)],
+    "fluid_coarse_size": [_i, _i, C.POINTER(_i)],
+    "fluid_pack_members_coarse": [_ctx, _i, _i, _i, _i, C.c_void_p, C.c_size_t],
+    "fluid_download_members_coarse": [_ctx, _i, _i, _MF],
+    "fluid_run_coarse": [_ctx, _f, _f, _f, C.POINTER(RunPlan), _i, C.POINTER(_i)],
+    "fluid_run_members_coarse": [_ctx, _MF, _MF, _MF, C.POINTER(RunPlan), _i, C.POINTER(_i)],
     "fluid_set_jacobi_variant": [_ctx, _i],
     "fluid_division_mode": [_ctx, _f, _f, C.POINTER(_i)],
     "fluid_autotune_pending": [_ctx, C.POINTER(_i)],
@@ -147,6 +152,7 @@ OTHER_SYMBOLS = {"fluid_last_error": (C.c_char_p, []), "fluid_arena_bytes": (C.c
                  "fluid_arena_bytes_ex": (C.c_size_t, [_i, _i]),
                  "fluid_arena_bytes_ensemble": (C.c_size_t, [_i, _i, _i])}
 MAX_MEMBERS = 21845
+COARSE_FACTORS = (1, 2, 4, 8, 16, 32, 64)
 
 _lib = None
 

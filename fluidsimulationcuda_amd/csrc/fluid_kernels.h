@@ -161,5 +161,10 @@ void launch_ensemble_stats(hipStream_t s, int st, const void* x, int pitch, int 
 // pack: dense = widen(x) * inv (fp16 storage; fp32 copies the words); unpack: x = narrow(dense), to nearest even.
 void launch_pack_members(hipStream_t s, int st, const void* x, int pitch, int n, Members mb, float inv, float* dense, size_t dstride);
 void launch_unpack_members(hipStream_t s, int st, void* x, int pitch, int n, Members mb, const float* dense, size_t dstride);
+// The block-averaged pack: every factor x factor block of a member's (n + 2)^2 array as one float (the order of the sum:
+// include/fluid_amd.h "coarse snapshots"), member m of the result m * cstride floats behind `coarse`, ((n + 2) / factor)^2
+// floats each.  factor: 2, 4 .. 64, a divisor of n + 2.  One launch, one read of the field.
+void launch_pack_members_coarse(hipStream_t s, int st, const void* x, int pitch, int n, Members mb, float inv, int factor, float* coarse,
+                                size_t cstride);
 
 }  // namespace fluid

@@ -1946,6 +1946,104 @@ __global__ __launch_bounds__(256) void k_unpack_members(S* __restrict__ x, int p
 }
 
 // ---------------------------------------------------------------------------
+// block-averaged pack (include/fluid_amd.h "coarse snapshots"): the (n + 2)^2 array of a member, ghost ring included, cut
+// into R x R blocks, R = 2^LR, each written as one float.  The order of the sum is part of the contract: per row of a block
+// a pairwise tree over adjacent columns in double, then the rows added one after the other, one exact scaling, one
+// rounding.  The kernel is one read of the field: a lane takes the VW = 4 (fp16: 8) columns VW * g .. VW * g + VW - 1 of
+// a row -- a group, block-aligned -- and walks down the R rows of its block, 8 rows' loads in flight at a time, with the
+// running sum(s) in registers.  Column 0
+// sits one element before an aligned line, so a group is the last element of one aligned 16-byte vector and the first
+// VW - 1 of the next: the lane loads the aligned vector at column VW * g + 1 and takes column VW * g from the lane below
+// it, which holds it as the last element of its own vector (one lane exchange per load); lane 0 of a wave and the first
+// group of a row load that one element themselves.  The last element of a row's last vector is a pad column (inside the
+// pitch: pitch_for), loaded and not used.  R > VW: the R / VW lanes of a block finish each row's tree with xor exchanges,
+// lower lane + upper lane at every level in the block's first lane, which writes the cell.  R < VW: a lane owns VW / R
+// cells.  Grid (blocks over the side * groups lanes of a member, members), member bases in 64-bit scalar arithmetic, field
+// offsets of type I (narrow_index), as in k_pack_members.  No LDS, no atomics; the stores are 1 / R^2 of the traffic.
+// ---------------------------------------------------------------------------
+// ROWS rows of a lane's group, from row `at` on, all their loads in flight together: s[0 .. OUTS) takes (FIRST: starts from) each
+// row's tree over the columns of each of the lane's blocks (R > VW: of the whole block), row after row
+template <typename S, typename I, int LR, int ROWS, bool FIRST>
+__device__ __forceinline__ void coarse_rows(const S* __restrict__ x, I at, int pitch, float inv, bool own, double* s)
+{
+    constexpr int VW = StatsVec<S>::VW, R = 1 << LR;
+    constexpr int LANES = R > VW ? R / VW : 1, OUTS = R < VW ? VW / R : 1;
+    typedef S vec_t __attribute__((ext_vector_type(VW)));
+    vec_t v[ROWS];                                      // columns VW * g + 1 .. VW * g + VW
+    S lone[ROWS];                                       // column VW * g, where no lane below holds it
+#pragma unroll
+    for (int i = 0; i < ROWS; ++i) {
+        v[i] = *reinterpret_cast<const vec_t*>(x + (I)(at + (I)i * (I)pitch));
+        lone[i] = (S)0;
+    }
+    if (own) {
+#pragma unroll
+        for (int i = 0; i < ROWS; ++i) lone[i] = x[(I)(at + (I)i * (I)pitch - (I)1)];
+    }
+#pragma unroll
+    for (int i = 0; i < ROWS; ++i) {
+        float f[VW], mine;
+        if constexpr (sizeof(S) == 4) {
+#pragma unroll
+            for (int e = 0; e < VW; ++e) f[e] = v[i][e];
+            mine = lone[i];
+        } else {
+#pragma unroll
+            for (int e = 0; e < VW; ++e) f[e] = keep_f32((float)v[i][e]) * inv;
+            mine = keep_f32((float)lone[i]) * inv;
+        }
+        const float below = __shfl_up(f[VW - 1], 1);
+        double d[VW];
+        d[0] = (double)(own ? mine : below);
+#pragma unroll
+        for (int e = 1; e < VW; ++e) d[e] = (double)f[e - 1];
+#pragma unroll
+        for (int width = VW >> 1; width >= OUTS; width >>= 1)      // the levels of the tree inside the group
+#pragma unroll
+            for (int k = 0; k < width; ++k) d[k] = d[2 * k] + d[2 * k + 1];
+#pragma unroll
+        for (int m = 1; m < LANES; m <<= 1) d[0] = d[0] + __shfl_xor(d[0], m);      // ... and across the block's lanes
+#pragma unroll
+        for (int k = 0; k < OUTS; ++k) s[k] = FIRST && i == 0 ? d[k] : s[k] + d[k];      // the sum starts from row 0, not from 0.0
+    }
+}
+
+template <typename S, typename I, int LR>
+__global__ __launch_bounds__(256) void k_pack_members_coarse(const S* __restrict__ x, int pitch, int n, size_t ms, int groups, float inv,
+                                                             float* __restrict__ coarse, size_t cstride)
+{
+    constexpr int VW = StatsVec<S>::VW, R = 1 << LR;
+    constexpr int LANES = R > VW ? R / VW : 1;          // lanes that share a coarse cell
+    constexpr int OUTS = R < VW ? VW / R : 1;           // coarse cells of one lane
+    constexpr int ROWS = R < 8 ? R : 8;                 // rows whose loads are in flight together
+    constexpr double SCALE = 1.0 / (double)(1 << (2 * LR));
+    const int side = (n + 2) >> LR;
+    const unsigned t = blockIdx.x * 256u + threadIdx.x;           // side * groups < 2^32 for every N the library accepts
+    // (n + 2) % R == 0: groups % LANES == 0, so the lanes of a block are LANES aligned lanes of one wave, all here or all gone
+    if (t >= (unsigned)side * (unsigned)groups) return;
+    const int bi = (int)(t / (unsigned)groups), g = (int)(t % (unsigned)groups);
+    x += blockIdx.y * ms;
+    coarse += blockIdx.y * cstride;
+    const bool own = (threadIdx.x & 63u) == 0 || g == 0;          // no lane below that holds column VW * g
+    I at = (I)(bi << LR) * (I)pitch + (I)(XOFF + 1 + VW * g);      // XOFF + 1 = 64: 16 aligned bytes
+    double s[OUTS];
+    coarse_rows<S, I, LR, ROWS, true>(x, at, pitch, inv, own, s);
+#pragma unroll 1
+    for (int i = ROWS; i < R; i += ROWS) {
+        at += (I)ROWS * (I)pitch;
+        coarse_rows<S, I, LR, ROWS, false>(x, at, pitch, inv, own, s);
+    }
+    const size_t out = (size_t)bi * (size_t)side;
+    if constexpr (R >= VW) {
+        if ((g & (LANES - 1)) == 0) coarse[out + (size_t)(g / LANES)] = (float)(s[0] * SCALE);
+    } else {
+#pragma unroll
+        for (int k = 0; k < OUTS; ++k)
+            if (g * OUTS + k < side) coarse[out + (size_t)(g * OUTS + k)] = (float)(s[k] * SCALE);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // launch wrappers (host).  Shapes are validated by the caller (fluid_solver).
 // `st` selects the field storage type the untyped pointers refer to.
 // ---------------------------------------------------------------------------
@@ -2224,6 +2322,30 @@ void launch_unpack_members(hipStream_t s, int st, void* x, int pitch, int n, Mem
     const dim3 grid(cdiv((unsigned)(n + 2) * (unsigned)vecs, 256), mb.count);
     FLUID_BY_STORAGE_INDEX(st, pitch, n, hipLaunchKernelGGL((k_unpack_members<S, I>), grid, dim3(256), 0, s, (S*)x, pitch, n, mb.stride, vecs,
                                                             dense, dstride));
+}
+
+// factor: 2, 4, .. 64 and a divisor of n + 2 (fluid_solver checks it; factor 1 is launch_pack_members)
+void launch_pack_members_coarse(hipStream_t s, int st, const void* x, int pitch, int n, Members mb, float inv, int factor, float* coarse,
+                                size_t cstride)
+{
+    const int vw = 16 / (int)storage_bytes(st);
+    const int groups = (n + 2 + vw - 1) / vw;           // block-aligned groups of vw columns per row, column 0 included
+    const int lr = __builtin_ctz((unsigned)factor);
+    const dim3 grid(cdiv((unsigned)((n + 2) >> lr) * (unsigned)groups, 256), mb.count);
+#define FLUID_COARSE_CASE(LR)                                                                                                             \
+    case LR:                                                                                                                              \
+        FLUID_BY_STORAGE_INDEX(st, pitch, n, hipLaunchKernelGGL((k_pack_members_coarse<S, I, LR>), grid, dim3(256), 0, s, (const S*)x,    \
+                                                                pitch, n, mb.stride, groups, inv, coarse, cstride));                      \
+        break
+    switch (lr) {
+        FLUID_COARSE_CASE(1);
+        FLUID_COARSE_CASE(2);
+        FLUID_COARSE_CASE(3);
+        FLUID_COARSE_CASE(4);
+        FLUID_COARSE_CASE(5);
+        FLUID_COARSE_CASE(6);
+    }
+#undef FLUID_COARSE_CASE
 }
 
 }  // namespace fluid

@@ -2559,7 +2559,31 @@ int fluid_ensemble_stats_ptr(fluid_ctx* c, void** mean_dev, void** variance_dev)
 // (include/fluid_amd.h "moving ensembles".)  One launch moves all members of a field -- or a range of them -- between the
 // library's layout and a dense float array on the device; the bulk host copies and fluid_run are built on it.  The
 // launches belong to none of the timing categories.  Every refusal is found before anything is launched or changed.
-static size_t member_cells(const fluid_ctx* c) { return (size_t)c->w * (size_t)c->w; }
+// factor 0: a dense call; otherwise the cells of a member of a coarse dense array (the factor has passed check_factor)
+static size_t member_cells(const fluid_ctx* c, int factor = 0)
+{
+    const size_t side = (size_t)(factor ? c->w / factor : c->w);
+    return side * side;
+}
+
+// Inside this file factor 0 stands for the dense calls, which share their bodies with the coarse ones: an entry point that
+// takes a factor from the caller refuses 0 here, before anything else, and every body checks a non-zero factor (check_factor).
+static int refuse_factor_zero(const char* call, int factor)
+{
+    if (factor == 0) return fail(FLUID_E_INVALID, "%s: factor 0: the factor must be one of 1, 2, 4, 8, 16, 32, 64", call);
+    return FLUID_OK;
+}
+
+// a coarse factor for a grid of N: one of 1, 2, 4 .. 64 that divides N + 2
+static int check_factor(const char* call, int N, int factor)
+{
+    if (N < 1) return fail(FLUID_E_INVALID, "%s: N = %d, factor %d: N must be at least 1", call, N, factor);
+    if (factor < 1 || factor > 64 || (factor & (factor - 1)) != 0)
+        return fail(FLUID_E_INVALID, "%s: N = %d, factor %d: the factor must be one of 1, 2, 4, 8, 16, 32, 64", call, N, factor);
+    if ((N + 2) % factor != 0)
+        return fail(FLUID_E_INVALID, "%s: N = %d, factor %d: the factor must divide N + 2 = %d", call, N, factor, N + 2);
+    return FLUID_OK;
+}
 
 // bytes from the first float of member 0 to the end of member count - 1 in a dense array; false: not representable
 static bool dense_span(size_t cells, int count, size_t stride, size_t* bytes)
@@ -2609,29 +2633,37 @@ static int check_device_span(const fluid_ctx* c, const char* call, const char* n
 }
 
 // first / count / member_stride as a pack or unpack call means them (0: to the end; 0: dense), and the device array behind them
-static int check_member_move(const fluid_ctx* c, const char* call, int field, int first, int* count, const void* dev, size_t* stride)
+// (factor: 0 for the dense calls; a coarse pack's array has ((N + 2) / factor)^2 cells per member)
+static int check_member_move(const fluid_ctx* c, const char* call, int field, int first, int* count, const void* dev, size_t* stride,
+                             int factor = 0)
 {
     if (!c->valid_field(field)) return fail(FLUID_E_INVALID, "%s: bad field id %d", call, field);
     TRY(refuse_slabs(c, call));
+    if (factor) TRY(check_factor(call, c->n, factor));
     if (first < 0 || first > c->members || *count < 0 || *count > c->members - first)
         return fail(FLUID_E_INVALID, "%s: first %d, count %d outside the %d members of this context", call, first, *count, c->members);
     if (*count == 0) *count = c->members - first;
-    const size_t cells = member_cells(c);
+    const size_t cells = member_cells(c, factor);
     if (*stride == 0) *stride = cells;
-    if (*stride < cells) return fail(FLUID_E_INVALID, "%s: member_stride %zu is below (N + 2)^2 = %zu", call, *stride, cells);
+    if (*stride < cells) {
+        if (factor) return fail(FLUID_E_INVALID, "%s: member_stride %zu is below ((N + 2) / %d)^2 = %zu", call, *stride, factor, cells);
+        return fail(FLUID_E_INVALID, "%s: member_stride %zu is below (N + 2)^2 = %zu", call, *stride, cells);
+    }
     size_t bytes = 0;
     if (!dense_span(cells, *count, *stride, &bytes)) return fail(FLUID_E_INVALID, "%s: member_stride %zu is too large", call, *stride);
     return check_device_span(c, call, "the dense array", dev, bytes);
 }
 
-// as fluid_download_member sees the field: the lazy state settled, a scale kept and divided back on the way out
-static int pack_range(fluid_ctx* c, int field, int first, int count, float* dst, size_t stride)
+// as fluid_download_member sees the field: the lazy state settled, a scale kept and divided back on the way out.
+// factor 0: the dense pack; a coarse factor: the block-averaged one -- factor 1 is the dense pack, bit for bit, and runs it.
+static int pack_range(fluid_ctx* c, int field, int first, int count, float* dst, size_t stride, int factor = 0)
 {
     if (count == 0) return FLUID_OK;
     const float inv = c->st != fluid::STORAGE_F32 ? 1.0f / c->field[field].fscale : 1.0f;
     TRY(materialize(c, field, /*keep_scale=*/inv != 1.0f));
     const char* x = static_cast<const char*>(c->ptr(field)) + (size_t)first * c->field_bytes;
-    fluid::launch_pack_members(c->stream, c->st, x, c->pitch, c->n, {count, c->field_floats}, inv, dst, stride);
+    if (factor > 1) fluid::launch_pack_members_coarse(c->stream, c->st, x, c->pitch, c->n, {count, c->field_floats}, inv, factor, dst, stride);
+    else fluid::launch_pack_members(c->stream, c->st, x, c->pitch, c->n, {count, c->field_floats}, inv, dst, stride);
     HIP_TRY(hipGetLastError());
     return FLUID_OK;
 }
@@ -2666,6 +2698,23 @@ int fluid_pack_members(fluid_ctx* c, int field, int first, int count, void* dst_
     return pack_range(c, field, first, count, static_cast<float*>(dst_dev), member_stride);
 }
 
+int fluid_coarse_size(int N, int factor, int* side)
+{
+    if (!side) return fail(FLUID_E_INVALID, "fluid_coarse_size: null pointer `side`");
+    TRY(check_factor("fluid_coarse_size", N, factor));
+    *side = (N + 2) / factor;
+    return FLUID_OK;
+}
+
+int fluid_pack_members_coarse(fluid_ctx* c, int field, int first, int count, int factor, void* dst_dev, size_t member_stride)
+{
+    TRY(refuse_factor_zero("fluid_pack_members_coarse", factor));
+    if (!dst_dev) return fail(FLUID_E_INVALID, "fluid_pack_members_coarse: null device pointer `dst_dev`");
+    if (!c) return fail(FLUID_E_INVALID, "fluid_pack_members_coarse: null context");
+    TRY(check_member_move(c, "fluid_pack_members_coarse", field, first, &count, dst_dev, &member_stride, factor));
+    return pack_range(c, field, first, count, static_cast<float*>(dst_dev), member_stride, factor);
+}
+
 int fluid_unpack_members(fluid_ctx* c, int field, int first, int count, const void* src_dev, size_t member_stride)
 {
     if (!src_dev) return fail(FLUID_E_INVALID, "fluid_unpack_members: null device pointer `src_dev`");
@@ -2694,21 +2743,33 @@ static int ensure_stage(fluid_ctx* c, const char* call)
     return FLUID_OK;
 }
 
-int fluid_download_members(fluid_ctx* c, int field, float* host)
+// fluid_download_members (factor 0) / fluid_download_members_coarse: the same staging buffer, in groups of as many (coarse)
+// members as fit in it
+static int download_body(fluid_ctx* c, const char* call, int field, int factor, float* host)
 {
-    if (!host) return fail(FLUID_E_INVALID, "fluid_download_members: null host pointer");
-    if (!c) return fail(FLUID_E_INVALID, "fluid_download_members: null context");
-    if (!c->valid_field(field)) return fail(FLUID_E_INVALID, "fluid_download_members: bad field id %d", field);
-    TRY(refuse_slabs(c, "fluid_download_members"));
-    TRY(ensure_stage(c, "fluid_download_members"));
-    const size_t cells = member_cells(c);
-    for (int first = 0; first < c->members; first += c->stage.members) {      // groups in stream order: the buffer is reused
-        const int count = std::min(c->stage.members, c->members - first);
-        TRY(pack_range(c, field, first, count, c->stage.dev, cells));
+    if (!host) return fail(FLUID_E_INVALID, "%s: null host pointer", call);
+    if (!c) return fail(FLUID_E_INVALID, "%s: null context", call);
+    if (!c->valid_field(field)) return fail(FLUID_E_INVALID, "%s: bad field id %d", call, field);
+    TRY(refuse_slabs(c, call));
+    if (factor) TRY(check_factor(call, c->n, factor));
+    TRY(ensure_stage(c, call));
+    const size_t cells = member_cells(c, factor);
+    const int group = (int)std::min<size_t>((size_t)c->members, (size_t)c->stage.members * (member_cells(c) / cells));
+    for (int first = 0; first < c->members; first += group) {      // groups in stream order: the buffer is reused
+        const int count = std::min(group, c->members - first);
+        TRY(pack_range(c, field, first, count, c->stage.dev, cells, factor));
         HIP_TRY(hipMemcpyAsync(host + (size_t)first * cells, c->stage.dev, (size_t)count * cells * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     return FLUID_OK;
+}
+
+int fluid_download_members(fluid_ctx* c, int field, float* host) { return download_body(c, "fluid_download_members", field, 0, host); }
+
+int fluid_download_members_coarse(fluid_ctx* c, int field, int factor, float* host)
+{
+    TRY(refuse_factor_zero("fluid_download_members_coarse", factor));
+    return download_body(c, "fluid_download_members_coarse", field, factor, host);
 }
 
 int fluid_upload_members(fluid_ctx* c, int field, const float* host)
@@ -2732,14 +2793,18 @@ int fluid_upload_members(fluid_ctx* c, int field, const float* host)
 // fluid_run / fluid_run_members: one body (see "calls whose physical parameters are one value for everybody or one per
 // member").  Defined as the loop of existing calls it replaces: per step the three source blocks unpacked and a step that
 // consumes them, or fluid_step's rule; after every `every`-th step each listed field packed into its snapshot slot.
+// factor 0: the dense snapshots of fluid_run / fluid_run_members; a coarse factor: every snapshot pack is the block-averaged one
+// and `snapshots` / `capacity` count coarse floats (the sources stay full resolution).
 static int run_body(fluid_ctx* c, const char* call, const MemberVal& dt, const MemberVal& diff, const MemberVal& visc, const fluid_run_plan* p,
-                    int* snapshots_written)
+                    int factor, int* snapshots_written)
 {
     TRY(refuse_slabs(c, call));
+    if (factor) TRY(check_factor(call, c->n, factor));
     if (p->iters < 0 || (p->iters & 1)) return fail(FLUID_E_INVALID, "%s: sweep count must be even and >= 0 (got %d)", call, p->iters);
     if (p->nsteps < 0) return fail(FLUID_E_INVALID, "%s: nsteps < 0", call);
     if (p->every < 0) return fail(FLUID_E_INVALID, "%s: every < 0", call);
     const size_t cells = member_cells(c), block = (size_t)c->members * cells;
+    const size_t snap_cells = member_cells(c, factor), snap_block = (size_t)c->members * snap_cells;
     const int snapshots = p->every ? p->nsteps / p->every : 0;
     if (p->every > 0) {
         if (p->nfields < 1 || p->nfields > FLUID_NFIELDS) return fail(FLUID_E_INVALID, "%s: nfields %d outside [1, %d]", call, p->nfields, FLUID_NFIELDS);
@@ -2747,7 +2812,7 @@ static int run_body(fluid_ctx* c, const char* call, const MemberVal& dt, const M
         if (!p->snapshots) return fail(FLUID_E_INVALID, "%s: null device pointer `snapshots`", call);
         for (int k = 0; k < p->nfields; ++k)
             if (!c->valid_field(p->fields[k])) return fail(FLUID_E_INVALID, "%s: bad field id %d", call, p->fields[k]);
-        const size_t need = (size_t)snapshots * (size_t)p->nfields * block;
+        const size_t need = (size_t)snapshots * (size_t)p->nfields * snap_block;
         if (p->capacity < need)
             return fail(FLUID_E_INVALID, "%s: capacity %zu floats is below the %zu of %d snapshots x %d fields x %d members", call, p->capacity, need,
                         snapshots, p->nfields, c->members);
@@ -2765,8 +2830,8 @@ static int run_body(fluid_ctx* c, const char* call, const MemberVal& dt, const M
         TRY(full_step(c, dt, diff, visc, p->iters));
         if (p->every && (z + 1) % p->every == 0)
             for (int k = 0; k < p->nfields; ++k) {
-                TRY(pack_range(c, p->fields[k], 0, c->members, snap, cells));
-                snap += block;
+                TRY(pack_range(c, p->fields[k], 0, c->members, snap, snap_cells, factor));
+                snap += snap_block;
             }
     }
     HIP_TRY(hipGetLastError());
@@ -2778,16 +2843,39 @@ int fluid_run(fluid_ctx* c, float dt, float diff, float visc, const fluid_run_pl
 {
     if (!plan) return fail(FLUID_E_INVALID, "fluid_run: null plan");
     if (!c) return fail(FLUID_E_INVALID, "fluid_run: null context");
-    return run_body(c, "fluid_run", dt, diff, visc, plan, snapshots_written);
+    return run_body(c, "fluid_run", dt, diff, visc, plan, 0, snapshots_written);
+}
+
+int fluid_run_coarse(fluid_ctx* c, float dt, float diff, float visc, const fluid_run_plan* plan, int factor, int* snapshots_written)
+{
+    TRY(refuse_factor_zero("fluid_run_coarse", factor));
+    if (!plan) return fail(FLUID_E_INVALID, "fluid_run_coarse: null plan");
+    if (!c) return fail(FLUID_E_INVALID, "fluid_run_coarse: null context");
+    return run_body(c, "fluid_run_coarse", dt, diff, visc, plan, factor, snapshots_written);
+}
+
+// fluid_run_members (factor 0) / fluid_run_members_coarse
+static int run_members_body(fluid_ctx* c, const char* call, const float* dt, const float* diff, const float* visc, const fluid_run_plan* plan,
+                            int factor, int* snapshots_written)
+{
+    if (!plan) return fail(FLUID_E_INVALID, "%s: null plan", call);
+    TRY(check_member_args(c, call, {{"dt", dt}, {"diff", diff}, {"visc", visc}}));
+    if (c->members == 1) return run_body(c, call, dt[0], diff[0], visc[0], plan, factor, snapshots_written);
+    if (factor) TRY(check_factor(call, c->n, factor));      // before ensure_consts: a refusal changes nothing
+    TRY(ensure_consts(c));
+    return run_body(c, call, {dt, c->members}, {diff, c->members}, {visc, c->members}, plan, factor, snapshots_written);
 }
 
 int fluid_run_members(fluid_ctx* c, const float* dt, const float* diff, const float* visc, const fluid_run_plan* plan, int* snapshots_written)
 {
-    if (!plan) return fail(FLUID_E_INVALID, "fluid_run_members: null plan");
-    TRY(check_member_args(c, "fluid_run_members", {{"dt", dt}, {"diff", diff}, {"visc", visc}}));
-    if (c->members == 1) return run_body(c, "fluid_run_members", dt[0], diff[0], visc[0], plan, snapshots_written);
-    TRY(ensure_consts(c));
-    return run_body(c, "fluid_run_members", {dt, c->members}, {diff, c->members}, {visc, c->members}, plan, snapshots_written);
+    return run_members_body(c, "fluid_run_members", dt, diff, visc, plan, 0, snapshots_written);
+}
+
+int fluid_run_members_coarse(fluid_ctx* c, const float* dt, const float* diff, const float* visc, const fluid_run_plan* plan, int factor,
+                             int* snapshots_written)
+{
+    TRY(refuse_factor_zero("fluid_run_members_coarse", factor));
+    return run_members_body(c, "fluid_run_members_coarse", dt, diff, visc, plan, factor, snapshots_written);
 }
 
 // ---- timing -------------------------------------------------------------------

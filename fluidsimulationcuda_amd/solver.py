@@ -142,13 +142,18 @@ class FluidSolver:
                 raise ValueError("field must have shape (%d, %d, %d), got %s" % (self.members, self.n + 2, self.n + 2, arr.shape))
             capi.check(capi.lib().fluid_upload_members(self._h, _fid(name), _mf(arr)))
 
-    def download_members(self, field, out=None):
-        """All members of a field as one (members, N+2, N+2) array."""
+    def download_members(self, field, out=None, coarse=None):
+        """All members of a field as one (members, N+2, N+2) array; coarse=r: block-averaged over r x r cells, a
+        (members, C, C) array with C = coarse_size(N, r)."""
+        side = self.n + 2 if coarse is None else coarse_size(self.n, coarse)
         if out is None:
-            out = np.empty((self.members, self.n + 2, self.n + 2), dtype=np.float32)
-        if out.dtype != np.float32 or not out.flags.c_contiguous or out.shape != (self.members, self.n + 2, self.n + 2):
-            raise ValueError("out must be C-contiguous float32 of shape (%d, %d, %d)" % (self.members, self.n + 2, self.n + 2))
-        capi.check(capi.lib().fluid_download_members(self._h, _fid(field), _mf(out)))
+            out = np.empty((self.members, side, side), dtype=np.float32)
+        if out.dtype != np.float32 or not out.flags.c_contiguous or out.shape != (self.members, side, side):
+            raise ValueError("out must be C-contiguous float32 of shape (%d, %d, %d)" % (self.members, side, side))
+        if coarse is None:
+            capi.check(capi.lib().fluid_download_members(self._h, _fid(field), _mf(out)))
+        else:
+            capi.check(capi.lib().fluid_download_members_coarse(self._h, _fid(field), int(coarse), _mf(out)))
         return out
 
     # -- whole ensembles on the device: dense float arrays, member after member, each (N+2, N+2) with its ghost ring
@@ -160,14 +165,17 @@ class FluidSolver:
             if torch is not None and torch.cuda.is_available():
                 torch.cuda.current_stream().synchronize()
 
-    def pack(self, field, out=None, first=0, count=0, member_stride=0, wait=True):
+    def pack(self, field, out=None, first=0, count=0, member_stride=0, wait=True, coarse=None):
         """Members [first, first + count) of a field (count=0: to the end) into a dense device array, in one launch.
 
         `out`: a device buffer -- anything with data_ptr(), a __cuda_array_interface__, or an integer address; None: a
         (count, N+2, N+2) float32 torch tensor is allocated (member_stride must then be 0).  wait=True makes the hand-over
         safe both ways: torch's current stream is waited for before the launch is enqueued, the context's stream after
-        it.  wait=False only enqueues: for a caller who shares a stream with the library (the constructor's stream=)."""
-        w = self.n + 2
+        it.  wait=False only enqueues: for a caller who shares a stream with the library (the constructor's stream=).
+        coarse=r (1, 2, 4 .. 64, a divisor of N+2): every r x r block of a member's array as its mean, in the summation
+        order the header defines -- a member is then C x C floats, C = coarse_size(N, r), and so is what member_stride
+        counts and what is allocated."""
+        w = self.n + 2 if coarse is None else coarse_size(self.n, coarse)
         n = int(count) if count else self.members - int(first)
         if out is None:
             if member_stride not in (0, w * w):
@@ -175,7 +183,11 @@ class FluidSolver:
             import torch
             out = torch.empty((max(n, 0), w, w), dtype=torch.float32, device="cuda")
         self._handover(wait)
-        capi.check(capi.lib().fluid_pack_members(self._h, _fid(field), int(first), int(count), device_address(out), int(member_stride)))
+        if coarse is None:
+            capi.check(capi.lib().fluid_pack_members(self._h, _fid(field), int(first), int(count), device_address(out), int(member_stride)))
+        else:
+            capi.check(capi.lib().fluid_pack_members_coarse(self._h, _fid(field), int(first), int(count), int(coarse), device_address(out),
+                                                            int(member_stride)))
         if wait:
             self.synchronize()
         return out
@@ -189,13 +201,15 @@ class FluidSolver:
             self.synchronize()
 
     def run(self, nsteps, every=0, fields=(), sources=None, out=None, dt=DT, diff=DIFF, visc=VIS, iters=ITERS, use_sources=False,
-            wait=True):
+            wait=True, coarse=None):
         """nsteps steps without the host in the loop.  `sources`: a dense device array (3, members, N+2, N+2) -- u_prev,
         v_prev, dens_prev -- put back before EVERY step (a forced run); None: step()'s rule.  every > 0: after every
         `every`-th step the listed fields are recorded into `out`, a dense device array (snapshots, len(fields), members,
         N+2, N+2) (None: a torch tensor of that shape is allocated).  Returns (out, snapshots written); out is None when
-        nothing is recorded.  dt / diff / visc: a scalar or one value per member, like step.  `wait`: as for pack."""
-        w = self.n + 2
+        nothing is recorded.  dt / diff / visc: a scalar or one value per member, like step.  `wait`: as for pack.
+        coarse=r: the snapshots are block-averaged like pack(coarse=r), `out` is (snapshots, len(fields), members, C, C);
+        the sources stay full resolution."""
+        w = self.n + 2 if coarse is None else coarse_size(self.n, coarse)
         ids = [_fid(f) for f in fields]
         every, nsteps = int(every), int(nsteps)
         count = nsteps // every if every > 0 and nsteps > 0 else 0
@@ -212,10 +226,10 @@ class FluidSolver:
         written = C.c_int()
         mv = member_values(self.members, dt=dt, diff=diff, visc=visc)
         self._handover(wait)
-        if mv is None:
-            capi.check(capi.lib().fluid_run(self._h, dt, diff, visc, C.byref(plan), C.byref(written)))
-        else:
-            capi.check(capi.lib().fluid_run_members(self._h, *[_mf(a) for a in mv.values()], C.byref(plan), C.byref(written)))
+        tail = (C.byref(plan), C.byref(written)) if coarse is None else (C.byref(plan), int(coarse), C.byref(written))
+        name = "fluid_run" if mv is None else "fluid_run_members"
+        fn = getattr(capi.lib(), name if coarse is None else name + "_coarse")
+        capi.check(fn(self._h, *((dt, diff, visc) if mv is None else [_mf(a) for a in mv.values()]), *tail))
         if wait:
             self.synchronize()
         return (out if every > 0 else None), written.value
@@ -425,6 +439,14 @@ class FluidSolver:
 
         self._cb = capi.EXCHANGE_FN(tramp)
         capi.check(capi.lib().fluid_set_exchange(self._h, self._cb, None))
+
+
+def coarse_size(n, factor):
+    """Side C = (n + 2) / factor of a block-averaged member; raises FluidError unless factor is one of 1, 2, 4 .. 64 and
+    divides n + 2 (fluid_coarse_size: host logic, no device)."""
+    side = C.c_int()
+    capi.check(capi.lib().fluid_coarse_size(int(n), int(factor), C.byref(side)))
+    return side.value
 
 
 def coefficients(n, dt, coef):

@@ -369,6 +369,44 @@ int fluid_run(fluid_ctx *ctx, float dt, float diff, float visc, const fluid_run_
 int fluid_run_members(fluid_ctx *ctx, const float *dt, const float *diff, const float *visc, const fluid_run_plan *plan,
                       int *snapshots_written);
 
+/* ---- coarse snapshots: block-averaged pack, download, recorded runs ------------------------------------------
+ * W = N + 2.  A COARSE FACTOR r is one of 1, 2, 4, 8, 16, 32, 64 and must divide W; C = W / r.  The r x r blocks tile the
+ * whole W x W array of a member, ghost ring included -- the array a dense pack writes.  r = 1 is the dense pack, bit for bit.
+ * Coarse cell (I, J) of a member is defined from the values x[i][j] that fluid_download_member would show right after the
+ * call, in IEEE double with no contraction:
+ *  1. per row i of the block, the r values (double)x[i][rJ .. rJ + r - 1] are summed as a pairwise tree over adjacent
+ *     columns: level 1 adds columns (0, 1), (2, 3), ..; level 2 adds those results pairwise; log2 r levels give p_i;
+ *  2. s = p_0, then s += p_i for i = 1 .. r - 1 in row order -- from p_0, not from 0.0: a block of -0 has the mean -0;
+ *  3. out = (float)(s * 2^(-2 log2 r)): the scaling is exact, there is ONE rounding to float, float denormals are kept.
+ * With fp16 storage each element is widened exactly and the pressure scale divided back in float, exactly as
+ * fluid_pack_members does it, before step 1.  The order is part of the contract: the same bits on every call, for every
+ * member count and launch shape; no floating-point atomics.  A NaN or inf poisons only the coarse cells whose block holds it.
+ * A COARSE DENSE array is float, member after member, each C*C row-major; member m starts m * member_stride floats behind
+ * the base (0: C*C; otherwise at least C*C); 4-byte alignment.
+ *
+ * - fluid_coarse_size: host logic, no device: *side = (N + 2) / factor.
+ * - fluid_pack_members_coarse: everything fluid_pack_members promises -- one kernel launch whatever the count and factor,
+ *   on the context's stream, no wait; the field's lazy state is settled first and nothing a later step or download sees is
+ *   altered; the floats between two members and everything outside the members' C*C cells are not touched.
+ * - fluid_download_members_coarse: all members into a host array of M*C*C floats, synchronous, ONE wait, through the
+ *   staging buffer of fluid_download_members (no second buffer), each group as many coarse members as fit in it.
+ * - fluid_run_coarse / fluid_run_members_coarse: fluid_run / fluid_run_members in every respect, except that each snapshot
+ *   pack is a fluid_pack_members_coarse with `factor`: plan->snapshots is laid out [snapshot][field][member][C*C], and
+ *   plan->capacity and its check count coarse floats.  plan->sources stays full resolution.
+ * Refusals, all FLUID_E_INVALID with a message that names the call, found before anything is launched or any state
+ * changes: those of the dense calls (null context, device pointer, host pointer or plan -- null pointers before the
+ * context is looked at; bad field id; first / count out of range; row slabs), a factor that is not one of the seven
+ * values, a factor that does not divide N + 2 (fluid_coarse_size: also N < 1; its message names N, the factor and the rule
+ * broken), a stride below C*C, a device extent that does not hold the coarse span (asked of the runtime on the host).
+ * The launches belong to none of the fluid_timing categories. */
+int fluid_coarse_size(int N, int factor, int *side);
+int fluid_pack_members_coarse(fluid_ctx *ctx, int field, int first, int count, int factor, void *dst_dev, size_t member_stride);
+int fluid_download_members_coarse(fluid_ctx *ctx, int field, int factor, float *host);
+int fluid_run_coarse(fluid_ctx *ctx, float dt, float diff, float visc, const fluid_run_plan *plan, int factor,
+                     int *snapshots_written);
+int fluid_run_members_coarse(fluid_ctx *ctx, const float *dt, const float *diff, const float *visc,
+                             const fluid_run_plan *plan, int factor, int *snapshots_written);
+
 int fluid_set_jacobi_variant(fluid_ctx *ctx, int variant);
 /* How FLUID_JACOBI_TB divides by `beta` in a solve with these coefficients (diagnostic; runs the on-device proof
  * if this beta has not been seen): 0 true division, 2 double-precision reciprocal, 3 two-term float reciprocal
