@@ -128,6 +128,8 @@ SIGNATURES = {
     "fluid_download_members_coarse": [_ctx, _i, _i, _MF],
     "fluid_run_coarse": [_ctx, _f, _f, _f, C.POINTER(RunPlan), _i, C.POINTER(_i)],
     "fluid_run_members_coarse": [_ctx, _MF, _MF, _MF, C.POINTER(RunPlan), _i, C.POINTER(_i)],
+    "fluid_transform_members": [_ctx, C.POINTER(_i), _i, _MF],
+    "fluid_select_members": [_ctx, C.POINTER(_i), _i, C.POINTER(_i)],
     "fluid_set_jacobi_variant": [_ctx, _i],
     "fluid_division_mode": [_ctx, _f, _f, C.POINTER(_i)],
     "fluid_autotune_pending": [_ctx, C.POINTER(_i)],
@@ -153,6 +155,7 @@ OTHER_SYMBOLS = {"fluid_last_error": (C.c_char_p, []), "fluid_arena_bytes": (C.c
                  "fluid_arena_bytes_ensemble": (C.c_size_t, [_i, _i, _i])}
 MAX_MEMBERS = 21845
 COARSE_FACTORS = (1, 2, 4, 8, 16, 32, 64)
+TRANSFORM_MAX_MEMBERS = 64
 
 _lib = None
 

@@ -116,6 +116,21 @@ struct MemberStage {
     int members = 0;
 };
 
+// The weight tables of fluid_transform_members / fluid_select_members: kSlots tables of `slot` bytes each in device memory
+// with a pinned host twin, library-owned and outside the arena, allocated by the first such call and freed in
+// fluid_destroy (fluid_solver.hip: ensure_transform).  A call fills the next host slot and copies it to its device slot on
+// the context's stream: the copy runs behind every launch enqueued so far, so the device bytes need no wait, and the host
+// bytes are reused only after the event behind their own copy -- kSlots calls ago -- has completed.  (The ConstRing is
+// sized for the per-member records: 64 KiB at small M, where one 64-member table is 32.5 KiB.)
+struct TransformTables {
+    static constexpr int kSlots = 8;
+    char *dev = nullptr, *host = nullptr;
+    size_t slot = 0;
+    int next = 0;
+    hipEvent_t copied[kSlots] = {};
+    bool in_use[kSlots] = {};
+};
+
 struct fluid_ctx {
     int n = 0, w = 0, pitch = 0;
     size_t field_floats = 0;
@@ -149,6 +164,7 @@ struct fluid_ctx {
     ConstRing consts;                     // tables of per-member constants (fluid_*_members)
     EnsembleReduce red;                   // results and scratch of the ensemble diagnostics
     MemberStage stage;                    // device staging of the bulk host copies
+    TransformTables xform;                // weight tables of fluid_transform_members / fluid_select_members
     unsigned int* tiles = nullptr;        // 3 x members x tile_rows x tile_pitch words: |x0| minima per tile for division mode 3
     unsigned int* h_scalar = nullptr;     // pinned host mirror
     hipEvent_t scalar_ready = nullptr;    // recorded behind the scalar's device-to-host copy

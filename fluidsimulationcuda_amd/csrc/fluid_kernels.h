@@ -166,5 +166,20 @@ void launch_unpack_members(hipStream_t s, int st, void* x, int pitch, int n, Mem
 // floats each.  factor: 2, 4 .. 64, a divisor of n + 2.  One launch, one read of the field.
 void launch_pack_members_coarse(hipStream_t s, int st, const void* x, int pitch, int n, Members mb, float inv, int factor, float* coarse,
                                 size_t cstride);
+// Recombining the members of a field in place (include/fluid_amd.h "recombining ensembles"): new member m of every cell =
+// the sum over the old members k, in member order, of widen(x_k) * inv * table[k * MP + m] in double, rounded once to float
+// and narrowed.  mb.count in [1, kTransformMaxMembers]; MP = transform_padded(mb.count); `table`: device memory, [mb.count][MP]
+// doubles, padding columns 0.  dense: no weight of the mb.count x mb.count matrix is zero and `bits` is not read; otherwise
+// bit m of bits[k] (device memory) says that table[k * MP + m] takes part -- a zero weight of either sign does not -- and
+// bit m of `empty` that column m has no term and is stored as +0.  One launch; pad columns are not touched.
+constexpr int kTransformMaxMembers = 64;
+inline int transform_padded(int members)
+{
+    int mp = 1;
+    while (mp < members) mp <<= 1;
+    return mp;
+}
+void launch_transform_members(hipStream_t s, int st, void* x, int pitch, int n, Members mb, float inv, const double* table,
+                              const unsigned long long* bits, unsigned long long empty, bool dense);
 
 }  // namespace fluid

@@ -2044,6 +2044,84 @@ __global__ __launch_bounds__(256) void k_pack_members_coarse(const S* __restrict
 }
 
 // ---------------------------------------------------------------------------
+// recombining ensembles (include/fluid_amd.h "recombining ensembles"): every new member of a field a linear combination of
+// the old ones, in place, X' = X T.  A lane owns ONE cell of one row in all members -- with fp16 storage too: two bytes per
+// lane, consecutive lanes consecutive bytes -- and keeps MP double accumulators in registers, MP = the member count rounded
+// up to a power of two: 2 * MP VGPRs, 128 at MP = 64, which is why a lane owns no 16-byte vector here.  It walks the old
+// members in order, kTransformAhead of their loads in flight at a time, widens each value once (as the pack does: fp16
+// widened exactly, times inv = 1 / FieldState::fscale) and adds its product with each weight of row k of the table to that
+// column's accumulator: one v_fma_f64 per term -- the product of two widened floats is exact in double, so the fused form
+// rounds exactly where mul + add would.  An accumulator starts at -0.0: -0.0 + p == p for every p, +-0, inf and NaN
+// included, so the sum starts from its first term without a flag.  All loads of a cell precede its first store by data
+// dependence: the call is in place.
+// The table: [members][MP] doubles (padding columns 0), read by every lane at the same address -- scalar loads, the weight
+// an SGPR operand of the fma.  DENSE: no weight of the members x members matrix is zero, every term is taken (a padding
+// column's accumulator may then hold anything; it is never stored).  Otherwise bits[k] holds a set bit for every column m
+// with a non-zero weight of old member k and a term is skipped by a uniform branch -- scalar work only: first per k, then
+// per group of 8 columns, then per column, so a selection costs M * (MP / 8 + 8) scalar tests and M fmas per cell.
+// `empty`: the columns with no term at all (known on the host), stored as +0.
+// Grid (blocks over the n + 2 columns, rows): row and member bases are 64-bit scalar arithmetic, a lane's own offset is
+// its column -- no index-width template, nothing of its own for fields past 4 GiB.  No LDS, no atomics.
+// ---------------------------------------------------------------------------
+constexpr int kTransformAhead = 4;
+
+template <int MP, bool DENSE>
+__device__ __forceinline__ void transform_term(double (&acc)[MP], double xd, const double* __restrict__ w, unsigned long long bits)
+{
+    if constexpr (DENSE) {
+        // 32 weights -- 64 SGPRs -- at a time: without the barrier the scheduler hoists the scalar loads of all the rows in
+        // flight to the top and spills SGPRs into VGPR lanes, a v_readlane per weight
+#pragma unroll
+        for (int g = 0; g < MP; g += 32) {
+#pragma unroll
+            for (int m = g; m < g + 32 && m < MP; ++m) acc[m] = __builtin_fma(xd, w[m], acc[m]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    } else {
+        if (bits == 0) return;
+#pragma unroll
+        for (int g = 0; g < MP; g += 8) {
+            if (MP > 8 && ((bits >> g) & 0xffull) == 0) continue;
+#pragma unroll
+            for (int m = g; m < g + 8 && m < MP; ++m)
+                if ((bits >> m) & 1ull) acc[m] = __builtin_fma(xd, w[m], acc[m]);
+        }
+    }
+}
+
+template <typename S, int MP, bool DENSE>
+__global__ __launch_bounds__(256) void k_transform_members(S* __restrict__ x, int pitch, int n, size_t ms, int members, float inv,
+                                                           const double* __restrict__ table, const unsigned long long* __restrict__ bits,
+                                                           unsigned long long empty)
+{
+    const unsigned col = blockIdx.x * 256u + threadIdx.x;
+    if (col > (unsigned)(n + 1)) return;
+    x += (size_t)blockIdx.y * (size_t)pitch + (size_t)XOFF;      // this row of member 0, scalar; the lane adds its column
+    double acc[MP];
+#pragma unroll
+    for (int m = 0; m < MP; ++m) acc[m] = -0.0;
+    int k = 0;
+    for (; k + kTransformAhead <= members; k += kTransformAhead) {
+        float f[kTransformAhead];
+#pragma unroll
+        for (int r = 0; r < kTransformAhead; ++r) f[r] = ld1(x + (size_t)(k + r) * ms + col);
+#pragma unroll
+        for (int r = 0; r < kTransformAhead; ++r) {
+            if constexpr (sizeof(S) != 4) f[r] = f[r] * inv;
+            transform_term<MP, DENSE>(acc, (double)f[r], table + (size_t)(k + r) * MP, DENSE ? 0ull : bits[k + r]);
+        }
+    }
+    for (; k < members; ++k) {
+        float f = ld1(x + (size_t)k * ms + col);
+        if constexpr (sizeof(S) != 4) f = f * inv;
+        transform_term<MP, DENSE>(acc, (double)f, table + (size_t)k * MP, DENSE ? 0ull : bits[k]);
+    }
+#pragma unroll
+    for (int m = 0; m < MP; ++m)
+        if (m < members) st1(x + (size_t)m * ms + col, (empty >> m) & 1ull ? 0.0f : (float)acc[m]);
+}
+
+// ---------------------------------------------------------------------------
 // launch wrappers (host).  Shapes are validated by the caller (fluid_solver).
 // `st` selects the field storage type the untyped pointers refer to.
 // ---------------------------------------------------------------------------
@@ -2346,6 +2424,33 @@ void launch_pack_members_coarse(hipStream_t s, int st, const void* x, int pitch,
         FLUID_COARSE_CASE(6);
     }
 #undef FLUID_COARSE_CASE
+}
+
+// mb.count in [1, 64] (fluid_solver checks it); `table`: transform_padded(mb.count) doubles per old member; `bits` may be
+// null when `dense`
+void launch_transform_members(hipStream_t s, int st, void* x, int pitch, int n, Members mb, float inv, const double* table,
+                              const unsigned long long* bits, unsigned long long empty, bool dense)
+{
+    const dim3 grid(cdiv((unsigned)(n + 2), 256), (unsigned)(n + 2));
+#define FLUID_TRANSFORM_CASE(MP)                                                                                                           \
+    case MP:                                                                                                                               \
+        if (dense)                                                                                                                         \
+            FLUID_BY_STORAGE(st, hipLaunchKernelGGL((k_transform_members<S, MP, true>), grid, dim3(256), 0, s, (S*)x, pitch, n, mb.stride, \
+                                                    mb.count, inv, table, bits, empty));                                                   \
+        else                                                                                                                               \
+            FLUID_BY_STORAGE(st, hipLaunchKernelGGL((k_transform_members<S, MP, false>), grid, dim3(256), 0, s, (S*)x, pitch, n, mb.stride, \
+                                                    mb.count, inv, table, bits, empty));                                                   \
+        break
+    switch (transform_padded(mb.count)) {
+        FLUID_TRANSFORM_CASE(1);
+        FLUID_TRANSFORM_CASE(2);
+        FLUID_TRANSFORM_CASE(4);
+        FLUID_TRANSFORM_CASE(8);
+        FLUID_TRANSFORM_CASE(16);
+        FLUID_TRANSFORM_CASE(32);
+        FLUID_TRANSFORM_CASE(64);
+    }
+#undef FLUID_TRANSFORM_CASE
 }
 
 }  // namespace fluid

@@ -1859,6 +1859,10 @@ int fluid_destroy(fluid_ctx* c)
     if (c->red.d_mean) (void)hipFree(c->red.d_mean);
     if (c->red.d_var) (void)hipFree(c->red.d_var);
     if (c->stage.dev) (void)hipFree(c->stage.dev);
+    for (hipEvent_t ev : c->xform.copied)
+        if (ev) (void)hipEventDestroy(ev);
+    if (c->xform.dev) (void)hipFree(c->xform.dev);
+    if (c->xform.host) (void)hipHostFree(c->xform.host);
     if (c->d_partials) (void)hipFree(c->d_partials);
     if (c->scalar_ready) (void)hipEventDestroy(c->scalar_ready);
     if (c->own_arena && c->arena) (void)hipFree(c->arena);
@@ -2721,6 +2725,128 @@ int fluid_unpack_members(fluid_ctx* c, int field, int first, int count, const vo
     if (!c) return fail(FLUID_E_INVALID, "fluid_unpack_members: null context");
     TRY(check_member_move(c, "fluid_unpack_members", field, first, &count, src_dev, &member_stride));
     return unpack_range(c, field, first, count, static_cast<const float*>(src_dev), member_stride);
+}
+
+// ---- recombining ensembles: fluid_transform_members / fluid_select_members -------------------------------------------
+// (include/fluid_amd.h "recombining ensembles".)  One body: a selection is the transform with its one-hot matrix.  Per
+// call one table -- the weights widened to double (exact), [M][MP], then one word per old member with a bit for every
+// non-zero weight -- copied on the context's stream from pinned memory (fluid_ctx.h: TransformTables); per listed field
+// one launch.  No wait anywhere; the launches belong to none of the timing categories.
+static size_t transform_table_bytes(int members)
+{
+    return (size_t)members * (size_t)fluid::transform_padded(members) * sizeof(double) + (size_t)members * sizeof(unsigned long long);
+}
+
+static int ensure_transform(fluid_ctx* c, const char* call)
+{
+    TransformTables& t = c->xform;
+    if (t.dev) return FLUID_OK;
+    const size_t slot = const_pad(transform_table_bytes(c->members)), bytes = slot * TransformTables::kSlots;
+    char *dev = nullptr, *host = nullptr;
+    hipError_t e = hipMalloc((void**)&dev, bytes);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&host, bytes, hipHostMallocDefault);
+    for (int k = 0; e == hipSuccess && k < TransformTables::kSlots; ++k)
+        if (!t.copied[k]) e = hipEventCreateWithFlags(&t.copied[k], hipEventDisableTiming);
+    if (e != hipSuccess) {          // (events already made stay with the context: the next call takes them, fluid_destroy frees them)
+        (void)hipGetLastError();
+        if (dev) (void)hipFree(dev);
+        if (host) (void)hipHostFree(host);
+        return fail(e == hipErrorOutOfMemory ? FLUID_E_NOMEM : FLUID_E_HIP, "%s: allocating weight tables of %zu bytes: %s", call, bytes,
+                    hipGetErrorString(e));
+    }
+    t.dev = dev;
+    t.host = host;
+    t.slot = slot;
+    return FLUID_OK;
+}
+
+// weights: M * M floats, weights[k * M + m] the weight of OLD member k in NEW member m, all finite (the entry points check)
+static int transform_body(fluid_ctx* c, const char* call, const int* fields, int nfields, const float* weights)
+{
+    const int M = c->members, MP = fluid::transform_padded(M);
+    TRY(ensure_transform(c, call));
+    TransformTables& t = c->xform;
+    const int s = t.next;
+    if (t.in_use[s]) HIP_TRY(hipEventSynchronize(t.copied[s]));      // a formality unless kSlots calls are still queued
+    double* table = reinterpret_cast<double*>(t.host + (size_t)s * t.slot);
+    unsigned long long* bits = reinterpret_cast<unsigned long long*>(table + (size_t)M * MP);
+    unsigned long long used = 0;
+    bool dense = true;
+    for (int k = 0; k < M; ++k) {
+        unsigned long long row = 0;
+        for (int m = 0; m < MP; ++m) {
+            const float w = m < M ? weights[(size_t)k * M + m] : 0.0f;
+            table[(size_t)k * MP + m] = (double)w;
+            if (w != 0.0f) row |= 1ull << m;
+            else if (m < M) dense = false;
+        }
+        bits[k] = row;
+        used |= row;
+    }
+    const unsigned long long empty = ~used;                          // (bits past M are never looked at)
+    char* dev = t.dev + (size_t)s * t.slot;
+    HIP_TRY(hipMemcpyAsync(dev, table, transform_table_bytes(M), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipEventRecord(t.copied[s], c->stream));
+    t.in_use[s] = true;
+    t.next = (s + 1) % TransformTables::kSlots;
+    const double* dtable = reinterpret_cast<const double*>(dev);
+    const unsigned long long* dbits = reinterpret_cast<const unsigned long long*>(dtable + (size_t)M * MP);
+    for (int k = 0; k < nfields; ++k) {
+        const int f = fields[k];
+        const float inv = c->st != fluid::STORAGE_F32 ? 1.0f / c->field[f].fscale : 1.0f;      // as pack_range sees the field
+        TRY(materialize(c, f, /*keep_scale=*/inv != 1.0f));
+        fluid::launch_transform_members(c->stream, c->st, c->ptr(f), c->pitch, c->n, c->mb(), inv, dtable, dbits, empty, dense);
+        HIP_TRY(hipGetLastError());
+        wrote(c, f, kEverywhere);                                    // plain values (scale 1), nothing owed
+    }
+    return FLUID_OK;
+}
+
+// what both calls refuse beyond their own array, before anything is launched or changed
+static int check_transform(const fluid_ctx* c, const char* call, const int* fields, int nfields)
+{
+    if (nfields < 1 || nfields > FLUID_NFIELDS) return fail(FLUID_E_INVALID, "%s: nfields %d outside [1, %d]", call, nfields, FLUID_NFIELDS);
+    for (int k = 0; k < nfields; ++k) {
+        if (!c->valid_field(fields[k])) return fail(FLUID_E_INVALID, "%s: bad field id %d (fields[%d])", call, fields[k], k);
+        for (int j = 0; j < k; ++j)
+            if (fields[j] == fields[k]) return fail(FLUID_E_INVALID, "%s: field %d is listed twice (fields[%d] and fields[%d])", call, fields[k], j, k);
+    }
+    if (c->members > FLUID_TRANSFORM_MAX_MEMBERS)
+        return fail(FLUID_E_INVALID, "%s: this context has %d members, above FLUID_TRANSFORM_MAX_MEMBERS = %d", call, c->members,
+                    FLUID_TRANSFORM_MAX_MEMBERS);
+    return refuse_slabs(c, call);
+}
+
+int fluid_transform_members(fluid_ctx* c, const int* fields, int nfields, const float* weights)
+{
+    static_assert(FLUID_TRANSFORM_MAX_MEMBERS == fluid::kTransformMaxMembers, "the header's cap is the kernel's");
+    if (!fields) return fail(FLUID_E_INVALID, "fluid_transform_members: null array `fields`");
+    if (!weights) return fail(FLUID_E_INVALID, "fluid_transform_members: null array `weights`");
+    if (!c) return fail(FLUID_E_INVALID, "fluid_transform_members: null context");
+    TRY(check_transform(c, "fluid_transform_members", fields, nfields));
+    const int M = c->members;
+    for (int k = 0; k < M; ++k)
+        for (int m = 0; m < M; ++m)
+            if (!std::isfinite(weights[(size_t)k * M + m]))
+                return fail(FLUID_E_INVALID, "fluid_transform_members: weights[%d * M + %d] (old member k = %d, new member m = %d) is not finite",
+                            k, m, k, m);
+    return transform_body(c, "fluid_transform_members", fields, nfields, weights);
+}
+
+int fluid_select_members(fluid_ctx* c, const int* fields, int nfields, const int* source)
+{
+    if (!fields) return fail(FLUID_E_INVALID, "fluid_select_members: null array `fields`");
+    if (!source) return fail(FLUID_E_INVALID, "fluid_select_members: null array `source`");
+    if (!c) return fail(FLUID_E_INVALID, "fluid_select_members: null context");
+    TRY(check_transform(c, "fluid_select_members", fields, nfields));
+    const int M = c->members;
+    std::vector<float> onehot((size_t)M * M, 0.0f);
+    for (int m = 0; m < M; ++m) {
+        if (source[m] < 0 || source[m] >= M)
+            return fail(FLUID_E_INVALID, "fluid_select_members: source[%d] = %d (new member m = %d) outside [0, %d)", m, source[m], m, M);
+        onehot[(size_t)source[m] * M + m] = 1.0f;
+    }
+    return transform_body(c, "fluid_select_members", fields, nfields, onehot.data());
 }
 
 // The staging buffer of the bulk host copies: g = max(1, min(M, 64 MiB / member bytes)) dense members.  The 64 MiB is a

@@ -200,6 +200,27 @@ class FluidSolver:
         if wait:
             self.synchronize()
 
+    # -- recombining an ensemble in place: every new member a linear combination of the old ones
+    def transform(self, weights, fields=("u", "v", "dens")):
+        """X' = X T per cell of each listed field, in place, one launch per field and no wait: weights[k][m] is the weight
+        of OLD member k in NEW member m -- anything np.asarray(.., np.float32) turns into a (members, members) array.  The
+        sum runs over the non-zero weights in member order, in double, rounded once (include/fluid_amd.h, "recombining
+        ensembles").  members <= capi.TRANSFORM_MAX_MEMBERS."""
+        w = np.ascontiguousarray(np.asarray(weights, np.float32))
+        if w.shape != (self.members, self.members):
+            raise ValueError("weights must have shape (%d, %d), got %s" % (self.members, self.members, w.shape))
+        ids = [_fid(f) for f in fields]
+        capi.check(capi.lib().fluid_transform_members(self._h, (C.c_int * len(ids))(*ids), len(ids), _mf(w)))
+
+    def select(self, source, fields=("u", "v", "dens")):
+        """New member m := old member source[m] in each listed field, in place: branch from one member, resample, permute.
+        Bit copies (the transform with the one-hot matrix, in the same launch)."""
+        src = [int(s) for s in source]
+        if len(src) != self.members:
+            raise ValueError("source must name %d members, got %d" % (self.members, len(src)))
+        ids = [_fid(f) for f in fields]
+        capi.check(capi.lib().fluid_select_members(self._h, (C.c_int * len(ids))(*ids), len(ids), (C.c_int * len(src))(*src)))
+
     def run(self, nsteps, every=0, fields=(), sources=None, out=None, dt=DT, diff=DIFF, visc=VIS, iters=ITERS, use_sources=False,
             wait=True, coarse=None):
         """nsteps steps without the host in the loop.  `sources`: a dense device array (3, members, N+2, N+2) -- u_prev,

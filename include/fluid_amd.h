@@ -407,6 +407,52 @@ int fluid_run_coarse(fluid_ctx *ctx, float dt, float diff, float visc, const flu
 int fluid_run_members_coarse(fluid_ctx *ctx, const float *dt, const float *diff, const float *visc,
                              const fluid_run_plan *plan, int factor, int *snapshots_written);
 
+/* ---- recombining ensembles: every new member a linear combination of the old ones, in place ---------------------
+ * M = fluid_members(ctx), W = N + 2.  Branching a Monte-Carlo set from one member, replacing a member by a copy of
+ * another, resampling, inflation, recentring, an ensemble-space Kalman update: X' = X T with an M x M matrix T, per cell.
+ *
+ * - fluid_transform_members: `weights` is host memory, M*M floats; weights[k*M + m] is the weight of OLD member k in NEW
+ *   member m.  `fields`: nfields distinct field ids, host memory.  One kernel launch per listed field whatever M is,
+ *   enqueued on the context's stream, no wait; both host arrays belong to the caller again when the call returns.
+ *   Definition -- per listed field, per cell of the W x W array (ghost ring included), per new member m; pad columns are
+ *   neither read nor written:
+ *    1. x_k is the float fluid_pack_members would show for old member k right before the call: the field's lazy state is
+ *       settled first; with fp16 storage each value is widened exactly and a pressure scale divided back in float, exactly
+ *       as the pack does.
+ *    2. The terms are the k in increasing order with weights[k*M + m] != 0.  A zero weight of either sign takes no part:
+ *       a NaN or inf member with weight 0 poisons nobody.
+ *    3. With no term, y = +0.0f.
+ *    4. Otherwise s = (double)x_k * (double)w_k for the first term, then s = s + (double)x_k * (double)w_k for each further
+ *       term in member order, and y = (float)s: ONE rounding to nearest even; float denormals are kept, overflow goes to
+ *       +-inf.  Every product is exact in double (24 + 24 significand bits fit in 53, the exponent range is ample), so a
+ *       fused and an unfused multiply-add give the same bits -- which is why the weights are float and not double.
+ *    5. Every new member's cell is stored as fluid_unpack_members of ALL members would store y: narrow(y), with fp16
+ *       storage one more rounding to nearest even.  Afterwards the field holds plain values (scale 1) and owes itself
+ *       nothing.
+ *    6. All M old values of a cell are read before any new value of that cell is stored: the call is in place and means
+ *       what an out-of-place one would.
+ *    7. A NaN result is a NaN; its sign and payload are not specified.
+ *   The order is part of the contract: the same bits on every call, for every launch shape; no matrix instructions, no
+ *   atomics.  The ghost ring is transformed cell by cell like the interior: ghost columns and rows stay the exact +-mirror
+ *   of their neighbours (rounding is symmetric), the corners need not; fluid_op_set_bnd restores them for a caller who
+ *   wants that.
+ * - fluid_select_members: new member m := old member source[m], every source[m] in [0, M) (host memory).  It IS
+ *   fluid_transform_members with the one-hot matrix, in the same body: new members are bit copies for every non-NaN value,
+ *   -0 included.  Branch-from-one, resampling and permutation, in place.
+ * Any M in [1, FLUID_TRANSFORM_MAX_MEMBERS] works, one-member contexts included.  Above that the accumulators of a cell no
+ * longer fit the register file: fluid_pack_members -> outside code -> fluid_unpack_members remains the route there.
+ * The weight tables are library-owned device and pinned memory outside the arena (fluid_arena_bytes_ensemble is unchanged),
+ * allocated by the first such call and freed by fluid_destroy; a failed allocation is FLUID_E_NOMEM and leaves the context
+ * usable.  Successive calls with different weights need no wait.
+ * Refusals, all FLUID_E_INVALID with a message that names the call and, where it applies, the k, m or list position, found
+ * before anything is launched or any state changes, null pointers before the context is looked at: a null `fields`,
+ * `weights` or `source`, a null context; nfields outside [1, 12]; a bad field id; a field listed twice; a non-finite
+ * weight; a source[m] outside [0, M); M > FLUID_TRANSFORM_MAX_MEMBERS (the message gives both numbers); row slabs.
+ * The launches belong to none of the fluid_timing categories. */
+#define FLUID_TRANSFORM_MAX_MEMBERS 64
+int fluid_transform_members(fluid_ctx *ctx, const int *fields, int nfields, const float *weights);
+int fluid_select_members(fluid_ctx *ctx, const int *fields, int nfields, const int *source);
+
 int fluid_set_jacobi_variant(fluid_ctx *ctx, int variant);
 /* How FLUID_JACOBI_TB divides by `beta` in a solve with these coefficients (diagnostic; runs the on-device proof
  * if this beta has not been seen): 0 true division, 2 double-precision reciprocal, 3 two-term float reciprocal
