@@ -117,6 +117,7 @@ SIGNATURES = {
     "fluid_member_moments": [_ctx, _i, C.POINTER(C.c_double), C.POINTER(C.c_double)],
     "fluid_ensemble_stats": [_ctx, _i, _MF, _MF],
     "fluid_ensemble_stats_ptr": [_ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)],
+    "fluid_member_gram": [_ctx, _i, _i, C.POINTER(C.c_double)],
     "fluid_pack_members": [_ctx, _i, _i, _i, C.c_void_p, C.c_size_t],
     "fluid_unpack_members": [_ctx, _i, _i, _i, C.c_void_p, C.c_size_t],
     "fluid_download_members": [_ctx, _i, _MF],

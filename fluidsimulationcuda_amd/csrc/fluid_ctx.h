@@ -96,9 +96,9 @@ struct ConstRing {
     std::vector<hipEvent_t> free_events;
 };
 
-// What the ensemble diagnostics (fluid_*_members maxima, fluid_member_moments, fluid_ensemble_stats) need beyond the
-// fields: library-owned, outside the arena, each part allocated at the first call that needs it (fluid_solver.hip:
-// ensure_member_results, ensure_stats) and freed in fluid_destroy.
+// What the ensemble diagnostics (fluid_*_members maxima, fluid_member_moments, fluid_ensemble_stats, fluid_member_gram) need
+// beyond the fields: library-owned, outside the arena, each part allocated at the first call that needs it (fluid_solver.hip:
+// ensure_member_results, ensure_stats, ensure_gram) and freed in fluid_destroy.
 struct EnsembleReduce {
     unsigned int* d_max = nullptr;        // one result word per member (k_residual / k_absmax2 with a result stride of 1)
     double2* d_moments = nullptr;         // one {sum, sum of squares} per member
@@ -106,6 +106,9 @@ struct EnsembleReduce {
     char* host = nullptr;                 // pinned twin of the larger of the two result arrays
     float *d_mean = nullptr, *d_var = nullptr;   // the two statistics fields, field_floats floats each, pads zero
     bool have_stats = false;              // a fluid_ensemble_stats has filled them
+    // fluid_member_gram (ensure_gram): gram_blocks() per-block MP x MP matrices, MP = gram_padded(members), the folded
+    // matrix and its pinned twin
+    double *d_gram_partials = nullptr, *d_gram = nullptr, *gram_host = nullptr;
 };
 
 // The bulk host copies (fluid_download_members / fluid_upload_members) go through a dense float staging buffer on the

@@ -181,5 +181,14 @@ inline int transform_padded(int members)
 }
 void launch_transform_members(hipStream_t s, int st, void* x, int pitch, int n, Members mb, float inv, const double* table,
                               const unsigned long long* bits, unsigned long long empty, bool dense);
+// The Gram matrix of the members of a field over the interior cells (include/fluid_amd.h "ensemble diagnostics",
+// fluid_member_gram): out[k * MP + m], k <= m < mb.count, MP = gram_padded(mb.count) = the sum of a_k * a_m in double, a_k =
+// widen(x_k) * inv, less the per-cell mean over the members with `centre`; entries below the diagonal are not written.
+// mb.count in [1, kTransformMaxMembers].  Two launches whatever the member count: gram_blocks(n, members) blocks each leave
+// their MP x MP matrix in `partials` (gram_blocks * MP * MP doubles of scratch), a second kernel adds them in a fixed order.
+inline int gram_padded(int members) { return members > 8 ? transform_padded(members) : 8; }
+int gram_blocks(int n, int members);
+void launch_member_gram(hipStream_t s, int st, const void* x, int pitch, int n, Members mb, float inv, bool centre, double* partials,
+                        double* out);
 
 }  // namespace fluid

@@ -1729,6 +1729,151 @@ __global__ __launch_bounds__(64) void k_fold_moments(const double2* __restrict__
     if (threadIdx.x == 0) out[blockIdx.x] = make_double2(s, q);
 }
 
+// The M x M matrix of inner products between the members of a field, or between their anomalies about the ensemble mean
+// (include/fluid_amd.h "ensemble diagnostics", fluid_member_gram): a tall-skinny A^T A, interior cells x members, where
+// every stored value is read from memory ONCE.  MP = the member count padded to 8, 16, 32 or 64 (padding members are
+// zeros; their rows and columns are never read back).  A block stages a chunk of CH = 4096 / MP consecutive interior
+// cells of one row in all members into LDS as doubles, [cell][member], R = MP + 2 doubles per cell: a lane loads one value
+// (ld1: consecutive lanes, consecutive columns), widens it as the pack does and stores it; the two doubles of padding
+// keep a cell 16-byte aligned and spread the lanes of a store over the banks.  CENTRE: one lane per cell then forms the
+// mean chain of fluid_ensemble_stats in member order (IEEE double, no contraction) and subtracts it in place -- M adds per
+// cell against MP^2 fmas.
+// Each WAVE keeps the whole matrix in registers: lane (ta, tb) of the 8 x 8 lane grid owns the T x T tile of members
+// T * ta .., T * tb .., T = MP / 8 -- 64 double accumulators at MP = 64 -- and the four waves of a block take the cells
+// wave, wave + 4, .. of the chunk.  Per cell a lane reads its T + T operands from LDS (ds_read_b128; all lanes read the same
+// cell, so equal ta or tb broadcast) and issues T * T v_fma_f64.  (ta, tb) is laid over the lanes so that each of the four
+// 16-lane groups a ds_read_b128 is served in holds 4 values of ta and 4 of tb: their addresses lie in distinct banks.
+// The lower triangle's lanes (ta > tb) compute their tiles like the others and drop them: a wave runs no faster with them
+// masked.  The next chunk's 16 values per lane are loaded before the fmas of the current one.
+// An accumulator starts at -0.0, so a sum starts from its first term.  At the end the four waves' matrices are added through
+// LDS in wave order and the block's matrix (tiles with ta <= tb) goes to partials[block][MP * MP] with plain stores;
+// k_fold_gram adds the blocks' partials per entry in a fixed order.  No floating-point atomics, no matrix instructions:
+// the order of every addition is fixed by (n, members, storage, centre) alone.  Blocks stride over the chunks; row and
+// member bases are 64-bit arithmetic, so fields past 4 GiB need nothing of their own.
+constexpr int kGramChunkValues = 4096;       // cells x padded members of one staged chunk: 32 KiB of doubles
+constexpr int kGramLoads = kGramChunkValues / 256;
+
+template <int T>
+__device__ __forceinline__ void gram_operands(const double* __restrict__ p, double (&o)[T])
+{
+    if constexpr (T == 1) o[0] = p[0];
+    else {
+#pragma unroll
+        for (int i = 0; i < T; i += 2) {
+            const double2 v = *reinterpret_cast<const double2*>(p + i);
+            o[i] = v.x; o[i + 1] = v.y;
+        }
+    }
+}
+
+template <typename S, int MP, bool CENTRE>
+__global__ __launch_bounds__(256) void k_member_gram(const S* __restrict__ x, int pitch, int n, size_t ms, int members, float inv,
+                                                     int cpr, unsigned chunks, double* __restrict__ partials)
+{
+    constexpr int T = MP / 8, CH = kGramChunkValues / MP, R = MP + 2;
+    static_assert(MP * MP <= CH * R, "the block's matrix is folded in the staging memory");
+    __shared__ __attribute__((aligned(16))) double stage[CH * R];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int l5 = lane & 31, q = l5 >> 2;
+    const int ta = 4 * (lane >> 5) + (q >> 1), tb = 4 * ((0x96 >> q) & 1) + (l5 & 3);
+    double acc[T][T];
+#pragma unroll
+    for (int i = 0; i < T; ++i)
+#pragma unroll
+        for (int j = 0; j < T; ++j) acc[i][j] = -0.0;
+
+    float f[kGramLoads];
+    // chunk c: cells col0 .. col0 + nc - 1 of interior row 1 + c / cpr; value v = t + 256 * r of it: cell v % CH, member v / CH
+    auto cells_of = [&](unsigned c) { return min(CH, n - (int)(c % (unsigned)cpr) * CH); };
+    auto load = [&](unsigned c) {
+        const int nc = cells_of(c);
+        const S* row = x + (size_t)(1 + c / (unsigned)cpr) * (size_t)pitch + (size_t)(XOFF + 1) + (size_t)(c % (unsigned)cpr) * CH;
+#pragma unroll
+        for (int r = 0; r < kGramLoads; ++r) {
+            const int v = t + 256 * r, cell = v % CH, k = v / CH;
+            float a = 0.0f;
+            if (cell < nc && k < members) {
+                a = ld1(row + (size_t)k * ms + cell);
+                if constexpr (sizeof(S) != 4) a = a * inv;
+            }
+            f[r] = a;
+        }
+    };
+
+    unsigned chunk = blockIdx.x;              // (gridDim.x <= chunks: every block has a chunk)
+    load(chunk);
+    for (; chunk < chunks; chunk += gridDim.x) {
+        const int nc = cells_of(chunk);
+#pragma unroll
+        for (int r = 0; r < kGramLoads; ++r) {
+            const int v = t + 256 * r;
+            stage[(v % CH) * R + v / CH] = (double)f[r];
+        }
+        __syncthreads();
+        if constexpr (CENTRE) {
+            const double dm = (double)members;
+            for (int c = t; c < nc; c += 256) {
+                double* p = stage + c * R;
+                double s = p[0];
+                for (int m = 1; m < members; ++m) s = s + p[m];
+                const double mu = s / dm;
+                for (int m = 0; m < members; ++m) p[m] = p[m] - mu;
+            }
+            __syncthreads();
+        }
+        if (chunk + gridDim.x < chunks) load(chunk + gridDim.x);
+        for (int c = wave; c < nc; c += 4) {
+            double a[T], b[T];
+            gram_operands<T>(stage + c * R + ta * T, a);
+            gram_operands<T>(stage + c * R + tb * T, b);
+#pragma unroll
+            for (int i = 0; i < T; ++i)
+#pragma unroll
+                for (int j = 0; j < T; ++j) acc[i][j] = __builtin_fma(a[i], b[j], acc[i][j]);
+        }
+        __syncthreads();
+    }
+
+    // ((wave 0 + wave 1) + wave 2) + wave 3, every lane its own entries; the last wave stores the block's matrix
+    double* out = partials + (size_t)blockIdx.x * (MP * MP);
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        if (wave == w) {
+#pragma unroll
+            for (int i = 0; i < T; ++i)
+#pragma unroll
+                for (int j = 0; j < T; ++j) {
+                    const int at = (ta * T + i) * MP + tb * T + j;
+                    if (w > 0) acc[i][j] = stage[at] + acc[i][j];
+                    if (w < 3) stage[at] = acc[i][j];
+                    else if (ta <= tb) out[at] = acc[i][j];
+                }
+        }
+        if (w < 3) __syncthreads();
+    }
+}
+
+// Entry e of the padded matrix: the sum over the blocks' partials in a fixed order -- 16 entries per block, 16 lanes per
+// entry: lane p adds partials p, p + 16, .. in index order from -0.0, then the 16 sums are added in index order.  Entries
+// of tiles below the diagonal (tile side T) were not stored and are not read; out[e] of them is left alone.
+__global__ __launch_bounds__(256) void k_fold_gram(const double* __restrict__ partials, int count, int mp, int tile, double* __restrict__ out)
+{
+    __shared__ double part[16][16];
+    const int e = blockIdx.x * 16 + (threadIdx.x & 15), p0 = threadIdx.x >> 4;
+    const bool live = (e / mp) / tile <= (e % mp) / tile;
+    double s = -0.0;
+    if (live)
+        for (int p = p0; p < count; p += 16) s = s + partials[(size_t)p * (size_t)(mp * mp) + e];
+    part[p0][threadIdx.x & 15] = s;
+    __syncthreads();
+    if (threadIdx.x < 16 && live) {
+        s = part[0][threadIdx.x];
+#pragma unroll
+        for (int p = 1; p < 16; ++p) s = s + part[p][threadIdx.x];
+        out[e] = s;
+    }
+}
+
 // Across the members, per cell (ghost cells included): mean and population variance as float fields in the layout of a
 // field, by the two-pass definition of include/fluid_amd.h -- all in double, member order, the first member's value (not
 // 0.0) as the start of both chains.  One lane per VW = 4 (fp16: 8) consecutive columns of a row, vector v of a row covering
@@ -2368,6 +2513,46 @@ void launch_member_moments(hipStream_t s, int st, const void* x, int pitch, int 
     FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_member_moments<S>, dim3(blocks, mb.count), dim3(256), 0, s, (const S*)x, pitch, n, mb.stride,
                                             partials));
     hipLaunchKernelGGL(k_fold_moments, dim3(mb.count), dim3(64), 0, s, partials, blocks, out);
+}
+
+// chunks of one member's interior: gram_padded / 4096 fix the cells per chunk, a row is cut into whole chunks and a last
+// shorter one
+static inline unsigned gram_chunks(int n, int mp)
+{
+    const int ch = kGramChunkValues / mp;
+    return (unsigned)n * (unsigned)((n + ch - 1) / ch);
+}
+
+// at most two (MP = 64: 128 VGPRs of accumulators) or four resident blocks per CU, at least one chunk per block
+int gram_blocks(int n, int members)
+{
+    const int mp = gram_padded(members);
+    return (int)std::min<unsigned>(gram_chunks(n, mp), mp == 64 ? 512u : 1024u);
+}
+
+void launch_member_gram(hipStream_t s, int st, const void* x, int pitch, int n, Members mb, float inv, bool centre, double* partials,
+                        double* out)
+{
+    const int mp = gram_padded(mb.count), blocks = gram_blocks(n, mb.count);
+    const int cpr = (n + kGramChunkValues / mp - 1) / (kGramChunkValues / mp);
+    const unsigned chunks = gram_chunks(n, mp);
+#define FLUID_GRAM_CASE(MP)                                                                                                               \
+    case MP:                                                                                                                              \
+        if (centre)                                                                                                                       \
+            FLUID_BY_STORAGE(st, hipLaunchKernelGGL((k_member_gram<S, MP, true>), dim3(blocks), dim3(256), 0, s, (const S*)x, pitch, n,   \
+                                                    mb.stride, mb.count, inv, cpr, chunks, partials));                                    \
+        else                                                                                                                              \
+            FLUID_BY_STORAGE(st, hipLaunchKernelGGL((k_member_gram<S, MP, false>), dim3(blocks), dim3(256), 0, s, (const S*)x, pitch, n,  \
+                                                    mb.stride, mb.count, inv, cpr, chunks, partials));                                    \
+        break
+    switch (mp) {
+        FLUID_GRAM_CASE(8);
+        FLUID_GRAM_CASE(16);
+        FLUID_GRAM_CASE(32);
+        FLUID_GRAM_CASE(64);
+    }
+#undef FLUID_GRAM_CASE
+    hipLaunchKernelGGL(k_fold_gram, dim3(mp * mp / 16), dim3(256), 0, s, partials, blocks, mp, mp / 8, out);
 }
 
 void launch_ensemble_stats(hipStream_t s, int st, const void* x, int pitch, int n, Members mb, float* mean, float* var)

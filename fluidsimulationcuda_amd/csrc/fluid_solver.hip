@@ -1858,6 +1858,9 @@ int fluid_destroy(fluid_ctx* c)
     if (c->red.host) (void)hipHostFree(c->red.host);
     if (c->red.d_mean) (void)hipFree(c->red.d_mean);
     if (c->red.d_var) (void)hipFree(c->red.d_var);
+    if (c->red.d_gram_partials) (void)hipFree(c->red.d_gram_partials);
+    if (c->red.d_gram) (void)hipFree(c->red.d_gram);
+    if (c->red.gram_host) (void)hipHostFree(c->red.gram_host);
     if (c->stage.dev) (void)hipFree(c->stage.dev);
     for (hipEvent_t ev : c->xform.copied)
         if (ev) (void)hipEventDestroy(ev);
@@ -2528,6 +2531,52 @@ int fluid_member_moments(fluid_ctx* c, int field, double* sum, double* sumsq)
         if (sum) sum[m] = h[m].x;
         if (sumsq) sumsq[m] = h[m].y;
     }
+    return FLUID_OK;
+}
+
+// the scratch and the result of fluid_member_gram, sized for this context's N and M once
+static int ensure_gram(fluid_ctx* c)
+{
+    EnsembleReduce& r = c->red;
+    if (r.d_gram) return FLUID_OK;
+    const int mp = fluid::gram_padded(c->members);
+    const size_t matrix = (size_t)mp * mp * sizeof(double), parts = matrix * (size_t)fluid::gram_blocks(c->n, c->members);
+    double *d_part = nullptr, *d_out = nullptr, *host = nullptr;
+    hipError_t e = hipMalloc((void**)&d_part, parts);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_out, matrix);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&host, matrix, hipHostMallocDefault);
+    if (e != hipSuccess) {
+        if (d_part) (void)hipFree(d_part);
+        if (d_out) (void)hipFree(d_out);
+        (void)hipGetLastError();
+        return fail(e == hipErrorOutOfMemory ? FLUID_E_NOMEM : FLUID_E_HIP, "fluid_member_gram: allocating %zu bytes of partial matrices: %s",
+                    parts + matrix, hipGetErrorString(e));
+    }
+    r.d_gram_partials = d_part;
+    r.d_gram = d_out;
+    r.gram_host = host;
+    return FLUID_OK;
+}
+
+int fluid_member_gram(fluid_ctx* c, int field, int centre, double* gram)
+{
+    if (!gram) return fail(FLUID_E_INVALID, "fluid_member_gram: null array `gram`");
+    if (!c) return fail(FLUID_E_INVALID, "fluid_member_gram: null context");
+    if (!c->valid_field(field)) return fail(FLUID_E_INVALID, "fluid_member_gram: bad field id %d", field);
+    if (c->members > FLUID_TRANSFORM_MAX_MEMBERS)
+        return fail(FLUID_E_INVALID, "fluid_member_gram: this context has %d members, above FLUID_TRANSFORM_MAX_MEMBERS = %d", c->members,
+                    FLUID_TRANSFORM_MAX_MEMBERS);
+    TRY(refuse_slabs(c, "fluid_member_gram"));
+    TRY(ensure_gram(c));
+    const float inv = c->st != fluid::STORAGE_F32 ? 1.0f / c->field[field].fscale : 1.0f;      // as pack_range sees the field
+    TRY(materialize(c, field, /*keep_scale=*/inv != 1.0f));
+    fluid::launch_member_gram(c->stream, c->st, c->ptr(field), c->pitch, c->n, c->mb(), inv, centre != 0, c->red.d_gram_partials, c->red.d_gram);
+    HIP_TRY(hipGetLastError());
+    const int M = c->members, mp = fluid::gram_padded(M);
+    HIP_TRY(hipMemcpyAsync(c->red.gram_host, c->red.d_gram, (size_t)mp * mp * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int k = 0; k < M; ++k)                    // the upper triangle was computed; the lower one is its mirror
+        for (int m = k; m < M; ++m) gram[(size_t)k * M + m] = gram[(size_t)m * M + k] = c->red.gram_host[(size_t)k * mp + m];
     return FLUID_OK;
 }
 

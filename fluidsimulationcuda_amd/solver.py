@@ -370,6 +370,14 @@ class FluidSolver:
         capi.check(capi.lib().fluid_member_moments(self._h, _fid(field), s.ctypes.data_as(dp), q.ctypes.data_as(dp)))
         return s, q
 
+    def member_gram(self, field, centre=False):
+        """The (members, members) float64 matrix of inner products between the members of a field over the interior cells;
+        with `centre`, between their anomalies about the per-cell ensemble mean.  Bit-symmetric, the same bits on every
+        call (include/fluid_amd.h, "ensemble diagnostics": fluid_member_gram).  members <= capi.TRANSFORM_MAX_MEMBERS."""
+        g = np.empty((self.members, self.members), np.float64)
+        capi.check(capi.lib().fluid_member_gram(self._h, _fid(field), 1 if centre else 0, g.ctypes.data_as(C.POINTER(C.c_double))))
+        return g
+
     def ensemble_stats(self, field, mean=True, variance=True):
         """Per cell across the members: (mean, population variance) as (N+2, N+2) float32 arrays; None for the one not
         asked for.  With neither, the statistics are only enqueued and stay on the device (ensemble_stats_ptr)."""

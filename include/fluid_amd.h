@@ -270,9 +270,9 @@ int fluid_absmax_velocity(fluid_ctx *ctx, int u, int v, float *out);
  * M = fluid_members(ctx); all arrays are host memory; every call is synchronous like fluid_residual unless said
  * otherwise; none alters what a later download or step sees (a field's lazy state is settled first, as by
  * fluid_residual, not lost).  The launch count of a call does not depend on M: one kernel per maxima call, two per
- * moments call, one per statistics call.  Results and scratch are library-owned and outside the arena, allocated at the
- * first call that needs them (the two statistics fields: 2 x field_floats floats) and freed by fluid_destroy; an
- * allocation that fails is FLUID_E_NOMEM and leaves the context usable.
+ * moments or Gram call, one per statistics call.  Results and scratch are library-owned and outside the arena,
+ * allocated at the first call that needs them (the two statistics fields: 2 x field_floats floats) and freed by
+ * fluid_destroy; an allocation that fails is FLUID_E_NOMEM and leaves the context usable.
  *
  * Definitions:
  * - fluid_residual_members, fluid_absmax_velocity_members: out[m] = what fluid_residual / fluid_absmax_velocity return
@@ -298,21 +298,49 @@ int fluid_absmax_velocity(fluid_ctx *ctx, int u, int v, float *out);
  * - fluid_ensemble_stats_ptr: device addresses of the two library-owned result fields (always float, layout of
  *   fluid_layout(): pitch, xoff; pad columns zero), holding the results of the last fluid_ensemble_stats until the next
  *   one or fluid_destroy.  FLUID_E_INVALID before the first.
+ * - fluid_member_gram: the M x M matrix of inner products between the members of a field, or between their anomalies
+ *   about the ensemble mean: G = A^T A, what inflation, recentring, an ensemble-space Kalman update, snapshot POD or a
+ *   member-similarity check compute the matrix of fluid_transform_members from.  `gram`: M*M doubles.
+ *    1. x_k[i][j] is the float fluid_pack_members would show for member k right before the call: the field's lazy state is
+ *       settled first, as for fluid_residual, and nothing a later step or download sees is altered; with fp16 storage each
+ *       value is widened exactly and a pressure scale divided back in float, exactly as the pack does.
+ *    2. centre == 0: a_k = (double)x_k.  centre != 0, per cell: mean_d is exactly the mean_d of fluid_ensemble_stats --
+ *       s = (double)x_0; s += (double)x_m for m = 1 .. M-1 in member order; mean_d = s / (double)M, IEEE double, no
+ *       contraction -- and a_k = (double)x_k - mean_d, one rounding.  The subtraction is done per cell before any product,
+ *       on purpose: the identity G - (G 1)(1^T G) / (M 1^T G 1) loses a spread that is small against the mean, as the
+ *       one-pass variance does.
+ *    3. gram[k*M + m] = the sum over the interior cells (rows and columns 1..N, as for the moments: the ghost ring is a
+ *       mirror and takes no part) of a_k * a_m, accumulated in double.  centre == 0: every product is exact in double
+ *       (24 + 24 bits).  centre != 0: a product may be fused into the addition or rounded on its own.
+ *    4. No floating-point atomics, no matrix instructions; the order of every addition is fixed by (N, M, storage type,
+ *       centre) alone: per-block partial matrices stored to a scratch buffer, folded by a second small kernel in index
+ *       order, as for the moments.  So the result is the same bits call after call, context after context, process after
+ *       process; and when every partial sum is representable (dyadic data) it is the exact sum.  Every sum starts from
+ *       its first term, not from 0.0: a sum that is zero has the sign IEEE addition gives it in that order.
+ *    5. gram[k*M + m] and gram[m*M + k] are the same bits: one triangle is computed and mirrored.
+ *    6. centre == 0: a non-finite value in member k poisons row k and column k only; every other entry keeps the bits it
+ *       has without it.  centre != 0: the mean of such a cell is non-finite, and so is EVERY entry.
+ *    7. M = 1: the one entry is the sum of squares; with centre, +0 (NaN if the field is not finite).
+ *   M in [1, FLUID_TRANSFORM_MAX_MEMBERS] (below): the consumer of G is the transform, which has that cap, and M*M doubles
+ *   per block partial stop being small beyond it.  At most two kernels per call whatever M is (partials, fold).
  * - fp16 storage: every value is widened exactly; results stay float / double.  All calls see a field as
  *   fluid_download_member would show it right after the call (the fp16 pressure scale and pending increments are settled
  *   first, as for fluid_residual).
  * Refusals, all FLUID_E_INVALID with a message that names the call (and the member for a bad entry), found before
  * anything is launched or any state changes: null context, null output where one is required, bad field id, a
  * non-finite alpha[m] / beta[m] (x == x0 is no error, as in fluid_residual).  On a context with one member the two
- * _members maxima are the scalar calls with element 0, row slabs included.  fluid_member_moments, fluid_ensemble_stats
- * and fluid_ensemble_stats_ptr are refused on row slabs (nranks > 1): a sum over ranks needs an exchange kind the
- * callback contract does not have.  fluid_residual and fluid_absmax_velocity keep returning the maximum over the
- * members. */
+ * _members maxima are the scalar calls with element 0, row slabs included.  fluid_member_moments, fluid_member_gram,
+ * fluid_ensemble_stats and fluid_ensemble_stats_ptr are refused on row slabs (nranks > 1): a sum over ranks needs an
+ * exchange kind the callback contract does not have.  fluid_member_gram also refuses M > FLUID_TRANSFORM_MAX_MEMBERS (the
+ * message gives both numbers), and finds a null `gram` before the context is looked at.  fluid_residual and
+ * fluid_absmax_velocity keep returning the maximum over the members.  The launches of the moments, the Gram matrix and
+ * the statistics belong to none of the fluid_timing categories. */
 int fluid_residual_members(fluid_ctx *ctx, int x, int x0, const float *alpha, const float *beta, float *out);
 int fluid_absmax_velocity_members(fluid_ctx *ctx, int u, int v, float *out);
 int fluid_member_moments(fluid_ctx *ctx, int field, double *sum, double *sumsq);
 int fluid_ensemble_stats(fluid_ctx *ctx, int field, float *mean, float *variance);
 int fluid_ensemble_stats_ptr(fluid_ctx *ctx, void **mean_dev, void **variance_dev);
+int fluid_member_gram(fluid_ctx *ctx, int field, int centre, double *gram);
 
 /* ---- moving ensembles: device pack / unpack, bulk host copies, recorded runs -------------------------------
  * M = fluid_members(ctx), W = N + 2.  A DENSE array is always float, one member after the other, each member the
