@@ -131,6 +131,11 @@ SIGNATURES = {
     "fluid_run_members_coarse": [_ctx, _MF, _MF, _MF, C.POINTER(RunPlan), _i, C.POINTER(_i)],
     "fluid_transform_members": [_ctx, C.POINTER(_i), _i, _MF],
     "fluid_select_members": [_ctx, C.POINTER(_i), _i, C.POINTER(_i)],
+    "fluid_set_observation_points": [_ctx, _MF, _MF, _i],
+    "fluid_observation_points": [_ctx, C.POINTER(_i)],
+    "fluid_observe_members": [_ctx, _i, C.c_void_p, C.c_size_t],
+    "fluid_observe_members_host": [_ctx, _i, _MF],
+    "fluid_observation_gram": [_ctx, _i, _i, _MF, _MF, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)],
     "fluid_set_jacobi_variant": [_ctx, _i],
     "fluid_division_mode": [_ctx, _f, _f, C.POINTER(_i)],
     "fluid_autotune_pending": [_ctx, C.POINTER(_i)],
@@ -157,6 +162,7 @@ OTHER_SYMBOLS = {"fluid_last_error": (C.c_char_p, []), "fluid_arena_bytes": (C.c
 MAX_MEMBERS = 21845
 COARSE_FACTORS = (1, 2, 4, 8, 16, 32, 64)
 TRANSFORM_MAX_MEMBERS = 64
+OBSERVE_MAX_POINTS = 1 << 20
 
 _lib = None
 

@@ -134,6 +134,21 @@ struct TransformTables {
     bool in_use[kSlots] = {};
 };
 
+// Observing ensembles (fluid_set_observation_points, fluid_observe_members, fluid_observation_gram): the network and the
+// scratch of its Gram call, library-owned and outside the arena (fluid_solver.hip: fluid_set_observation_points,
+// ensure_observation_gram), freed in fluid_destroy.  The network is ONE allocation of 32 bytes per point: four floats of
+// weights, the 64-bit tap offset, and one float each for the observed values and 1 / sigma a Gram call copies in.
+struct Observation {
+    char* table = nullptr;                // [points] float4 weights | [points] tap offsets | [points] obs | [points] 1 / sigma
+    int points = 0;
+    double *d_partials = nullptr, *d_out = nullptr, *host = nullptr;    // per-block partials, the folded result, its pinned twin
+    int partial_blocks = 0;               // what d_partials has room for
+    const float* weight() const { return reinterpret_cast<const float*>(table); }
+    const unsigned long long* tap() const { return reinterpret_cast<const unsigned long long*>(table + (size_t)points * 16); }
+    float* obs() const { return reinterpret_cast<float*>(table + (size_t)points * 24); }
+    float* sigma() const { return reinterpret_cast<float*>(table + (size_t)points * 28); }
+};
+
 struct fluid_ctx {
     int n = 0, w = 0, pitch = 0;
     size_t field_floats = 0;
@@ -168,6 +183,7 @@ struct fluid_ctx {
     EnsembleReduce red;                   // results and scratch of the ensemble diagnostics
     MemberStage stage;                    // device staging of the bulk host copies
     TransformTables xform;                // weight tables of fluid_transform_members / fluid_select_members
+    Observation observe;                  // the observation network and the scratch of fluid_observation_gram
     unsigned int* tiles = nullptr;        // 3 x members x tile_rows x tile_pitch words: |x0| minima per tile for division mode 3
     unsigned int* h_scalar = nullptr;     // pinned host mirror
     hipEvent_t scalar_ready = nullptr;    // recorded behind the scalar's device-to-host copy

@@ -191,4 +191,30 @@ int gram_blocks(int n, int members);
 void launch_member_gram(hipStream_t s, int st, const void* x, int pitch, int n, Members mb, float inv, bool centre, double* partials,
                         double* out);
 
+// Observing ensembles (include/fluid_amd.h "observing ensembles").  The network is a table in device memory, one record per
+// point: `tap`, the element offset of x[i0][j0] within a member (i0 * pitch + XOFF + j0), and four floats of `weight`
+// (16-byte aligned), {s0, s1, t0, t1} of the header's definition -- computed on the host, where the points are validated.
+struct ObservationPoints {
+    const unsigned long long* tap = nullptr;
+    const float* weight = nullptr;
+    int count = 0;
+};
+// out[m * ostride + p - first_point] = the observation of member m (m < mb.count) at point p, first_point <= p < first_point +
+// npoints: one launch whatever the counts, the member in the grid.  `inv`: as for the pack.
+void launch_observe_members(hipStream_t s, int st, const void* x, int pitch, Members mb, float inv, const ObservationPoints& pts,
+                            int first_point, int npoints, float* out, size_t ostride);
+// fluid_observation_gram: out[observation_gram_entries(mb.count)] = the padded MP x MP matrix as launch_member_gram leaves it
+// (MP = gram_padded(mb.count), entries below the diagonal not written), then rhs[MP], then dd -- the last two only with `obs`.
+// `obs`, `sigma`: pts.count floats of device memory each, or null (no innovation; 1 / sigma = 1).  mb.count in [1,
+// kTransformMaxMembers].  Two launches: observation_gram_blocks(points, members) blocks each leave one partial of
+// observation_gram_entries doubles in `partials`, a second kernel adds them in a fixed order.
+inline size_t observation_gram_entries(int members)
+{
+    const size_t mp = (size_t)gram_padded(members);
+    return mp * mp + mp + 1;
+}
+int observation_gram_blocks(int points, int members);
+void launch_observation_gram(hipStream_t s, int st, const void* x, int pitch, Members mb, float inv, const ObservationPoints& pts,
+                             bool centre, const float* obs, const float* sigma, double* partials, double* out);
+
 }  // namespace fluid

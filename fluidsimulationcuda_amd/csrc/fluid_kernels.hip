@@ -1874,6 +1874,188 @@ __global__ __launch_bounds__(256) void k_fold_gram(const double* __restrict__ pa
     }
 }
 
+// ---- observing ensembles (include/fluid_amd.h "observing ensembles") -------------------------------------------------------
+// One observation: the bilinear point sample of advect_sample, in float, operation by operation -- the taps as the pack
+// shows them (fp16 storage: widened, the scale divided back in float), two lerps along the rows, one along the columns.
+// `tap`: element offset of x[i0][j0] in a member; w = {s0, s1, t0, t1}.  All four taps are read whatever the weights: a
+// non-finite tap under a zero weight makes the observation non-finite, as in the reference's advect.
+template <typename S>
+__device__ __forceinline__ float observe_point(const S* __restrict__ x, int pitch, unsigned long long tap, const float4& w, float inv)
+{
+    const S* p = x + tap;
+    float q00 = ld1(p), q10 = ld1(p + 1), q01 = ld1(p + pitch), q11 = ld1(p + pitch + 1);            // q[col][row]
+    if constexpr (sizeof(S) != 4) {
+        q00 = q00 * inv; q10 = q10 * inv; q01 = q01 * inv; q11 = q11 * inv;
+    }
+    const float a = w.z * q00 + w.w * q01;
+    const float e = w.z * q10 + w.w * q11;
+    return w.x * a + w.y * e;
+}
+
+// fluid_observe_members: one lane per point, the member in the grid (blockIdx.y); four gathered taps, one coalesced store.
+// Points [p0, p0 + np) of the table; out[member * ostride + (point - p0)].
+template <typename S>
+__global__ __launch_bounds__(256) void k_observe_members(const S* __restrict__ x, int pitch, size_t ms, float inv,
+                                                         const unsigned long long* __restrict__ tap, const float4* __restrict__ weight, int p0,
+                                                         int np, float* __restrict__ out, size_t ostride)
+{
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= (unsigned)np) return;
+    const unsigned p = (unsigned)p0 + i;
+    out[(size_t)blockIdx.y * ostride + i] = observe_point<S>(x + (size_t)blockIdx.y * ms, pitch, tap[p], weight[p], inv);
+}
+
+// fluid_observation_gram: k_member_gram with the observations of the members in place of their cells.  A chunk is CH = 64
+// points in all MP padded members (padding members are zeros), staged in LDS as doubles [point][member], R = MP + 2 doubles
+// per point; wave w gathers and interpolates members w, w + 4, .. of the chunk, lane l its point l, so a lane reads its
+// point's offset and weights once per chunk.  One lane per point (wave 0) then does the operand chain of the header: the
+// mean chain in member order and its subtraction (CENTRE), the multiplication by 1 / sigma (`sigma` non-null), and -- OBS --
+// the innovation d = (y - mean) / sigma, which goes into the point's first padding double, stage[point][MP].
+// The products are k_member_gram's: lane (ta, tb) of the 8 x 8 lane grid owns a T x T tile, the four waves take the points
+// wave, wave + 4, .., and are added in wave order at the end.  The innovation column needs no accumulator of its own: the
+// lanes below the diagonal, whose tiles are dropped anyway, take d for one of their operands --
+//   lane (tb + 1, tb), tb = 0 .. 6: a[0] := d, so acc[0][j] = sum d * a_m, m = T * tb + j: rhs of tile row tb;
+//   lane (7, 0):                   b[0] := d, so acc[i][0] = sum a_k * d, k = 7 T + i:     rhs of tile row 7;
+//   lane (6, 0):                   both,      so acc[0][0] = sum d * d.
+// A block's partial is E = MP * MP + MP + 1 doubles: the matrix (tiles with ta <= tb), rhs[MP], dd; plain stores, no
+// atomics, no matrix instructions.  Blocks stride over the chunks: the order of every addition is fixed by (points,
+// members, CENTRE, OBS).
+constexpr int kObsChunk = 64;
+
+template <typename S, int MP, bool CENTRE, bool OBS>
+__global__ __launch_bounds__(256) void k_observation_gram(const S* __restrict__ x, int pitch, size_t ms, int members, float inv,
+                                                          const unsigned long long* __restrict__ tap, const float4* __restrict__ weight,
+                                                          const float* __restrict__ obs, const float* __restrict__ sigma, int points,
+                                                          unsigned chunks, double* __restrict__ partials)
+{
+    constexpr int T = MP / 8, CH = kObsChunk, R = MP + 2, L = CH * MP / 256, E = MP * MP + MP + 1;
+    static_assert(MP * MP <= CH * R, "the block's matrix is folded in the staging memory");
+    __shared__ __attribute__((aligned(16))) double stage[CH * R];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int l5 = lane & 31, q = l5 >> 2;
+    const int ta = 4 * (lane >> 5) + (q >> 1), tb = 4 * ((0x96 >> q) & 1) + (l5 & 3);
+    const bool d_for_a = OBS && (ta == tb + 1 || (ta == 6 && tb == 0)), d_for_b = OBS && tb == 0 && ta >= 6;
+    double acc[T][T];
+#pragma unroll
+    for (int i = 0; i < T; ++i)
+#pragma unroll
+        for (int j = 0; j < T; ++j) acc[i][j] = -0.0;
+
+    float f[L];
+    auto points_of = [&](unsigned c) { return min(CH, points - (int)c * CH); };
+    auto load = [&](unsigned c) {
+        const int pt = (int)c * CH + lane;
+        const bool live = pt < points;
+        const unsigned long long o = live ? tap[pt] : 0ull;
+        const float4 w = live ? weight[pt] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+#pragma unroll
+        for (int r = 0; r < L; ++r) {
+            const int k = wave + 4 * r;
+            float a = 0.0f;
+            if (live && k < members) a = observe_point<S>(x + (size_t)k * ms, pitch, o, w, inv);
+            f[r] = a;
+        }
+    };
+
+    unsigned chunk = blockIdx.x;              // (gridDim.x <= chunks: every block has a chunk)
+    load(chunk);
+    for (; chunk < chunks; chunk += gridDim.x) {
+        const int nc = points_of(chunk);
+#pragma unroll
+        for (int r = 0; r < L; ++r) stage[lane * R + wave + 4 * r] = (double)f[r];
+        __syncthreads();
+        if (CENTRE || OBS || sigma) {
+            if (t < nc) {
+                const int pt = (int)chunk * CH + t;
+                double* p = stage + t * R;
+                double mu = 0.0;
+                if constexpr (CENTRE) {
+                    double s = p[0];
+                    for (int m = 1; m < members; ++m) s = s + p[m];
+                    mu = s / (double)members;
+                }
+                const double sg = sigma ? (double)sigma[pt] : 1.0;
+                if (CENTRE || sigma)
+                    for (int m = 0; m < members; ++m) {
+                        double v = p[m];
+                        if constexpr (CENTRE) v = v - mu;
+                        if (sigma) v = v * sg;
+                        p[m] = v;
+                    }
+                if constexpr (OBS) {
+                    double dv = (double)obs[pt];
+                    if constexpr (CENTRE) dv = dv - mu;
+                    if (sigma) dv = dv * sg;
+                    p[MP] = dv;
+                }
+            }
+            __syncthreads();
+        }
+        if (chunk + gridDim.x < chunks) load(chunk + gridDim.x);
+        for (int c = wave; c < nc; c += 4) {
+            double a[T], b[T];
+            gram_operands<T>(stage + c * R + ta * T, a);
+            gram_operands<T>(stage + c * R + tb * T, b);
+            if constexpr (OBS) {
+                const double dv = stage[c * R + MP];
+                if (d_for_a) a[0] = dv;
+                if (d_for_b) b[0] = dv;
+            }
+#pragma unroll
+            for (int i = 0; i < T; ++i)
+#pragma unroll
+                for (int j = 0; j < T; ++j) acc[i][j] = __builtin_fma(a[i], b[j], acc[i][j]);
+        }
+        __syncthreads();
+    }
+
+    // ((wave 0 + wave 1) + wave 2) + wave 3, every lane its own entries; the last wave stores the block's partial
+    double* out = partials + (size_t)blockIdx.x * E;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        if (wave == w) {
+#pragma unroll
+            for (int i = 0; i < T; ++i)
+#pragma unroll
+                for (int j = 0; j < T; ++j) {
+                    const int at = (ta * T + i) * MP + tb * T + j;
+                    if (w > 0) acc[i][j] = stage[at] + acc[i][j];
+                    if (w < 3) stage[at] = acc[i][j];
+                    else if (ta <= tb) out[at] = acc[i][j];
+                    else if constexpr (OBS) {
+                        if (ta == tb + 1 && i == 0) out[MP * MP + tb * T + j] = acc[i][j];
+                        if (ta == 7 && tb == 0 && j == 0) out[MP * MP + 7 * T + i] = acc[i][j];
+                        if (ta == 6 && tb == 0 && i == 0 && j == 0) out[MP * MP + MP] = acc[i][j];
+                    }
+                }
+        }
+        if (w < 3) __syncthreads();
+    }
+}
+
+// k_fold_gram for the partials of k_observation_gram: entry e of the E = mp * mp + mp + 1 doubles of a partial (matrix,
+// rhs, dd), the same fixed order -- 16 lanes per entry, lane p adds partials p, p + 16, .. from -0.0, then the 16 sums in
+// index order.  Matrix entries of tiles below the diagonal were not stored and are not read; rhs and dd only with `obs`.
+__global__ __launch_bounds__(256) void k_fold_observation_gram(const double* __restrict__ partials, int count, int mp, int tile, int obs,
+                                                               double* __restrict__ out)
+{
+    __shared__ double part[16][16];
+    const int entries = mp * mp + mp + 1;
+    const int e = blockIdx.x * 16 + (threadIdx.x & 15), p0 = threadIdx.x >> 4;
+    const bool live = e < mp * mp ? (e / mp) / tile <= (e % mp) / tile : (obs && e < entries);
+    double s = -0.0;
+    if (live)
+        for (int p = p0; p < count; p += 16) s = s + partials[(size_t)p * (size_t)entries + e];
+    part[p0][threadIdx.x & 15] = s;
+    __syncthreads();
+    if (threadIdx.x < 16 && live) {
+        s = part[0][threadIdx.x];
+#pragma unroll
+        for (int p = 1; p < 16; ++p) s = s + part[p][threadIdx.x];
+        out[e] = s;
+    }
+}
+
 // Across the members, per cell (ghost cells included): mean and population variance as float fields in the layout of a
 // field, by the two-pass definition of include/fluid_amd.h -- all in double, member order, the first member's value (not
 // 0.0) as the start of both chains.  One lane per VW = 4 (fp16: 8) consecutive columns of a row, vector v of a row covering
@@ -2553,6 +2735,48 @@ void launch_member_gram(hipStream_t s, int st, const void* x, int pitch, int n, 
     }
 #undef FLUID_GRAM_CASE
     hipLaunchKernelGGL(k_fold_gram, dim3(mp * mp / 16), dim3(256), 0, s, partials, blocks, mp, mp / 8, out);
+}
+
+void launch_observe_members(hipStream_t s, int st, const void* x, int pitch, Members mb, float inv, const ObservationPoints& pts,
+                            int first_point, int npoints, float* out, size_t ostride)
+{
+    const dim3 grid(cdiv((unsigned)npoints, 256), mb.count);
+    FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_observe_members<S>, grid, dim3(256), 0, s, (const S*)x, pitch, mb.stride, inv, pts.tap,
+                                            (const float4*)pts.weight, first_point, npoints, out, ostride));
+}
+
+// as gram_blocks: at most two (MP = 64) or four resident blocks per CU, at least one chunk of 64 points per block
+int observation_gram_blocks(int points, int members)
+{
+    return (int)std::min<unsigned>(cdiv((unsigned)points, kObsChunk), gram_padded(members) == 64 ? 512u : 1024u);
+}
+
+void launch_observation_gram(hipStream_t s, int st, const void* x, int pitch, Members mb, float inv, const ObservationPoints& pts,
+                             bool centre, const float* obs, const float* sigma, double* partials, double* out)
+{
+    const int mp = gram_padded(mb.count), blocks = observation_gram_blocks(pts.count, mb.count);
+    const unsigned chunks = cdiv((unsigned)pts.count, kObsChunk);
+#define FLUID_OBS_GRAM_LAUNCH(MP, CENTRE, OBS)                                                                                             \
+    FLUID_BY_STORAGE(st, hipLaunchKernelGGL((k_observation_gram<S, MP, CENTRE, OBS>), dim3(blocks), dim3(256), 0, s, (const S*)x, pitch,   \
+                                            mb.stride, mb.count, inv, pts.tap, (const float4*)pts.weight, obs, sigma, pts.count, chunks,   \
+                                            partials))
+#define FLUID_OBS_GRAM_CASE(MP)                                     \
+    case MP:                                                        \
+        if (centre && obs) FLUID_OBS_GRAM_LAUNCH(MP, true, true);   \
+        else if (centre) FLUID_OBS_GRAM_LAUNCH(MP, true, false);    \
+        else if (obs) FLUID_OBS_GRAM_LAUNCH(MP, false, true);       \
+        else FLUID_OBS_GRAM_LAUNCH(MP, false, false);               \
+        break
+    switch (mp) {
+        FLUID_OBS_GRAM_CASE(8);
+        FLUID_OBS_GRAM_CASE(16);
+        FLUID_OBS_GRAM_CASE(32);
+        FLUID_OBS_GRAM_CASE(64);
+    }
+#undef FLUID_OBS_GRAM_CASE
+#undef FLUID_OBS_GRAM_LAUNCH
+    hipLaunchKernelGGL(k_fold_observation_gram, dim3(cdiv((unsigned)observation_gram_entries(mb.count), 16)), dim3(256), 0, s, partials,
+                       blocks, mp, mp / 8, obs ? 1 : 0, out);
 }
 
 void launch_ensemble_stats(hipStream_t s, int st, const void* x, int pitch, int n, Members mb, float* mean, float* var)

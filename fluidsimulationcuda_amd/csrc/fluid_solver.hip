@@ -1862,6 +1862,10 @@ int fluid_destroy(fluid_ctx* c)
     if (c->red.d_gram) (void)hipFree(c->red.d_gram);
     if (c->red.gram_host) (void)hipHostFree(c->red.gram_host);
     if (c->stage.dev) (void)hipFree(c->stage.dev);
+    if (c->observe.table) (void)hipFree(c->observe.table);
+    if (c->observe.d_partials) (void)hipFree(c->observe.d_partials);
+    if (c->observe.d_out) (void)hipFree(c->observe.d_out);
+    if (c->observe.host) (void)hipHostFree(c->observe.host);
     for (hipEvent_t ev : c->xform.copied)
         if (ev) (void)hipEventDestroy(ev);
     if (c->xform.dev) (void)hipFree(c->xform.dev);
@@ -2962,6 +2966,202 @@ int fluid_upload_members(fluid_ctx* c, int field, const float* host)
     }
     wrote(c, field, kEverywhere);              // every member was replaced: an unpack of all members, in groups
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return FLUID_OK;
+}
+
+// ---- observing ensembles: a resident network of points, the members' values at it, their Gram matrix --------------------
+// (include/fluid_amd.h "observing ensembles".)  The network is a table in library-owned device memory outside the arena
+// (fluid_ctx.h: Observation), built and validated on the host; the observing calls settle the field as a pack does and
+// launch on the context's stream.  The launches belong to none of the timing categories.  Every refusal is found before
+// anything is launched or changed.
+int fluid_set_observation_points(fluid_ctx* c, const float* col, const float* row, int npoints)
+{
+    if (npoints != 0 && !col) return fail(FLUID_E_INVALID, "fluid_set_observation_points: null array `col`");
+    if (npoints != 0 && !row) return fail(FLUID_E_INVALID, "fluid_set_observation_points: null array `row`");
+    if (!c) return fail(FLUID_E_INVALID, "fluid_set_observation_points: null context");
+    if (npoints < 0 || npoints > FLUID_OBSERVE_MAX_POINTS)
+        return fail(FLUID_E_INVALID, "fluid_set_observation_points: npoints %d outside [0, FLUID_OBSERVE_MAX_POINTS = %d]", npoints,
+                    FLUID_OBSERVE_MAX_POINTS);
+    TRY(refuse_slabs(c, "fluid_set_observation_points"));
+    const double hi = (double)c->n + 0.5;
+    for (int p = 0; p < npoints; ++p) {
+        const float xy[2] = {col[p], row[p]};
+        for (int a = 0; a < 2; ++a)
+            if (!std::isfinite(xy[a]) || (double)xy[a] < 0.5 || (double)xy[a] > hi)
+                return fail(FLUID_E_INVALID, "fluid_set_observation_points: point %d: %s = %g is not a finite value in [0.5, N + 0.5 = %g]", p,
+                            a ? "row" : "col", (double)xy[a], hi);
+    }
+    Observation& o = c->observe;
+    char* table = nullptr;
+    if (npoints > 0) {
+        const size_t P = (size_t)npoints;
+        std::vector<char> host(P * 24);
+        float* weight = reinterpret_cast<float*>(host.data());
+        unsigned long long* tap = reinterpret_cast<unsigned long long*>(host.data() + P * 16);
+        for (size_t p = 0; p < P; ++p) {
+            const int j0 = (int)col[p], i0 = (int)row[p];             // at most N: every tap of the 2 x 2 stencil exists
+            const float s1 = col[p] - (float)j0, t1 = row[p] - (float)i0;
+            weight[4 * p + 0] = 1.0f - s1;
+            weight[4 * p + 1] = s1;
+            weight[4 * p + 2] = 1.0f - t1;
+            weight[4 * p + 3] = t1;
+            tap[p] = (unsigned long long)i0 * (unsigned long long)c->pitch + (unsigned long long)(fluid::XOFF + j0);
+        }
+        hipError_t e = hipMalloc((void**)&table, P * 32);
+        if (e == hipSuccess) e = hipMemcpyAsync(table, host.data(), host.size(), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) {                                          // the old network stays in place
+            if (table) (void)hipFree(table);
+            (void)hipGetLastError();
+            return fail(e == hipErrorOutOfMemory ? FLUID_E_NOMEM : FLUID_E_HIP, "fluid_set_observation_points: a table of %zu bytes: %s", P * 32,
+                        hipGetErrorString(e));
+        }
+    } else if (o.table) HIP_TRY(hipStreamSynchronize(c->stream));      // launches that still read the old table
+    if (o.table) (void)hipFree(o.table);
+    o.table = table;
+    o.points = npoints;
+    return FLUID_OK;
+}
+
+int fluid_observation_points(fluid_ctx* c, int* npoints)
+{
+    if (!npoints) return fail(FLUID_E_INVALID, "fluid_observation_points: null pointer `npoints`");
+    if (!c) return fail(FLUID_E_INVALID, "fluid_observation_points: null context");
+    TRY(refuse_slabs(c, "fluid_observation_points"));
+    *npoints = c->observe.points;
+    return FLUID_OK;
+}
+
+// what the three observing calls refuse beyond their own pointers
+static int check_observe(const fluid_ctx* c, const char* call, int field)
+{
+    if (!c->valid_field(field)) return fail(FLUID_E_INVALID, "%s: bad field id %d", call, field);
+    TRY(refuse_slabs(c, call));
+    if (c->observe.points == 0) return fail(FLUID_E_INVALID, "%s: no observation network is set (fluid_set_observation_points)", call);
+    return FLUID_OK;
+}
+
+static fluid::ObservationPoints observation_points(const fluid_ctx* c) { return {c->observe.tap(), c->observe.weight(), c->observe.points}; }
+
+// as pack_range sees the field: the lazy state settled, a scale kept and divided back in the kernel
+static int settle_for_observing(fluid_ctx* c, int field, float* inv)
+{
+    *inv = c->st != fluid::STORAGE_F32 ? 1.0f / c->field[field].fscale : 1.0f;
+    return materialize(c, field, /*keep_scale=*/*inv != 1.0f);
+}
+
+int fluid_observe_members(fluid_ctx* c, int field, void* out_dev, size_t member_stride)
+{
+    if (!out_dev) return fail(FLUID_E_INVALID, "fluid_observe_members: null device pointer `out_dev`");
+    if (!c) return fail(FLUID_E_INVALID, "fluid_observe_members: null context");
+    TRY(check_observe(c, "fluid_observe_members", field));
+    const size_t P = (size_t)c->observe.points;
+    if (member_stride == 0) member_stride = P;
+    if (member_stride < P) return fail(FLUID_E_INVALID, "fluid_observe_members: member_stride %zu is below the %zu points of the network", member_stride, P);
+    size_t bytes = 0;
+    if (!dense_span(P, c->members, member_stride, &bytes)) return fail(FLUID_E_INVALID, "fluid_observe_members: member_stride %zu is too large", member_stride);
+    TRY(check_device_span(c, "fluid_observe_members", "out_dev", out_dev, bytes));
+    float inv = 1.0f;
+    TRY(settle_for_observing(c, field, &inv));
+    fluid::launch_observe_members(c->stream, c->st, c->ptr(field), c->pitch, c->mb(), inv, observation_points(c), 0, (int)P,
+                                  static_cast<float*>(out_dev), member_stride);
+    HIP_TRY(hipGetLastError());
+    return FLUID_OK;
+}
+
+// Through the staging buffer of fluid_download_members, whatever its size: as many whole members per group as fit in it,
+// or -- a network larger than the buffer -- one member at a time in pieces of points.  Groups in stream order, one wait.
+int fluid_observe_members_host(fluid_ctx* c, int field, float* host)
+{
+    if (!host) return fail(FLUID_E_INVALID, "fluid_observe_members_host: null host pointer `host`");
+    if (!c) return fail(FLUID_E_INVALID, "fluid_observe_members_host: null context");
+    TRY(check_observe(c, "fluid_observe_members_host", field));
+    TRY(ensure_stage(c, "fluid_observe_members_host"));
+    float inv = 1.0f;
+    TRY(settle_for_observing(c, field, &inv));
+    const size_t P = (size_t)c->observe.points, room = (size_t)c->stage.members * member_cells(c);
+    const int group = (int)std::max<size_t>(1, std::min<size_t>((size_t)c->members, room / P));
+    const size_t piece = std::min(P, room);
+    const fluid::ObservationPoints pts = observation_points(c);
+    for (int first = 0; first < c->members; first += group) {
+        const int count = std::min(group, c->members - first);
+        const char* x = static_cast<const char*>(c->ptr(field)) + (size_t)first * c->field_bytes;
+        for (size_t p0 = 0; p0 < P; p0 += piece) {                       // (one piece unless the network outgrows the buffer: count is 1 then)
+            const size_t np = std::min(piece, P - p0);
+            fluid::launch_observe_members(c->stream, c->st, x, c->pitch, {count, c->field_floats}, inv, pts, (int)p0, (int)np, c->stage.dev, np);
+            HIP_TRY(hipGetLastError());
+            if (np == P)
+                HIP_TRY(hipMemcpyAsync(host + (size_t)first * P, c->stage.dev, (size_t)count * P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+            else
+                HIP_TRY(hipMemcpyAsync(host + (size_t)first * P + p0, c->stage.dev, np * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return FLUID_OK;
+}
+
+// the scratch and the result of fluid_observation_gram: partials for the blocks of this network (a larger network later:
+// allocated anew, the old ones freed after it), the folded result and its pinned twin
+static int ensure_observation_gram(fluid_ctx* c)
+{
+    Observation& o = c->observe;
+    const int blocks = fluid::observation_gram_blocks(o.points, c->members);
+    const size_t entries = fluid::observation_gram_entries(c->members) * sizeof(double), parts = entries * (size_t)blocks;
+    if (o.d_out && blocks <= o.partial_blocks) return FLUID_OK;
+    double *d_part = nullptr, *d_out = o.d_out, *host = o.host;
+    hipError_t e = hipMalloc((void**)&d_part, parts);
+    if (e == hipSuccess && !d_out) e = hipMalloc((void**)&d_out, entries);
+    if (e == hipSuccess && !host) e = hipHostMalloc((void**)&host, entries, hipHostMallocDefault);
+    if (e != hipSuccess) {
+        if (d_part) (void)hipFree(d_part);
+        if (d_out && d_out != o.d_out) (void)hipFree(d_out);
+        (void)hipGetLastError();
+        return fail(e == hipErrorOutOfMemory ? FLUID_E_NOMEM : FLUID_E_HIP, "fluid_observation_gram: allocating %zu bytes of partial results: %s",
+                    parts + entries, hipGetErrorString(e));
+    }
+    if (o.d_partials) {                                                  // (every earlier call ended in a wait: nothing reads them)
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        (void)hipFree(o.d_partials);
+    }
+    o.d_partials = d_part;
+    o.partial_blocks = blocks;
+    o.d_out = d_out;
+    o.host = host;
+    return FLUID_OK;
+}
+
+int fluid_observation_gram(fluid_ctx* c, int field, int centre, const float* obs, const float* inv_sigma, double* gram, double* rhs, double* dd)
+{
+    if (!gram) return fail(FLUID_E_INVALID, "fluid_observation_gram: null array `gram`");
+    if (!obs && (rhs || dd)) return fail(FLUID_E_INVALID, "fluid_observation_gram: `%s` is given but `obs` is null", rhs ? "rhs" : "dd");
+    if (!c) return fail(FLUID_E_INVALID, "fluid_observation_gram: null context");
+    if (!c->valid_field(field)) return fail(FLUID_E_INVALID, "fluid_observation_gram: bad field id %d", field);
+    if (c->members > FLUID_TRANSFORM_MAX_MEMBERS)
+        return fail(FLUID_E_INVALID, "fluid_observation_gram: this context has %d members, above FLUID_TRANSFORM_MAX_MEMBERS = %d", c->members,
+                    FLUID_TRANSFORM_MAX_MEMBERS);
+    TRY(check_observe(c, "fluid_observation_gram", field));
+    Observation& o = c->observe;
+    const size_t P = (size_t)o.points;
+    if (inv_sigma)
+        for (size_t p = 0; p < P; ++p)
+            if (!std::isfinite(inv_sigma[p]))
+                return fail(FLUID_E_INVALID, "fluid_observation_gram: inv_sigma[%zu] (point %zu) is not finite", p, p);
+    TRY(ensure_observation_gram(c));
+    if (obs) HIP_TRY(hipMemcpyAsync(o.obs(), obs, P * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (inv_sigma) HIP_TRY(hipMemcpyAsync(o.sigma(), inv_sigma, P * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    float inv = 1.0f;
+    TRY(settle_for_observing(c, field, &inv));
+    fluid::launch_observation_gram(c->stream, c->st, c->ptr(field), c->pitch, c->mb(), inv, observation_points(c), centre != 0,
+                                   obs ? o.obs() : nullptr, inv_sigma ? o.sigma() : nullptr, o.d_partials, o.d_out);
+    HIP_TRY(hipGetLastError());
+    const int M = c->members, mp = fluid::gram_padded(M);
+    HIP_TRY(hipMemcpyAsync(o.host, o.d_out, fluid::observation_gram_entries(M) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int k = 0; k < M; ++k)                    // the upper triangle was computed; the lower one is its mirror
+        for (int m = k; m < M; ++m) gram[(size_t)k * M + m] = gram[(size_t)m * M + k] = o.host[(size_t)k * mp + m];
+    if (rhs)
+        for (int k = 0; k < M; ++k) rhs[k] = o.host[(size_t)mp * mp + k];
+    if (dd) *dd = o.host[(size_t)mp * mp + mp];
     return FLUID_OK;
 }
 

@@ -221,6 +221,71 @@ class FluidSolver:
         ids = [_fid(f) for f in fields]
         capi.check(capi.lib().fluid_select_members(self._h, (C.c_int * len(ids))(*ids), len(ids), (C.c_int * len(src))(*src)))
 
+    # -- observing an ensemble: a resident network of points, every member's bilinear sample at it, their Gram matrix
+    def set_observation_points(self, cols, rows):
+        """The observation network: positions in cell-index coordinates (cell centres at 1..N, the walls at 0.5 and
+        N + 0.5), two sequences of the same length.  Replaces the previous network; empty sequences clear it
+        (include/fluid_amd.h, "observing ensembles")."""
+        c = np.ascontiguousarray(np.asarray(cols, np.float32).ravel())
+        r = np.ascontiguousarray(np.asarray(rows, np.float32).ravel())
+        if c.shape != r.shape:
+            raise ValueError("cols and rows must have the same length, got %d and %d" % (c.size, r.size))
+        capi.check(capi.lib().fluid_set_observation_points(self._h, _mf(c), _mf(r), int(c.size)))
+
+    def observation_points(self):
+        """The number of points of the network; 0 when none is set."""
+        p = C.c_int()
+        capi.check(capi.lib().fluid_observation_points(self._h, C.byref(p)))
+        return p.value
+
+    def observe(self, field):
+        """Every member's value at every point of the network as a (members, points) float32 array: the bilinear sample
+        the solver's advection uses, on what pack would show (include/fluid_amd.h, "observing ensembles")."""
+        out = np.empty((self.members, self.observation_points()), np.float32)
+        capi.check(capi.lib().fluid_observe_members_host(self._h, _fid(field), _mf(out)))
+        return out
+
+    def observe_device(self, field, out=None, member_stride=0, wait=True):
+        """observe() into a dense device array, in one launch: out[m * member_stride + p] (member_stride=0: the number of
+        points).  `out`, `wait`: as for pack; None: a (members, points) float32 torch tensor is allocated (member_stride
+        must then be 0)."""
+        if out is None:
+            points = self.observation_points()
+            if member_stride not in (0, points):
+                raise ValueError("out=None allocates a dense tensor: member_stride must be 0")
+            import torch
+            out = torch.empty((self.members, points), dtype=torch.float32, device="cuda")
+        self._handover(wait)
+        capi.check(capi.lib().fluid_observe_members(self._h, _fid(field), device_address(out), int(member_stride)))
+        if wait:
+            self.synchronize()
+        return out
+
+    def observation_gram(self, field, obs=None, inv_sigma=None, centre=True):
+        """The Gram matrix of the members in observation space: C[k][m] = sum over the points of a_k a_m, a_k = (h_k - mean)
+        / sigma (the mean over the members subtracted with `centre`; inv_sigma: 1 / sigma per point, None for 1).  With
+        `obs`, the observed values y: returns (C, rhs, dd), rhs[k] = sum a_k d and dd = sum d d for the innovation d =
+        (y - mean) / sigma; without: C alone.  Float64, bit-symmetric, the same bits on every call (include/fluid_amd.h,
+        "observing ensembles": fluid_observation_gram).  members <= capi.TRANSFORM_MAX_MEMBERS."""
+        points = self.observation_points()
+
+        def per_point(a, name):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(np.asarray(a, np.float32).ravel())
+            if a.size != points:
+                raise ValueError("%s must hold one value per point (%d), got %d" % (name, points, a.size))
+            return a
+
+        y, s = per_point(obs, "obs"), per_point(inv_sigma, "inv_sigma")
+        dp = C.POINTER(C.c_double)
+        g = np.empty((self.members, self.members), np.float64)
+        rhs, dd = np.empty(self.members, np.float64), C.c_double()
+        capi.check(capi.lib().fluid_observation_gram(self._h, _fid(field), 1 if centre else 0, None if y is None else _mf(y),
+                                                     None if s is None else _mf(s), g.ctypes.data_as(dp),
+                                                     None if y is None else rhs.ctypes.data_as(dp), None if y is None else C.byref(dd)))
+        return g if y is None else (g, rhs, dd.value)
+
     def run(self, nsteps, every=0, fields=(), sources=None, out=None, dt=DT, diff=DIFF, visc=VIS, iters=ITERS, use_sources=False,
             wait=True, coarse=None):
         """nsteps steps without the host in the loop.  `sources`: a dense device array (3, members, N+2, N+2) -- u_prev,

@@ -481,6 +481,75 @@ int fluid_run_members_coarse(fluid_ctx *ctx, const float *dt, const float *diff,
 int fluid_transform_members(fluid_ctx *ctx, const int *fields, int nfields, const float *weights);
 int fluid_select_members(fluid_ctx *ctx, const int *fields, int nfields, const int *source);
 
+/* ---- observing ensembles: point samples of every member, and their Gram matrix -----------------------------------
+ * M = fluid_members(ctx); x[i][j] = row i, column j of a member.  A Kalman-type update, a particle-filter weight or a
+ * time series from probes need the members as an instrument sees them: H x_m at P points, P a few to 10^5 against N*N
+ * cells.  The network of points is resident; "step -> observe -> M x M algebra on the host -> fluid_transform_members" is
+ * an assimilation cycle that never takes the ensemble apart.
+ *
+ * - fluid_set_observation_points: `col`, `row` are host arrays of npoints floats, positions in cell-index coordinates:
+ *   cell centres at the integers 1..N, the walls at 0.5 and N + 0.5.  Every coordinate must be finite and lie in
+ *   [0.5, N + 0.5], the range the reference's advection clamps a back-trace to (FluidSequential.c:120-123).  The points
+ *   are validated on the host and kept in library-owned device memory outside the arena (fluid_arena_bytes_ensemble is
+ *   unchanged; 32 bytes per point), freed by fluid_destroy.  The call replaces the previous network; npoints = 0 clears it
+ *   and frees the memory (the arrays may then be null).  It may wait for the stream; both arrays are the caller's again on
+ *   return.  A failed allocation is FLUID_E_NOMEM and leaves the context usable and the old network in place.
+ * - fluid_observation_points: *npoints = P, 0 when no network is set.
+ * - The observation h_k[p] of member k at point p = (col, row), ONE definition for all calls, in float with no contraction
+ *   -- the interpolant of the solver's own advection:
+ *       j0 = (int)col;  i0 = (int)row;
+ *       s1 = col - (float)j0;  s0 = 1.0f - s1;
+ *       t1 = row - (float)i0;  t0 = 1.0f - t1;
+ *       h  = s0 * (t0 * x[i0][j0]   + t1 * x[i0+1][j0])
+ *          + s1 * (t0 * x[i0][j0+1] + t1 * x[i0+1][j0+1]);
+ *   The taps are the values fluid_pack_members would show right before the call: the field's lazy state is settled first,
+ *   as for fluid_member_gram, and nothing a later step or download sees is altered; with fp16 storage each tap is widened
+ *   exactly and the pressure scale divided back in float, as the pack does.  The ghost ring is read like any cell; j0 and
+ *   i0 are at most N, so every tap exists.  A point at a cell centre returns that cell's value when all four taps are
+ *   finite (a zero that results may be +0).  A non-finite tap makes the observation non-finite even under a zero weight,
+ *   as in the reference's advect: it affects only that member and only the points whose 2 x 2 stencil holds it.
+ * - fluid_observe_members: out_dev[m * member_stride + p] = h_m[p], a dense DEVICE array.  member_stride = 0: P; any other
+ *   value must be at least P (the floats in between are not touched).  One kernel launch whatever M and P are, on the
+ *   context's stream, no wait.  Any M up to 21845; row and member offsets are 64-bit.
+ * - fluid_observe_members_host: the same values into a host array of M*P floats, synchronous, ONE wait, through the
+ *   staging buffer of fluid_download_members (no second buffer), in groups of members when M*P exceeds it.
+ * - fluid_observation_gram: the observation-space counterpart of fluid_member_gram -- what an ensemble-space update (ETKF,
+ *   EnKF) computes its matrix from.  `obs`: P observed values y_p, or null; `inv_sigma`: P values s_p = 1 / sigma_p, or
+ *   null for 1.0; both host arrays.  `gram`: M*M doubles; `rhs`: M doubles or null; `dd`: one double or null.
+ *    1. h_k[p] as above.
+ *    2. centre != 0: mean_d[p] is the member-order chain of fluid_ensemble_stats: s = (double)h_0, then s += (double)h_m
+ *       for m = 1 .. M-1, then mean_d = s / (double)M.  centre == 0: mean_d = 0 and the subtraction is skipped.
+ *    3. a_k[p] = ((double)h_k - mean_d) * (double)s_p;  d[p] = ((double)y_p - mean_d) * (double)s_p; each operation rounds
+ *       once.  A multiplication by 1.0 is exact: a null inv_sigma gives the bits that all ones give.
+ *    4. gram[k*M + m] = sum over p of a_k * a_m;  rhs[k] = sum over p of a_k * d;  *dd = sum over p of d * d; accumulated
+ *       in double, a product fused into the addition or rounded on its own.  rhs and dd may be null; they MUST be null
+ *       when obs is null.
+ *    5. No floating-point atomics, no matrix instructions: per-block partials go to library-owned scratch and are folded
+ *       by a second small kernel in index order; at most two launches.  The order of every addition is fixed by P, M,
+ *       centre and whether obs is given: the same bits call after call and process after process, and the exact sum when
+ *       every partial sum is representable.  Every sum starts from its first term.
+ *    6. gram is bit-symmetric: one triangle is computed and mirrored.
+ *    7. centre == 0: a non-finite h_k poisons row k, column k and rhs[k] only; a non-finite y_p poisons rhs and dd only.
+ *       centre != 0: a non-finite h_k at a point poisons everything.
+ *    8. M in [1, FLUID_TRANSFORM_MAX_MEMBERS].
+ *   Synchronous like fluid_member_gram: two kernels, one copy of M*M + M + 1 doubles (padded), one wait.
+ * Refusals, all FLUID_E_INVALID with a message that names the call and, where it applies, the point index or the member,
+ * found before anything is launched or any state changes, null pointers before the context is looked at: a null context;
+ * a null required pointer (col, row with npoints != 0; npoints; out_dev; host; gram); rhs or dd given with obs null; a bad
+ * field id; npoints outside [0, FLUID_OBSERVE_MAX_POINTS]; a coordinate that is not finite or lies outside
+ * [0.5, N + 0.5]; no network set, for the three observing calls; a stride below P; a device pointer that is not device
+ * memory of the context's device or whose extent does not lie inside one allocation (asked of the runtime on the host,
+ * as for a pack); a non-finite inv_sigma[p], named by its index; M > FLUID_TRANSFORM_MAX_MEMBERS for the Gram call (the
+ * message gives both numbers); row slabs (nranks > 1), for all five calls.
+ * The launches belong to none of the fluid_timing categories. */
+#define FLUID_OBSERVE_MAX_POINTS (1 << 20)
+int fluid_set_observation_points(fluid_ctx *ctx, const float *col, const float *row, int npoints);
+int fluid_observation_points(fluid_ctx *ctx, int *npoints);
+int fluid_observe_members(fluid_ctx *ctx, int field, void *out_dev, size_t member_stride);
+int fluid_observe_members_host(fluid_ctx *ctx, int field, float *host);
+int fluid_observation_gram(fluid_ctx *ctx, int field, int centre, const float *obs, const float *inv_sigma,
+                           double *gram, double *rhs, double *dd);
+
 int fluid_set_jacobi_variant(fluid_ctx *ctx, int variant);
 /* How FLUID_JACOBI_TB divides by `beta` in a solve with these coefficients (diagnostic; runs the on-device proof
  * if this beta has not been seen): 0 true division, 2 double-precision reciprocal, 3 two-term float reciprocal
