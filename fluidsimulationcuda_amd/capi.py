@@ -136,6 +136,8 @@ SIGNATURES = {
     "fluid_observe_members": [_ctx, _i, C.c_void_p, C.c_size_t],
     "fluid_observe_members_host": [_ctx, _i, _MF],
     "fluid_observation_gram": [_ctx, _i, _i, _MF, _MF, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)],
+    "fluid_transform_members_local": [_ctx, C.POINTER(_i), _i, _MF, C.c_void_p, C.POINTER(_i)],
+    "fluid_taper_gaspari_cohn": [_ctx, _f, _f, _f, C.c_void_p, C.POINTER(_i)],
     "fluid_set_jacobi_variant": [_ctx, _i],
     "fluid_division_mode": [_ctx, _f, _f, C.POINTER(_i)],
     "fluid_autotune_pending": [_ctx, C.POINTER(_i)],

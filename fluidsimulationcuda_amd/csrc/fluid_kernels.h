@@ -217,4 +217,52 @@ int observation_gram_blocks(int points, int members);
 void launch_observation_gram(hipStream_t s, int st, const void* x, int pitch, Members mb, float inv, const ObservationPoints& pts,
                              bool centre, const float* obs, const float* sigma, double* partials, double* out);
 
+// Localised updates (include/fluid_amd.h "localised updates").
+// The box of a launch, half-open, in cells of the (n + 2)^2 array: rows [row_lo, row_hi), columns [col_lo, col_hi).
+struct CellBox {
+    int row_lo, row_hi, col_lo, col_hi;
+    bool empty() const { return row_lo >= row_hi || col_lo >= col_hi; }
+};
+// The tapered increment in place: per cell of `box` with taper g != 0 and per member m with bit m of `used` set, x_m =
+// narrow((float)(widen(x_m) + g * s_m)), s_m the member-order sum of launch_transform_members over `table` (the increments)
+// -- product and sum rounded one after the other, in double.  `inv`, `scale`: 1 / FieldState::fscale and fscale of an fp16
+// field held scaled (powers of two; both 1 otherwise): values are read as widen(x) * inv, narrow(y) is stored times scale.
+// `table`, `bits`, `dense`: as for launch_transform_members; `taper`: (n + 2)^2 floats of device memory, row-major, or null
+// for g = 1.  One launch, its grid the box; cells outside it are neither read nor written.  The box is not empty.
+void launch_transform_members_local(hipStream_t s, int st, void* x, int pitch, int n, Members mb, float inv, float scale,
+                                    const double* table, const unsigned long long* bits, unsigned long long used, bool dense,
+                                    const float* taper, CellBox box);
+// The Gaspari-Cohn taper of half-width c about (col, row), one definition for the kernel and for the host's bounding box:
+// taper_radius is r at a cell dx columns and dy rows from the centre, taper_value the piecewise polynomial in Horner form,
+// clamped to [0, 1]; every operation rounds once (no contraction), in double.
+__host__ __device__ inline double taper_radius(double dx, double dy, double c)
+{
+#pragma clang fp contract(off)
+    const double xx = dx * dx, yy = dy * dy;
+    return sqrt(xx + yy) / c;
+}
+__host__ __device__ inline double taper_value(double r)
+{
+#pragma clang fp contract(off)
+    if (!(r < 2.0)) return 0.0;
+    double g;
+    if (r <= 1.0) {
+        g = -0.25 * r + 0.5;
+        g = g * r + 0.625;
+        g = g * r - 5.0 / 3.0;
+        g = g * r;
+        g = g * r + 1.0;
+    } else {
+        g = (1.0 / 12.0) * r - 0.5;
+        g = g * r + 0.625;
+        g = g * r + 5.0 / 3.0;
+        g = g * r - 5.0;
+        g = g * r + 4.0;
+        g = g - (2.0 / 3.0) / r;
+    }
+    return g < 0.0 ? 0.0 : g > 1.0 ? 1.0 : g;
+}
+// out[i * (n + 2) + j] = (float)taper_value(taper_radius(j - col, i - row, c)) for every cell of the (n + 2)^2 array: one launch
+void launch_taper_gaspari_cohn(hipStream_t s, float* out, int n, float col, float row, float c);
+
 }  // namespace fluid

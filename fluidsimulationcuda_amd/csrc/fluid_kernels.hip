@@ -2449,6 +2449,92 @@ __global__ __launch_bounds__(256) void k_transform_members(S* __restrict__ x, in
 }
 
 // ---------------------------------------------------------------------------
+// localised updates (include/fluid_amd.h "localised updates"): the increment of a transform under a per-cell taper, in
+// place, X' = X + g o (X D), over a box of cells only.  The kernel of k_transform_members with three differences.  The grid
+// covers the box: blockIdx.y counts rows from row_lo, a block's 256 columns start at col_lo.  The taper is loaded first: a
+// lane whose g is zero has nothing to store, and a wave whose lanes all find zero leaves after that one load -- a taper's
+// bounding box is mostly such waves near its corners, a null box nearly all of them.  And the accumulators hold the
+// increment s_m, not the new value: after the walk over the old members each member with a term (`used`, known on the
+// host) is read once more -- its own cell, which no other lane stores and this lane has not stored yet -- and stored as
+// x_m + g * s_m, product and sum rounded one after the other in double, then to float, then to the storage type.  The
+// re-read costs a load that hits the cache; a second register set would cost 64 VGPRs at MP = 64.  Members without a term
+// are not stored.  An fp16 field held at a scale (FieldState::fscale, a power of two) keeps it, because the cells this
+// launch does not visit keep it: a value is read as widen(x) * inv, as the pack shows it, and narrow(y) goes back times
+// `scale` -- exact, both being halves and powers of two apart, unless the product leaves the range of a half.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ float tapered(float xm, double g, double s)
+{
+#pragma clang fp contract(off)
+    const double p = __dmul_rn(g, s);
+    return (float)__dadd_rn((double)xm, p);
+}
+
+template <typename S, int MP, bool DENSE>
+__global__ __launch_bounds__(256) void k_transform_members_local(S* __restrict__ x, int pitch, int w, size_t ms, int members,
+                                                                 float inv, float scale, const double* __restrict__ table,
+                                                                 const unsigned long long* __restrict__ bits, unsigned long long used,
+                                                                 const float* __restrict__ taper, int row_lo, int col_lo, int col_hi)
+{
+    const unsigned col = (unsigned)col_lo + blockIdx.x * 256u + threadIdx.x;
+    const size_t row = (size_t)row_lo + blockIdx.y;
+    const bool inside = col < (unsigned)col_hi;
+    float gf = 1.0f;
+    if (taper && inside) gf = taper[row * (size_t)w + col];
+    const bool live = inside && gf != 0.0f;                        // (a NaN taper is live: its cell becomes NaN)
+    if (__builtin_amdgcn_ballot_w64(live) == 0) return;            // the whole wave: uniform
+    if (!live) return;
+    x += row * (size_t)pitch + (size_t)XOFF;                       // this row of member 0, scalar; the lane adds its column
+    double acc[MP];
+#pragma unroll
+    for (int m = 0; m < MP; ++m) acc[m] = -0.0;
+    int k = 0;
+    for (; k + kTransformAhead <= members; k += kTransformAhead) {
+        float f[kTransformAhead];
+#pragma unroll
+        for (int r = 0; r < kTransformAhead; ++r) f[r] = ld1(x + (size_t)(k + r) * ms + col);
+#pragma unroll
+        for (int r = 0; r < kTransformAhead; ++r) {
+            if constexpr (sizeof(S) != 4) f[r] = f[r] * inv;
+            transform_term<MP, DENSE>(acc, (double)f[r], table + (size_t)(k + r) * MP, DENSE ? 0ull : bits[k + r]);
+        }
+    }
+    for (; k < members; ++k) {
+        float f = ld1(x + (size_t)k * ms + col);
+        if constexpr (sizeof(S) != 4) f = f * inv;
+        transform_term<MP, DENSE>(acc, (double)f, table + (size_t)k * MP, DENSE ? 0ull : bits[k]);
+    }
+    const double g = (double)gf;
+    constexpr int GROUP = MP < kTransformAhead ? MP : kTransformAhead;      // the loads of a group precede its stores
+#pragma unroll
+    for (int m0 = 0; m0 < MP; m0 += GROUP) {
+        float xm[GROUP];
+        bool take[GROUP];                                                   // uniform: scalar tests
+#pragma unroll
+        for (int r = 0; r < GROUP; ++r) {
+            take[r] = m0 + r < members && ((used >> (m0 + r)) & 1ull);
+            xm[r] = take[r] ? ld1(x + (size_t)(m0 + r) * ms + col) : 0.0f;
+            if constexpr (sizeof(S) != 4) xm[r] = xm[r] * inv;
+        }
+#pragma unroll
+        for (int r = 0; r < GROUP; ++r) {
+            if (!take[r]) continue;
+            float y = tapered(xm[r], g, acc[m0 + r]);
+            if constexpr (sizeof(S) != 4) y = as_stored<S>(y) * scale;      // narrow(y), then the field's scale
+            st1(x + (size_t)(m0 + r) * ms + col, y);
+        }
+    }
+}
+
+// one thread per cell of the dense (w x w) taper; the definition is fluid_kernels.h's, shared with the host's bounding box
+__global__ __launch_bounds__(256) void k_taper_gaspari_cohn(float* __restrict__ out, int w, double col, double row, double c)
+{
+    const unsigned j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= (unsigned)w) return;
+    const unsigned i = blockIdx.y;
+    out[(size_t)i * (size_t)w + j] = (float)taper_value(taper_radius((double)j - col, (double)i - row, c));
+}
+
+// ---------------------------------------------------------------------------
 // launch wrappers (host).  Shapes are validated by the caller (fluid_solver).
 // `st` selects the field storage type the untyped pointers refer to.
 // ---------------------------------------------------------------------------
@@ -2860,6 +2946,41 @@ void launch_transform_members(hipStream_t s, int st, void* x, int pitch, int n, 
         FLUID_TRANSFORM_CASE(64);
     }
 #undef FLUID_TRANSFORM_CASE
+}
+
+// as launch_transform_members; the box is not empty and lies inside the (n + 2)^2 array (fluid_solver checks both)
+void launch_transform_members_local(hipStream_t s, int st, void* x, int pitch, int n, Members mb, float inv, float scale,
+                                    const double* table, const unsigned long long* bits, unsigned long long used, bool dense,
+                                    const float* taper, CellBox box)
+{
+    const dim3 grid(cdiv((unsigned)(box.col_hi - box.col_lo), 256), (unsigned)(box.row_hi - box.row_lo));
+#define FLUID_LOCAL_CASE(MP)                                                                                                             \
+    case MP:                                                                                                                             \
+        if (dense)                                                                                                                       \
+            FLUID_BY_STORAGE(st, hipLaunchKernelGGL((k_transform_members_local<S, MP, true>), grid, dim3(256), 0, s, (S*)x, pitch, n + 2, \
+                                                    mb.stride, mb.count, inv, scale, table, bits, used, taper, box.row_lo, box.col_lo,   \
+                                                    box.col_hi));                                                                        \
+        else                                                                                                                             \
+            FLUID_BY_STORAGE(st, hipLaunchKernelGGL((k_transform_members_local<S, MP, false>), grid, dim3(256), 0, s, (S*)x, pitch,      \
+                                                    n + 2, mb.stride, mb.count, inv, scale, table, bits, used, taper, box.row_lo,        \
+                                                    box.col_lo, box.col_hi));                                                            \
+        break
+    switch (transform_padded(mb.count)) {
+        FLUID_LOCAL_CASE(1);
+        FLUID_LOCAL_CASE(2);
+        FLUID_LOCAL_CASE(4);
+        FLUID_LOCAL_CASE(8);
+        FLUID_LOCAL_CASE(16);
+        FLUID_LOCAL_CASE(32);
+        FLUID_LOCAL_CASE(64);
+    }
+#undef FLUID_LOCAL_CASE
+}
+
+void launch_taper_gaspari_cohn(hipStream_t s, float* out, int n, float col, float row, float c)
+{
+    const dim3 grid(cdiv((unsigned)(n + 2), 256), (unsigned)(n + 2));
+    hipLaunchKernelGGL(k_taper_gaspari_cohn, grid, dim3(256), 0, s, out, n + 2, (double)col, (double)row, (double)c);
 }
 
 }  // namespace fluid

@@ -2813,8 +2813,18 @@ static int ensure_transform(fluid_ctx* c, const char* call)
     return FLUID_OK;
 }
 
-// weights: M * M floats, weights[k * M + m] the weight of OLD member k in NEW member m, all finite (the entry points check)
-static int transform_body(fluid_ctx* c, const char* call, const int* fields, int nfields, const float* weights)
+// One call's table on its way to the device: `weights` -- M * M floats, weights[k * M + m] the weight of OLD member k in
+// (the increment of) NEW member m, all finite (the entry points check) -- widened into the next slot of the ring and
+// copied on the context's stream.  What the kernels take of it: the device addresses, `used` (a bit for every column with
+// a term) and whether every weight of the M x M matrix is non-zero.
+struct StagedTable {
+    const double* table = nullptr;
+    const unsigned long long* bits = nullptr;
+    unsigned long long used = 0;
+    bool dense = true;
+};
+
+static int stage_transform_table(fluid_ctx* c, const char* call, const float* weights, StagedTable* out)
 {
     const int M = c->members, MP = fluid::transform_padded(M);
     TRY(ensure_transform(c, call));
@@ -2823,32 +2833,39 @@ static int transform_body(fluid_ctx* c, const char* call, const int* fields, int
     if (t.in_use[s]) HIP_TRY(hipEventSynchronize(t.copied[s]));      // a formality unless kSlots calls are still queued
     double* table = reinterpret_cast<double*>(t.host + (size_t)s * t.slot);
     unsigned long long* bits = reinterpret_cast<unsigned long long*>(table + (size_t)M * MP);
-    unsigned long long used = 0;
-    bool dense = true;
+    StagedTable st;
     for (int k = 0; k < M; ++k) {
         unsigned long long row = 0;
         for (int m = 0; m < MP; ++m) {
             const float w = m < M ? weights[(size_t)k * M + m] : 0.0f;
             table[(size_t)k * MP + m] = (double)w;
             if (w != 0.0f) row |= 1ull << m;
-            else if (m < M) dense = false;
+            else if (m < M) st.dense = false;
         }
         bits[k] = row;
-        used |= row;
+        st.used |= row;
     }
-    const unsigned long long empty = ~used;                          // (bits past M are never looked at)
     char* dev = t.dev + (size_t)s * t.slot;
     HIP_TRY(hipMemcpyAsync(dev, table, transform_table_bytes(M), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipEventRecord(t.copied[s], c->stream));
     t.in_use[s] = true;
     t.next = (s + 1) % TransformTables::kSlots;
-    const double* dtable = reinterpret_cast<const double*>(dev);
-    const unsigned long long* dbits = reinterpret_cast<const unsigned long long*>(dtable + (size_t)M * MP);
+    st.table = reinterpret_cast<const double*>(dev);
+    st.bits = reinterpret_cast<const unsigned long long*>(st.table + (size_t)M * MP);
+    *out = st;
+    return FLUID_OK;
+}
+
+static int transform_body(fluid_ctx* c, const char* call, const int* fields, int nfields, const float* weights)
+{
+    StagedTable t;
+    TRY(stage_transform_table(c, call, weights, &t));
+    const unsigned long long empty = ~t.used;                        // (bits past M are never looked at)
     for (int k = 0; k < nfields; ++k) {
         const int f = fields[k];
         const float inv = c->st != fluid::STORAGE_F32 ? 1.0f / c->field[f].fscale : 1.0f;      // as pack_range sees the field
         TRY(materialize(c, f, /*keep_scale=*/inv != 1.0f));
-        fluid::launch_transform_members(c->stream, c->st, c->ptr(f), c->pitch, c->n, c->mb(), inv, dtable, dbits, empty, dense);
+        fluid::launch_transform_members(c->stream, c->st, c->ptr(f), c->pitch, c->n, c->mb(), inv, t.table, t.bits, empty, t.dense);
         HIP_TRY(hipGetLastError());
         wrote(c, f, kEverywhere);                                    // plain values (scale 1), nothing owed
     }
@@ -2900,6 +2917,104 @@ int fluid_select_members(fluid_ctx* c, const int* fields, int nfields, const int
         onehot[(size_t)source[m] * M + m] = 1.0f;
     }
     return transform_body(c, "fluid_select_members", fields, nfields, onehot.data());
+}
+
+// ---- localised updates: fluid_transform_members_local / fluid_taper_gaspari_cohn ------------------------------------------
+// (include/fluid_amd.h "localised updates".)  The increment of a transform under a per-cell taper, over a box of cells: the
+// table of increments goes through the ring of the transform (stage_transform_table), every listed field is settled as
+// pack_range settles it -- what it owes itself is added, a scale is KEPT: the launch stores some cells only, and a pass
+// over the others to divide a scale back would cost the grid, not the box, and round the half denormals -- and one launch
+// per field covers the box.  No wait; the launches belong to none of the timing categories.
+static const char* const kBoxEntry[4] = {"row_lo", "row_hi", "col_lo", "col_hi"};
+
+int fluid_transform_members_local(fluid_ctx* c, const int* fields, int nfields, const float* increments, const void* taper_dev,
+                                  const int* box)
+{
+    const char* call = "fluid_transform_members_local";
+    if (!fields) return fail(FLUID_E_INVALID, "%s: null array `fields`", call);
+    if (!increments) return fail(FLUID_E_INVALID, "%s: null array `increments`", call);
+    if (!c) return fail(FLUID_E_INVALID, "%s: null context", call);
+    TRY(check_transform(c, call, fields, nfields));
+    const int M = c->members;
+    for (int k = 0; k < M; ++k)
+        for (int m = 0; m < M; ++m)
+            if (!std::isfinite(increments[(size_t)k * M + m]))
+                return fail(FLUID_E_INVALID, "%s: increments[%d * M + %d] (old member k = %d, new member m = %d) is not finite", call, k, m, k, m);
+    fluid::CellBox b = {0, c->w, 0, c->w};
+    if (box) {
+        for (int e = 0; e < 4; ++e)
+            if (box[e] < 0 || box[e] > c->w)
+                return fail(FLUID_E_INVALID, "%s: box[%d] = %d (%s) outside [0, %d]", call, e, box[e], kBoxEntry[e], c->w);
+        for (int e = 0; e < 4; e += 2)
+            if (box[e] > box[e + 1])
+                return fail(FLUID_E_INVALID, "%s: box[%d] = %d (%s) is above box[%d] = %d (%s)", call, e, box[e], kBoxEntry[e], e + 1, box[e + 1],
+                            kBoxEntry[e + 1]);
+        b = {box[0], box[1], box[2], box[3]};
+    }
+    if (taper_dev) TRY(check_device_span(c, call, "taper_dev", taper_dev, member_cells(c) * sizeof(float)));
+    StagedTable t;
+    if (!b.empty()) TRY(stage_transform_table(c, call, increments, &t));
+    const bool launch = !b.empty() && (t.used & (M < 64 ? (1ull << M) - 1 : ~0ull)) != 0;      // (no term anywhere: nothing is stored)
+    for (int k = 0; k < nfields; ++k) {
+        const int f = fields[k];
+        const float scale = c->st != fluid::STORAGE_F32 ? c->field[f].fscale : 1.0f;           // as pack_range sees the field
+        TRY(materialize(c, f, /*keep_scale=*/scale != 1.0f));
+        if (!launch) continue;
+        fluid::launch_transform_members_local(c->stream, c->st, c->ptr(f), c->pitch, c->n, c->mb(), 1.0f / scale, scale, t.table, t.bits,
+                                              t.used, t.dense, static_cast<const float*>(taper_dev), b);
+        HIP_TRY(hipGetLastError());
+        wrote(c, f, kEverywhere);                                    // nothing owed ...
+        c->field[f].fscale = scale;                                  // ... and the scale it had: the launch stored at it
+    }
+    return FLUID_OK;
+}
+
+// The cells a taper can be non-zero in, on the host: along each axis the indices whose cell on the nearest row (column) of
+// the other axis has r < 2 -- r falls with the other axis' distance, rounding included, so no other row can add a column
+// -- by the kernel's own function, then one cell more on each side: what a rounding that differs between the host and the
+// device could move.  No such index: the empty box {0, 0, 0, 0}.
+static void taper_box(const fluid_ctx* c, float col, float row, float hw, int* box)
+{
+    const double centre[2] = {(double)row, (double)col}, hwd = (double)hw;
+    int first[2], last[2], nearest[2];
+    for (int a = 0; a < 2; ++a) nearest[a] = std::min(c->w - 1, std::max(0, (int)std::lround(centre[a])));
+    for (int a = 0; a < 2; ++a) {
+        const double other = (double)nearest[1 - a] - centre[1 - a];
+        const double reach = std::min(2.0 * hwd, (double)c->w) + 1.0;
+        const int lo = (int)std::max(0.0, std::floor(centre[a] - reach)), hi = (int)std::min((double)(c->w - 1), std::ceil(centre[a] + reach));
+        first[a] = c->w;
+        last[a] = -1;
+        for (int i = lo; i <= hi; ++i)
+            if (fluid::taper_radius((double)i - centre[a], other, hwd) < 2.0) {
+                first[a] = std::min(first[a], i);
+                last[a] = i;
+            }
+    }
+    if (last[0] < 0 || last[1] < 0) {
+        box[0] = box[1] = box[2] = box[3] = 0;
+        return;
+    }
+    for (int a = 0; a < 2; ++a) {
+        box[2 * a] = std::max(0, first[a] - 1);
+        box[2 * a + 1] = std::min(c->w, last[a] + 2);
+    }
+}
+
+int fluid_taper_gaspari_cohn(fluid_ctx* c, float col, float row, float hw, void* out_dev, int* box)
+{
+    const char* call = "fluid_taper_gaspari_cohn";
+    if (!out_dev) return fail(FLUID_E_INVALID, "%s: null device pointer `out_dev`", call);
+    if (!c) return fail(FLUID_E_INVALID, "%s: null context", call);
+    TRY(refuse_slabs(c, call));
+    const float top = (float)c->n + 0.5f;
+    if (!std::isfinite(col) || col < 0.5f || col > top) return fail(FLUID_E_INVALID, "%s: col = %g is not finite or outside [0.5, %g]", call, (double)col, (double)top);
+    if (!std::isfinite(row) || row < 0.5f || row > top) return fail(FLUID_E_INVALID, "%s: row = %g is not finite or outside [0.5, %g]", call, (double)row, (double)top);
+    if (!std::isfinite(hw) || !(hw > 0.0f)) return fail(FLUID_E_INVALID, "%s: c = %g is not finite or not above 0", call, (double)hw);
+    TRY(check_device_span(c, call, "out_dev", out_dev, member_cells(c) * sizeof(float)));
+    fluid::launch_taper_gaspari_cohn(c->stream, static_cast<float*>(out_dev), c->n, col, row, hw);
+    HIP_TRY(hipGetLastError());
+    if (box) taper_box(c, col, row, hw, box);
+    return FLUID_OK;
 }
 
 // The staging buffer of the bulk host copies: g = max(1, min(M, 64 MiB / member bytes)) dense members.  The 64 MiB is a

@@ -458,6 +458,48 @@ class FluidSolver:
         capi.check(capi.lib().fluid_ensemble_stats_ptr(self._h, C.byref(mu), C.byref(var)))
         return mu.value, var.value
 
+    # -- localised updates: the increment of a transform under a per-cell taper, over a box of cells
+    def transform_local(self, increments, taper=None, box=None, fields=("u", "v", "dens")):
+        """X' = X + g o (X D) per cell of each listed field, in place, one launch per field over the box only and no wait:
+        increments[k][m] is the weight of OLD member k in the INCREMENT of new member m (D = T - I for a transform T).
+        `taper`: a device buffer of (N+2) x (N+2) floats (as pack takes one; taper_gaspari_cohn makes one), None for 1
+        everywhere; torch's current stream is waited for before the launch, and the solver keeps the buffer referenced
+        until the next call.  `box`: (row_lo, row_hi, col_lo, col_hi), half-open, None for the whole array.  Cells
+        outside the box or with taper 0 keep their bits (include/fluid_amd.h, "localised updates").
+        members <= capi.TRANSFORM_MAX_MEMBERS."""
+        d = np.ascontiguousarray(np.asarray(increments, np.float32))
+        if d.shape != (self.members, self.members):
+            raise ValueError("increments must have shape (%d, %d), got %s" % (self.members, self.members, d.shape))
+        w = self.n + 2
+        address = None
+        if taper is not None:
+            if device_floats(taper, w * w) < w * w:
+                raise ValueError("taper must hold (N+2)^2 = %d floats, got %d" % (w * w, device_floats(taper, w * w)))
+            address = device_address(taper)
+            self._handover(True)
+        if box is not None:
+            b = [int(v) for v in box]
+            if len(b) != 4:
+                raise ValueError("box must be (row_lo, row_hi, col_lo, col_hi), got %d values" % len(b))
+            box = (C.c_int * 4)(*b)
+        ids = [_fid(f) for f in fields]
+        capi.check(capi.lib().fluid_transform_members_local(self._h, (C.c_int * len(ids))(*ids), len(ids), _mf(d), address, box))
+        self._taper = taper
+
+    def taper_gaspari_cohn(self, col, row, c):
+        """The Gaspari-Cohn taper of half-width c (support radius 2c) about (col, row), in the cell-index coordinates of
+        set_observation_points: ((N+2, N+2) float32 torch tensor on the device, box) -- the box (row_lo, row_hi, col_lo,
+        col_hi) holds every non-zero cell; both are what transform_local takes.  Waits for the context's stream: the tensor
+        is complete on return."""
+        import torch
+        w = self.n + 2
+        out = torch.empty((w, w), dtype=torch.float32, device="cuda")
+        box = (C.c_int * 4)()
+        self._handover(True)
+        capi.check(capi.lib().fluid_taper_gaspari_cohn(self._h, float(col), float(row), float(c), device_address(out), box))
+        self.synchronize()
+        return out, tuple(box)
+
     def set_jacobi_variant(self, variant):
         capi.check(capi.lib().fluid_set_jacobi_variant(self._h, variant))
 

@@ -550,6 +550,78 @@ int fluid_observe_members_host(fluid_ctx *ctx, int field, float *host);
 int fluid_observation_gram(fluid_ctx *ctx, int field, int centre, const float *obs, const float *inv_sigma,
                            double *gram, double *rhs, double *dd);
 
+/* ---- localised updates: the increment of a transform under a per-cell taper, over a box of cells ------------------
+ * M = fluid_members(ctx), W = N + 2.  With at most FLUID_TRANSFORM_MAX_MEMBERS members against N*N states a global
+ * ensemble update is rank-deficient and full of spurious long-range covariances; every practical scheme (LETKF, EnSRF)
+ * lets a batch of nearby observations change the state only inside a compactly supported taper around it:
+ *     X' = X + g o (X D)
+ * per cell, X the ensemble there, D an M x M matrix, g the taper's value at the cell.  One local analysis is
+ * fluid_observation_gram -> M x M algebra on the host -> fluid_taper_gaspari_cohn -> fluid_transform_members_local, and the
+ * last call costs what the taper's support costs, not what the grid costs.
+ *
+ * - fluid_transform_members_local: `increments` is host memory, M*M finite floats; increments[k*M + m] is the weight of
+ *   OLD member k in the INCREMENT of new member m: an ensemble transform T is D = T - I, formed by the caller (D and not T
+ *   keeps every product exact, step 3).  `fields`: nfields distinct field ids, host memory.  `taper_dev`: a dense DEVICE
+ *   array of W*W floats, row-major with the ghost ring -- the layout of one member of a dense pack -- shared by all members
+ *   and all listed fields, aligned to 4 bytes; null: g = 1 everywhere.  `box`: host memory, four ints {row_lo, row_hi,
+ *   col_lo, col_hi}, half-open ranges inside [0, W]; cells outside the box are neither read nor written and the taper is
+ *   not read there; null: the whole W x W array.  An empty box is legal: nothing is launched, the fields are still settled.
+ *   One kernel launch per listed field whatever M is, its grid the box, enqueued on the context's stream, no wait; the host
+ *   arrays belong to the caller again when the call returns, the taper when the stream has passed the launches.  The table
+ *   of increments travels through the ring of fluid_transform_members: successive calls with different matrices need no
+ *   wait.
+ *   Definition -- per listed field, per cell of the box, per new member m; pad columns are neither read nor written:
+ *    1. The field's lazy state is settled for all members first, as fluid_pack_members settles it: x_k is the float the
+ *       pack would show for old member k right before the call.  With fp32 storage, and with fp16 storage wherever the
+ *       field holds plain values (scale 1), that is the stored value widened exactly.  An fp16 field held at a pressure
+ *       scale KEEPS it -- dividing it back would be a pass over the whole grid and would round the half denormals of the
+ *       cells outside the box -- and x_k is the stored value widened exactly and divided by the scale in float, exactly, as
+ *       the pack does.  Cells the call does not store keep their bits and show what the pack showed before the call.
+ *    2. The terms are the k in increasing order with increments[k*M + m] != 0.  A zero of either sign takes no part: a NaN
+ *       or inf member with increment 0 poisons nobody.  With no term at all, member m is stored nowhere.
+ *    3. s_m = (double)x_k * (double)d_k for the first term, then s_m = s_m + (double)x_k * (double)d_k for each further term
+ *       in member order.  Every product is exact in double (24 + 24 significand bits), so a fused and an unfused
+ *       multiply-add give the same bits, as in fluid_transform_members.
+ *    4. g = the taper at the cell (null taper: 1).  g == 0, of either sign: the cell is unchanged in every member -- not
+ *       stored, whatever s_m is, non-finite included.
+ *    5. Otherwise p = (double)g * s_m, rounded once; y_d = (double)x_m + p, rounded once, the two NOT contracted into one
+ *       fused operation; y = (float)y_d.  g = 1 makes p exact.
+ *    6. The store is narrow(y): with fp16 storage one more rounding to nearest even, as fluid_unpack_members does.  In a
+ *       field held at a scale s (a power of two) the half narrow(y) is stored times s, so that the pack shows narrow(y):
+ *       exact, unless |narrow(y)| * s exceeds 65504, the range the library itself keeps that field in; then +-inf.
+ *    7. All M old values of a cell are read before any new value of that cell is stored: the call is in place and means
+ *       what an out-of-place one would.
+ *    8. A NaN result is a NaN; its sign and payload are not specified.  A non-finite g gives non-finite results in that
+ *       cell only.
+ *   The order is part of the contract: the same bits for every launch shape; no atomics, no matrix instructions.  The
+ *   ghost ring is a cell like any other where the box includes it.  M in [1, FLUID_TRANSFORM_MAX_MEMBERS].
+ * - fluid_taper_gaspari_cohn: writes the whole dense W x W array `out_dev` (the layout `taper_dev` has), zeros outside the
+ *   support, in one launch on the context's stream, no wait.  `col`, `row`: the centre, in the cell-index coordinates of
+ *   fluid_set_observation_points, finite and in [0.5, N + 0.5]; `c`: the half-width, finite and > 0; the support is r < 2,
+ *   a disc of radius 2c.  Per cell (i, j), in IEEE double, every operation rounded once and none contracted:
+ *       dx = (double)j - (double)col;  dy = (double)i - (double)row;
+ *       r  = sqrt(dx*dx + dy*dy) / (double)c;
+ *       r <= 1:     g = ((((-0.25*r + 0.5)*r + 0.625)*r - 5.0/3.0)*r)*r + 1.0;
+ *       1 < r < 2:  g = ((((((1.0/12.0)*r - 0.5)*r + 0.625)*r + 5.0/3.0)*r - 5.0)*r + 4.0) - (2.0/3.0)/r;
+ *       r >= 2:     g = 0 exactly;
+ *   (Horner's rule, innermost parenthesis first; 5.0/3.0, 1.0/12.0 and 2.0/3.0 are the doubles nearest the quotients) --
+ *   the Gaspari-Cohn fifth-order function 1 - 5r^2/3 + 5r^3/8 + r^4/2 - r^5/4 and 4 - 5r + 5r^2/3 + 5r^3/8 - r^4/2 + r^5/12
+ *   - 2/(3r).  Then g is clamped to [0, 1] and rounded to float.  g is 1 at a centre that sits on a cell.
+ *   `box` (may be null) receives four ints as fluid_transform_members_local takes them, computed on the host by the same
+ *   function: it contains every cell with g != 0, and is at most one cell larger on each side than the tight box of the
+ *   cells with r < 2 (clipped to the array); {0, 0, 0, 0} when no cell has r < 2.
+ * Refusals, all FLUID_E_INVALID with a message that names the call and, where it applies, the k, m, list position or box
+ * entry, found before anything is launched or any state changes, null pointers before the context is looked at: a null
+ * `fields`, `increments` or `out_dev`, a null context; nfields outside [1, 12]; a bad field id; a field listed twice; a
+ * non-finite increment; a box entry outside [0, W] or a lo above its hi; M > FLUID_TRANSFORM_MAX_MEMBERS (the message
+ * gives both numbers); row slabs; a `col`, `row` or `c` that is not finite or out of range; a device pointer that is not
+ * device memory of the context's device or whose W*W floats do not lie inside one allocation (asked of the runtime on the
+ * host, as for a pack).
+ * The launches belong to none of the fluid_timing categories. */
+int fluid_transform_members_local(fluid_ctx *ctx, const int *fields, int nfields, const float *increments,
+                                  const void *taper_dev, const int *box);
+int fluid_taper_gaspari_cohn(fluid_ctx *ctx, float col, float row, float c, void *out_dev, int *box);
+
 int fluid_set_jacobi_variant(fluid_ctx *ctx, int variant);
 /* How FLUID_JACOBI_TB divides by `beta` in a solve with these coefficients (diagnostic; runs the on-device proof
  * if this beta has not been seen): 0 true division, 2 double-precision reciprocal, 3 two-term float reciprocal
