@@ -134,6 +134,18 @@ struct TransformTables {
     bool in_use[kSlots] = {};
 };
 
+// The node tables of fluid_transform_members_lattice: ONE device buffer with a pinned host twin, library-owned and outside
+// the arena, allocated or grown by the first call that needs the room and freed in fluid_destroy (fluid_solver.hip:
+// ensure_lattice).  Per call: [nodes][M][MP] doubles, then [nodes][M] words of non-zero bits, then [nodes] words of their
+// OR.  The copy runs on the context's stream behind the launches of the call before, so the device bytes need no wait;
+// the host bytes are refilled only after the event behind their last copy has completed.
+struct LatticeNodeTables {
+    char *dev = nullptr, *host = nullptr;
+    size_t bytes = 0;                     // the room of each
+    hipEvent_t copied = nullptr;
+    bool in_use = false;                  // `copied` has been recorded
+};
+
 // Observing ensembles (fluid_set_observation_points, fluid_observe_members, fluid_observation_gram): the network and the
 // scratch of its Gram call, library-owned and outside the arena (fluid_solver.hip: fluid_set_observation_points,
 // ensure_observation_gram), freed in fluid_destroy.  The network is ONE allocation of 32 bytes per point: four floats of
@@ -183,6 +195,7 @@ struct fluid_ctx {
     EnsembleReduce red;                   // results and scratch of the ensemble diagnostics
     MemberStage stage;                    // device staging of the bulk host copies
     TransformTables xform;                // weight tables of fluid_transform_members / fluid_select_members
+    LatticeNodeTables lattice;            // node tables of fluid_transform_members_lattice
     Observation observe;                  // the observation network and the scratch of fluid_observation_gram
     unsigned int* tiles = nullptr;        // 3 x members x tile_rows x tile_pitch words: |x0| minima per tile for division mode 3
     unsigned int* h_scalar = nullptr;     // pinned host mirror

@@ -232,6 +232,24 @@ struct CellBox {
 void launch_transform_members_local(hipStream_t s, int st, void* x, int pitch, int n, Members mb, float inv, float scale,
                                     const double* table, const unsigned long long* bits, unsigned long long used, bool dense,
                                     const float* taper, CellBox box);
+// Lattice updates (include/fluid_amd.h "lattice updates").  The node tables in device memory: `table`, per node the
+// [mb.count][MP] doubles of launch_transform_members (the node's increments, padding columns 0), nodes in row-major order;
+// `bits`, per node and old member the word of non-zero columns; `cols`, per node the OR of its words: the columns with a term.
+struct LatticeTables {
+    const double* table = nullptr;
+    const unsigned long long* bits = nullptr;
+    const unsigned long long* cols = nullptr;
+};
+// node (a, b) on cell row row0 + a * step, column col0 + b * step
+struct Lattice {
+    int nodes_row, nodes_col, row0, col0, step;
+};
+// Every cell of the (n + 2)^2 array, per member m with a term in a corner node of weight phi != 0: x_m = narrow((float)
+// (widen(x_m) + s)), s the sum over those corners, in row-major node order, of phi * (the node's member-order sum of
+// launch_transform_members) -- each product and sum rounded on its own, in double; the header has the rules.  `inv`,
+// `scale`: as for launch_transform_members_local.  dense: no increment of any node is zero.  One launch.
+void launch_transform_members_lattice(hipStream_t s, int st, void* x, int pitch, int n, Members mb, float inv, float scale,
+                                      const LatticeTables& t, bool dense, const Lattice& lat);
 // The Gaspari-Cohn taper of half-width c about (col, row), one definition for the kernel and for the host's bounding box:
 // taper_radius is r at a cell dx columns and dy rows from the centre, taper_value the piecewise polynomial in Horner form,
 // clamped to [0, 1]; every operation rounds once (no contraction), in double.

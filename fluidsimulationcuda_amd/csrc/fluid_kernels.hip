@@ -2525,6 +2525,145 @@ __global__ __launch_bounds__(256) void k_transform_members_local(S* __restrict__
     }
 }
 
+// ---------------------------------------------------------------------------
+// lattice updates (include/fluid_amd.h "lattice updates"): X' = X + sum_b phi_b o (X D_b), the increment matrices D given at
+// the nodes of a coarse lattice and blended bilinearly to every cell, every product on the OLD X, in place, one launch.
+// A wave owns a patch of 64 cells, 2^lpc columns by 64 >> lpc rows, aligned to the lattice's origin; the spacing is a
+// multiple of both sides, so a patch lies inside one lattice cell: its (up to) four corner nodes -- hence the four tables,
+// their words of non-zero bits and which corners exist -- are wave-uniform and the weights stay scalar-load operands of
+// v_fma_f64 as in k_transform_members (transform_term).  Only phi is per lane.  The widest patch the spacing allows is
+// taken (one row of 64 columns at a multiple of 64): the bits do not depend on it.
+// Two full accumulator sets (node sum and blend) would be 256 VGPRs at MP = 64.  Instead the new members are taken in
+// chunks of 16: per chunk 16 blend sums, and per corner 16 node sums that are folded into them -- 64 VGPRs -- and each
+// chunk and corner walks the old members again as k_transform_members does, kTransformAhead loads in flight, from the
+// cache (a patch is members x 256 bytes).  Since a later chunk reads what an earlier one would have stored, nothing is
+// stored before the last walk: a chunk's results wait as floats, MP VGPRs more.  (Keeping the OLD values in registers
+// and walking them by an unrolled loop instead reads each once, but the scalar loads of 64 unrolled rows spill 60 to 170
+// SGPRs into VGPR lanes at MP >= 16 and leave two waves per SIMD at MP = 64.)  A node sum starts at -0.0 like every sum of
+// transform_term; so does the blend: -0.0 + p == p for every p, and a corner that takes no part in a lane (phi == 0 there,
+// or no term in that column) adds -0.0 by select, so its inf or NaN never meets the sum.  Corners with phi == 0 in the whole
+// wave, or without a term in the chunk, are skipped by uniform branches: that is every corner but one outside the hull and
+// on a 1 x 1 lattice.  A (lane, member) no corner takes part in is not stored; the others store narrow((float)(x_m + s))
+// times the field's scale.  Row and member bases are 64-bit scalar arithmetic; a lane adds a 32-bit offset inside its
+// patch.  Lanes of an edge patch that fall outside the array are masked.  No LDS, no atomics.
+// ---------------------------------------------------------------------------
+struct LatticeAxis {
+    int a;           // the lower node of the lattice cell: wave-uniform
+    double t0, t1;   // this lane's weights of nodes a and a + 1
+};
+
+// rule 2 of the header; q0 = the patch's first index less the origin (a multiple of the patch side), q = the lane's
+__device__ __forceinline__ LatticeAxis lattice_axis(int nodes, int step, long long q0, long long q)
+{
+    const long long last = (long long)(nodes - 1) * (long long)step;
+    LatticeAxis ax;
+    ax.a = (nodes == 1 || q0 <= 0) ? 0 : q0 >= last ? nodes - 2 : (int)(q0 / step);
+    if (nodes == 1 || q <= 0) ax.t1 = 0.0;
+    else if (q >= last) ax.t1 = 1.0;
+    else ax.t1 = (double)(q - (long long)ax.a * (long long)step) / (double)step;
+    ax.t0 = 1.0 - ax.t1;
+    return ax;
+}
+
+template <typename S, int MP, bool DENSE>
+__global__ __launch_bounds__(256) void k_transform_members_lattice(S* __restrict__ x, int pitch, int w, size_t ms, int members, float inv,
+                                                                   float scale, const double* __restrict__ table,
+                                                                   const unsigned long long* __restrict__ bits,
+                                                                   const unsigned long long* __restrict__ cols, int nodes_row,
+                                                                   int nodes_col, long long row0, long long col0, int step, int lpc,
+                                                                   int row_off, int col_off)
+{
+#pragma clang fp contract(off)
+    constexpr int CH = MP < 16 ? MP : 16;
+    constexpr unsigned long long CMASK = (1ull << CH) - 1ull;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = (int)(threadIdx.x & 63u);
+    const int pj = ((int)blockIdx.x * 4 + wave) * (1 << lpc) - col_off;      // the patch's first column and row: scalar,
+    const int pi = (int)blockIdx.y * (64 >> lpc) - row_off;                   // negative where the origin's phase says so
+    if (pj >= w) return;                                                       // (the whole wave)
+    const int lr = lane >> lpc, lc = lane & ((1 << lpc) - 1);
+    const int i = pi + lr, j = pj + lc;
+    const bool live = (unsigned)i < (unsigned)w && (unsigned)j < (unsigned)w;
+    const LatticeAxis ar = lattice_axis(nodes_row, step, (long long)pi - row0, (long long)i - row0);
+    const LatticeAxis ac = lattice_axis(nodes_col, step, (long long)pj - col0, (long long)j - col0);
+    // the corners in row-major node order: (a, b), (a, b + 1), (a + 1, b), (a + 1, b + 1)
+    const double phi0 = live ? __dmul_rn(ar.t0, ac.t0) : 0.0, phi1 = live ? __dmul_rn(ar.t0, ac.t1) : 0.0;
+    const double phi2 = live ? __dmul_rn(ar.t1, ac.t0) : 0.0, phi3 = live ? __dmul_rn(ar.t1, ac.t1) : 0.0;
+    unsigned long long ccols[4];      // per corner the columns with a term, 0 where the corner takes no part in this wave
+    size_t cnode[4];
+    unsigned long long any = 0, mine = 0;      // columns some corner of the wave has; columns this lane stores
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const int ca = ar.a + (c >> 1), cb = ac.a + (c & 1);
+        const double phi = c == 0 ? phi0 : c == 1 ? phi1 : c == 2 ? phi2 : phi3;
+        const bool exists = ca < nodes_row && cb < nodes_col;
+        cnode[c] = exists ? (size_t)ca * (size_t)nodes_col + (size_t)cb : 0;
+        ccols[c] = exists && __builtin_amdgcn_ballot_w64(phi != 0.0) != 0 ? cols[cnode[c]] : 0ull;
+        any |= ccols[c];
+        if (phi != 0.0) mine |= ccols[c];
+    }
+    if (any == 0) return;                                                      // uniform: nothing to store in this patch
+    const ptrdiff_t base = (ptrdiff_t)pi * (ptrdiff_t)pitch + (ptrdiff_t)pj + (ptrdiff_t)XOFF;      // scalar
+    const int at = lr * pitch + lc;                                            // the lane's offset inside the patch
+    const auto cell = [&](int m) { return x + (base + (ptrdiff_t)((size_t)m * ms)) + (unsigned)at; };      // scalar base + the lane's offset
+    float y[MP];
+#pragma unroll
+    for (int m0 = 0; m0 < MP; m0 += CH) {
+        if (m0 >= members || ((any >> m0) & CMASK) == 0) continue;             // uniform
+        double s[CH];
+#pragma unroll
+        for (int r = 0; r < CH; ++r) s[r] = -0.0;
+#pragma unroll 1
+        for (int c = 0; c < 4; ++c) {
+            const unsigned long long cc = (c == 0 ? ccols[0] : c == 1 ? ccols[1] : c == 2 ? ccols[2] : ccols[3]) >> m0;
+            if ((cc & CMASK) == 0) continue;
+            const size_t node = c == 0 ? cnode[0] : c == 1 ? cnode[1] : c == 2 ? cnode[2] : cnode[3];
+            const double phi = c == 0 ? phi0 : c == 1 ? phi1 : c == 2 ? phi2 : phi3;
+            const double* __restrict__ tab = table + node * (size_t)members * (size_t)MP + (size_t)m0;
+            const unsigned long long* __restrict__ nb = bits + node * (size_t)members;
+            double t[CH];
+#pragma unroll
+            for (int r = 0; r < CH; ++r) t[r] = -0.0;
+            int k = 0;
+            for (; k + kTransformAhead <= members; k += kTransformAhead) {
+                float f[kTransformAhead];
+#pragma unroll
+                for (int r = 0; r < kTransformAhead; ++r) f[r] = live ? ld1(cell(k + r)) : 0.0f;
+#pragma unroll
+                for (int r = 0; r < kTransformAhead; ++r) {
+                    if constexpr (sizeof(S) != 4) f[r] = f[r] * inv;
+                    transform_term<CH, DENSE>(t, (double)f[r], tab + (size_t)(k + r) * MP, DENSE ? 0ull : (nb[k + r] >> m0) & CMASK);
+                }
+            }
+            for (; k < members; ++k) {
+                float f = live ? ld1(cell(k)) : 0.0f;
+                if constexpr (sizeof(S) != 4) f = f * inv;
+                transform_term<CH, DENSE>(t, (double)f, tab + (size_t)k * MP, DENSE ? 0ull : (nb[k] >> m0) & CMASK);
+            }
+            const bool lane_in = phi != 0.0;
+#pragma unroll
+            for (int r = 0; r < CH; ++r) {
+                const double p = __dmul_rn(phi, t[r]);
+                s[r] = __dadd_rn(s[r], lane_in && ((cc >> r) & 1ull) ? p : -0.0);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < CH; ++r) {
+            const bool put = m0 + r < members && ((mine >> (m0 + r)) & 1ull);
+            float xm = put ? ld1(cell(m0 + r)) : 0.0f;
+            if constexpr (sizeof(S) != 4) xm = xm * inv;
+            y[m0 + r] = (float)__dadd_rn((double)xm, s[r]);
+        }
+    }
+#pragma unroll
+    for (int m = 0; m < MP; ++m) {
+        if (!(m < members && ((any >> m) & 1ull))) continue;                   // uniform; `mine` is the lane's own
+        if (!((mine >> m) & 1ull)) continue;
+        float v = y[m];
+        if constexpr (sizeof(S) != 4) v = as_stored<S>(v) * scale;             // narrow(y), then the field's scale
+        st1(cell(m), v);
+    }
+}
+
 // one thread per cell of the dense (w x w) taper; the definition is fluid_kernels.h's, shared with the host's bounding box
 __global__ __launch_bounds__(256) void k_taper_gaspari_cohn(float* __restrict__ out, int w, double col, double row, double c)
 {
@@ -2975,6 +3114,44 @@ void launch_transform_members_local(hipStream_t s, int st, void* x, int pitch, i
         FLUID_LOCAL_CASE(64);
     }
 #undef FLUID_LOCAL_CASE
+}
+
+// as launch_transform_members_local without taper and box; the lattice is valid (fluid_solver checks it): step a positive
+// multiple of 8, at least one node each way.  A patch is the widest power of two of columns, up to 64, that divides step.
+void launch_transform_members_lattice(hipStream_t s, int st, void* x, int pitch, int n, Members mb, float inv, float scale,
+                                      const LatticeTables& t, bool dense, const Lattice& lat)
+{
+    const int w = n + 2;
+    int lpc = 3;
+    while (lpc < 6 && lat.step % (2 << lpc) == 0) ++lpc;
+    const int pc = 1 << lpc, pr = 64 >> lpc;
+    // the first patch starts at or before cell 0, on the origin's phase
+    const int col_off = (int)((((long long)lat.col0 % pc) + pc) % pc), row_off = (int)((((long long)lat.row0 % pr) + pr) % pr);
+    const int cshift = (pc - col_off) % pc, rshift = (pr - row_off) % pr;
+    const dim3 grid(cdiv(cdiv((unsigned)(w + cshift), (unsigned)pc), 4), cdiv((unsigned)(w + rshift), (unsigned)pr));
+#define FLUID_LATTICE_CASE(MP)                                                                                                            \
+    case MP:                                                                                                                              \
+        if (dense)                                                                                                                        \
+            FLUID_BY_STORAGE(st, hipLaunchKernelGGL((k_transform_members_lattice<S, MP, true>), grid, dim3(256), 0, s, (S*)x, pitch, w,   \
+                                                    mb.stride, mb.count, inv, scale, t.table, t.bits, t.cols, lat.nodes_row,              \
+                                                    lat.nodes_col, (long long)lat.row0, (long long)lat.col0, lat.step, lpc, rshift,       \
+                                                    cshift));                                                                             \
+        else                                                                                                                              \
+            FLUID_BY_STORAGE(st, hipLaunchKernelGGL((k_transform_members_lattice<S, MP, false>), grid, dim3(256), 0, s, (S*)x, pitch, w,  \
+                                                    mb.stride, mb.count, inv, scale, t.table, t.bits, t.cols, lat.nodes_row,              \
+                                                    lat.nodes_col, (long long)lat.row0, (long long)lat.col0, lat.step, lpc, rshift,       \
+                                                    cshift));                                                                             \
+        break
+    switch (transform_padded(mb.count)) {
+        FLUID_LATTICE_CASE(1);
+        FLUID_LATTICE_CASE(2);
+        FLUID_LATTICE_CASE(4);
+        FLUID_LATTICE_CASE(8);
+        FLUID_LATTICE_CASE(16);
+        FLUID_LATTICE_CASE(32);
+        FLUID_LATTICE_CASE(64);
+    }
+#undef FLUID_LATTICE_CASE
 }
 
 void launch_taper_gaspari_cohn(hipStream_t s, float* out, int n, float col, float row, float c)

@@ -1870,6 +1870,9 @@ int fluid_destroy(fluid_ctx* c)
         if (ev) (void)hipEventDestroy(ev);
     if (c->xform.dev) (void)hipFree(c->xform.dev);
     if (c->xform.host) (void)hipHostFree(c->xform.host);
+    if (c->lattice.copied) (void)hipEventDestroy(c->lattice.copied);
+    if (c->lattice.dev) (void)hipFree(c->lattice.dev);
+    if (c->lattice.host) (void)hipHostFree(c->lattice.host);
     if (c->d_partials) (void)hipFree(c->d_partials);
     if (c->scalar_ready) (void)hipEventDestroy(c->scalar_ready);
     if (c->own_arena && c->arena) (void)hipFree(c->arena);
@@ -3014,6 +3017,110 @@ int fluid_taper_gaspari_cohn(fluid_ctx* c, float col, float row, float hw, void*
     fluid::launch_taper_gaspari_cohn(c->stream, static_cast<float*>(out_dev), c->n, col, row, hw);
     HIP_TRY(hipGetLastError());
     if (box) taper_box(c, col, row, hw, box);
+    return FLUID_OK;
+}
+
+// ---- lattice updates: fluid_transform_members_lattice ---------------------------------------------------------------------
+// (include/fluid_amd.h "lattice updates".)  The increments of every node go into ONE table buffer (fluid_ctx.h:
+// LatticeNodeTables) and travel on the context's stream; every listed field is settled as the local call settles it, scale
+// kept, and one launch per field covers the whole array.  No wait unless the call before this one has not finished copying
+// its tables out of the pinned twin; the launches belong to none of the timing categories.
+static int ensure_lattice(fluid_ctx* c, const char* call, size_t bytes)
+{
+    LatticeNodeTables& t = c->lattice;
+    if (t.bytes >= bytes) return FLUID_OK;
+    char *dev = nullptr, *host = nullptr;
+    hipError_t e = hipMalloc((void**)&dev, bytes);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&host, bytes, hipHostMallocDefault);
+    if (e == hipSuccess && !t.copied) e = hipEventCreateWithFlags(&t.copied, hipEventDisableTiming);
+    if (e != hipSuccess) {          // (the old, smaller buffers stay: the context is as it was)
+        (void)hipGetLastError();
+        if (dev) (void)hipFree(dev);
+        if (host) (void)hipHostFree(host);
+        return fail(e == hipErrorOutOfMemory ? FLUID_E_NOMEM : FLUID_E_HIP, "%s: allocating node tables of %zu bytes: %s", call, bytes,
+                    hipGetErrorString(e));
+    }
+    if (t.dev) {                    // growing: earlier lattice launches may still read the old tables
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        (void)hipFree(t.dev);
+        (void)hipHostFree(t.host);
+        t.in_use = false;
+    }
+    t.dev = dev;
+    t.host = host;
+    t.bytes = bytes;
+    return FLUID_OK;
+}
+
+int fluid_transform_members_lattice(fluid_ctx* c, const int* fields, int nfields, const float* increments, int nodes_row, int nodes_col,
+                                    int row0, int col0, int step)
+{
+    const char* call = "fluid_transform_members_lattice";
+    if (!fields) return fail(FLUID_E_INVALID, "%s: null array `fields`", call);
+    if (!increments) return fail(FLUID_E_INVALID, "%s: null array `increments`", call);
+    if (!c) return fail(FLUID_E_INVALID, "%s: null context", call);
+    TRY(check_transform(c, call, fields, nfields));
+    if (nodes_row < 1) return fail(FLUID_E_INVALID, "%s: nodes_row = %d is below 1", call, nodes_row);
+    if (nodes_col < 1) return fail(FLUID_E_INVALID, "%s: nodes_col = %d is below 1", call, nodes_col);
+    if ((long long)nodes_row * (long long)nodes_col > FLUID_LATTICE_MAX_NODES)
+        return fail(FLUID_E_INVALID, "%s: %d x %d = %lld nodes, above FLUID_LATTICE_MAX_NODES = %d", call, nodes_row, nodes_col,
+                    (long long)nodes_row * (long long)nodes_col, FLUID_LATTICE_MAX_NODES);
+    if (step < 8 || step % 8 != 0) return fail(FLUID_E_INVALID, "%s: step = %d is not a positive multiple of 8", call, step);
+    const int M = c->members, MP = fluid::transform_padded(M), nodes = nodes_row * nodes_col;
+    bool any = false;
+    for (int node = 0; node < nodes; ++node)
+        for (int k = 0; k < M; ++k)
+            for (int m = 0; m < M; ++m) {
+                const float d = increments[((size_t)node * M + k) * M + m];
+                if (!std::isfinite(d))
+                    return fail(FLUID_E_INVALID, "%s: the increment of node (a = %d, b = %d), old member k = %d, new member m = %d is not finite",
+                                call, node / nodes_col, node % nodes_col, k, m);
+                any = any || d != 0.0f;
+            }
+    fluid::LatticeTables dev;
+    bool dense = true;
+    if (any) {                                                       // (no term anywhere: nothing is stored, nothing staged)
+        const size_t table_bytes = (size_t)nodes * M * MP * sizeof(double), bits_bytes = (size_t)nodes * M * sizeof(unsigned long long);
+        const size_t bytes = table_bytes + bits_bytes + (size_t)nodes * sizeof(unsigned long long);
+        TRY(ensure_lattice(c, call, bytes));
+        LatticeNodeTables& t = c->lattice;
+        if (t.in_use) HIP_TRY(hipEventSynchronize(t.copied));       // the call before may still be copying out of the twin
+        double* table = reinterpret_cast<double*>(t.host);
+        unsigned long long* bits = reinterpret_cast<unsigned long long*>(t.host + table_bytes);
+        unsigned long long* cols = bits + (size_t)nodes * M;
+        for (int node = 0; node < nodes; ++node) {
+            unsigned long long all = 0;
+            for (int k = 0; k < M; ++k) {
+                unsigned long long row = 0;
+                for (int m = 0; m < MP; ++m) {
+                    const float d = m < M ? increments[((size_t)node * M + k) * M + m] : 0.0f;
+                    table[((size_t)node * M + k) * MP + m] = (double)d;
+                    if (d != 0.0f) row |= 1ull << m;
+                    else if (m < M) dense = false;
+                }
+                bits[(size_t)node * M + k] = row;
+                all |= row;
+            }
+            cols[node] = all;
+        }
+        HIP_TRY(hipMemcpyAsync(t.dev, t.host, bytes, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipEventRecord(t.copied, c->stream));
+        t.in_use = true;
+        dev.table = reinterpret_cast<const double*>(t.dev);
+        dev.bits = reinterpret_cast<const unsigned long long*>(t.dev + table_bytes);
+        dev.cols = dev.bits + (size_t)nodes * M;
+    }
+    const fluid::Lattice lat = {nodes_row, nodes_col, row0, col0, step};
+    for (int k = 0; k < nfields; ++k) {
+        const int f = fields[k];
+        const float scale = c->st != fluid::STORAGE_F32 ? c->field[f].fscale : 1.0f;           // as pack_range sees the field
+        TRY(materialize(c, f, /*keep_scale=*/scale != 1.0f));
+        if (!any) continue;
+        fluid::launch_transform_members_lattice(c->stream, c->st, c->ptr(f), c->pitch, c->n, c->mb(), 1.0f / scale, scale, dev, dense, lat);
+        HIP_TRY(hipGetLastError());
+        wrote(c, f, kEverywhere);                                    // nothing owed ...
+        c->field[f].fscale = scale;                                  // ... and the scale it had: the launch stored at it
+    }
     return FLUID_OK;
 }
 

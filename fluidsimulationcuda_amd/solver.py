@@ -500,6 +500,22 @@ class FluidSolver:
         self.synchronize()
         return out, tuple(box)
 
+    # -- lattice updates: increments at the nodes of a coarse lattice, blended bilinearly to every cell
+    def transform_lattice(self, increments, origin, step, fields=("u", "v", "dens")):
+        """X' = X + sum_b phi_b o (X D_b) per cell of each listed field, every product on the OLD X, in place, one launch
+        per field whatever the node count and no wait: increments[a][b][k][m] is the weight of OLD member k in the
+        INCREMENT of new member m at node (a, b), shape (nodes_row, nodes_col, members, members); node (a, b) sits on cell
+        row origin[0] + a * step, column origin[1] + b * step (any ints), `step` a positive multiple of 8; phi is the
+        bilinear weight of the node at the cell, constant outside the lattice's hull (include/fluid_amd.h, "lattice
+        updates").  members <= capi.TRANSFORM_MAX_MEMBERS."""
+        d = np.ascontiguousarray(np.asarray(increments, np.float32))
+        if d.ndim != 4 or d.shape[2:] != (self.members, self.members):
+            raise ValueError("increments must have shape (nodes_row, nodes_col, %d, %d), got %s" % (self.members, self.members, d.shape))
+        row0, col0 = (int(v) for v in origin)
+        ids = [_fid(f) for f in fields]
+        capi.check(capi.lib().fluid_transform_members_lattice(self._h, (C.c_int * len(ids))(*ids), len(ids), _mf(d), d.shape[0], d.shape[1],
+                                                              row0, col0, int(step)))
+
     def set_jacobi_variant(self, variant):
         capi.check(capi.lib().fluid_set_jacobi_variant(self._h, variant))
 

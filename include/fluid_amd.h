@@ -622,6 +622,69 @@ int fluid_transform_members_local(fluid_ctx *ctx, const int *fields, int nfields
                                   const void *taper_dev, const int *box);
 int fluid_taper_gaspari_cohn(fluid_ctx *ctx, float col, float row, float c, void *out_dev, int *box);
 
+/* ---- lattice updates: increments given at the nodes of a coarse lattice, blended to every cell in one launch ----------
+ * M = fluid_members(ctx), W = N + 2.  A localised filter (LETKF) computes an increment matrix D_b at each of many analysis
+ * points, all from the SAME background ensemble, and wants
+ *     X' = X + sum over b of phi_b o (X D_b)
+ * with every product taken on the old X.  A sequence of fluid_transform_members_local calls cannot say that: the calls are
+ * in place, so where two tapers overlap the second multiplies what the first already changed, and it costs one launch per
+ * field per analysis point.  The remedy is weight interpolation (Yang et al. 2009): D at the nodes of a coarse lattice,
+ * interpolated bilinearly to every cell -- here in one launch per field.
+ *
+ * - fluid_transform_members_lattice: `increments` is host memory, nodes_row * nodes_col * M * M finite floats;
+ *   increments[((a*nodes_col + b)*M + k)*M + m] is the weight of OLD member k in the INCREMENT of new member m at node
+ *   (a, b): D = T - I per node, as in fluid_transform_members_local.  Node (a, b) sits on cell row row0 + a*step, column
+ *   col0 + b*step; row0 and col0 may be any int, negative or past the array.  `step` is a positive multiple of 8: any
+ *   8 x 8 patch of cells aligned to the lattice's origin then lies inside one lattice cell (the launch takes coarser
+ *   patches where step allows; the bits do not depend on it).  nodes_row, nodes_col >= 1, nodes_row * nodes_col <=
+ *   FLUID_LATTICE_MAX_NODES.  `fields`: nfields distinct field ids, host memory.  Every cell of the W x W array is covered,
+ *   ghost ring included; there is no box and no taper.
+ *   Definition -- per listed field, per cell (i, j), per new member m; pad columns are neither read nor written:
+ *    1. The field's lazy state is settled for all members first, and x_k is read exactly as rule 1 of
+ *       fluid_transform_members_local reads it: an fp16 field held at a pressure scale KEEPS it, values are read divided
+ *       back and stored times the scale by that call's rule 6, with the same +-inf beyond 65504 / scale.
+ *    2. Axis weights.  Along rows, with n = nodes_row, S = step, q = i - row0, in integer arithmetic:
+ *         n == 1 or q <= 0:   a = 0,      t1 = 0;
+ *         q >= (n-1)*S:       a = n - 2,  t1 = 1;
+ *         otherwise:          a = q / S,  t1 = (double)(q - a*S) / (double)S, one rounding;
+ *       t0 = 1.0 - t1, one rounding.  Columns are the same with nodes_col, col0, j, giving b, u0, u1.  Cells outside the
+ *       lattice's hull take the nearest edge's weights: constant extrapolation.
+ *    3. Corners, up to four, in row-major order of the absolute node index: (a, b), (a, b+1), (a+1, b), (a+1, b+1), with
+ *       weights phi = t0*u0, t0*u1, t1*u0, t1*u1, each ONE double multiplication rounded once.  A corner past the lattice
+ *       (n == 1 on that axis) does not exist.
+ *    4. Node sums.  t_c = sum over k of (double)x_k * (double)d_c[k][m], over the k in increasing order with d_c[k][m] != 0,
+ *       started from its first term; every product is exact in double, as in fluid_transform_members.  A zero of either
+ *       sign takes no part.  A corner whose column m has no term has no t_c.
+ *    5. A corner takes part when it exists, phi_c != 0 and t_c exists.  A corner with phi_c == 0 is not evaluated into
+ *       the result, whatever it holds, inf and NaN included.  So a cell on a lattice line depends on that line's nodes
+ *       only, and a cell on a node gets exactly fluid_transform_members_local's result for that node's D.
+ *    6. Blend.  s = phi_c * t_c for the first corner that takes part; for each further one s = s + phi_c * t_c; product and
+ *       sum are each rounded once and NOT contracted into one fused operation.
+ *    7. y_d = (double)x_m + s, rounded once; y = (float)y_d; the store is narrow(y).  If no corner takes part for (cell,
+ *       m), that cell of member m is not stored and keeps every bit.
+ *    8. All M old values of a cell are read before any new value of that cell is stored: the call is in place and means
+ *       what an out-of-place one would.
+ *    9. A NaN result is a NaN; its sign and payload are not specified.
+ *   The order is part of the contract: the same bits for every launch shape; no atomics, no matrix instructions.
+ *   One kernel launch per listed field whatever M and the node count are, enqueued on the context's stream, no wait for
+ *   the fields; increments without a single term anywhere launch nothing, and the fields are still settled.  The node
+ *   tables -- the doubles the kernel reads and a word of non-zero bits per node and old member -- are library-owned
+ *   device memory outside the arena with a pinned staging twin (fluid_arena_bytes_ensemble is unchanged), allocated or
+ *   grown by the first call that needs the room and freed by fluid_destroy; a failed allocation is FLUID_E_NOMEM and
+ *   leaves the context usable and nothing changed.  There is ONE table buffer: the device copy is ordered behind earlier
+ *   launches by the stream, but a call may wait on an event until the lattice call before it has copied its tables out
+ *   of the staging twin, and a call that grows the buffer waits for the stream.  `increments` belongs to the caller again
+ *   when the call returns.  M in [1, FLUID_TRANSFORM_MAX_MEMBERS].
+ * Refusals, all FLUID_E_INVALID with a message that names the call, found before anything is launched or any state
+ * changes, null pointers before the context is looked at: a null `fields` or `increments`, a null context; nfields outside
+ * [1, 12]; a bad field id; a field listed twice; M > FLUID_TRANSFORM_MAX_MEMBERS (the message gives both numbers); row
+ * slabs; nodes_row or nodes_col below 1; more than FLUID_LATTICE_MAX_NODES nodes (the message gives both numbers); a step
+ * below 8 or not a multiple of 8; a non-finite increment (the message names a, b, k and m).
+ * The launches belong to none of the fluid_timing categories. */
+#define FLUID_LATTICE_MAX_NODES 4096
+int fluid_transform_members_lattice(fluid_ctx *ctx, const int *fields, int nfields, const float *increments, int nodes_row,
+                                    int nodes_col, int row0, int col0, int step);
+
 int fluid_set_jacobi_variant(fluid_ctx *ctx, int variant);
 /* How FLUID_JACOBI_TB divides by `beta` in a solve with these coefficients (diagnostic; runs the on-device proof
  * if this beta has not been seen): 0 true division, 2 double-precision reciprocal, 3 two-term float reciprocal
