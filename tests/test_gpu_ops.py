@@ -189,14 +189,16 @@ def test_reductions(F, oracle):
         s.upload(u=u, v=v)
         want = max(np.abs(u[1:-1, 1:-1]).max(), np.abs(v[1:-1, 1:-1]).max())
         assert s.absmax_velocity("u", "v") == want
-        # residual is a diagnostic: compare against a float64 evaluation loosely,
-        # and check it falls as the solve proceeds and leaves the fields alone
+        # residual: the kernel's float expression, bit for bit (residual32; the ensemble tests hold the same kernel to
+        # it), next to a float64 evaluation; it falls as the solve proceeds and leaves the fields alone
+        from test_gpu_lazy_state import residual32
         x, x0 = rnd(rng, n), rnd(rng, n)
         s.upload(u=x, v=x0)
         r0 = s.residual("u", "v", 1.0, 4.0)
         nb = x[1:-1, :-2] + x[1:-1, 2:] + x[:-2, 1:-1] + x[2:, 1:-1]
         ref = np.abs(4.0 * x[1:-1, 1:-1].astype(np.float64) - nb - x0[1:-1, 1:-1]).max()
         assert abs(r0 - ref) <= 1e-5 * ref
+        assert np.float32(r0).view(np.uint32) == residual32(x, x0, 1.0, 4.0).view(np.uint32), (r0, residual32(x, x0, 1.0, 4.0))
         assert_bit_equal(s.download("u"), x, "residual must not alter x")
         s.diffuse(0, "u", "v", 1.0, 4.0, 40)
         assert s.residual("u", "v", 1.0, 4.0) < r0
