@@ -139,6 +139,8 @@ SIGNATURES = {
     "fluid_transform_members_local": [_ctx, C.POINTER(_i), _i, _MF, C.c_void_p, C.POINTER(_i)],
     "fluid_transform_members_lattice": [_ctx, C.POINTER(_i), _i, _MF, _i, _i, _i, _i, _i],
     "fluid_taper_gaspari_cohn": [_ctx, _f, _f, _f, C.c_void_p, C.POINTER(_i)],
+    "fluid_observation_gram_lattice": [_ctx, _i, _i, _MF, _MF, _i, _i, _i, _i, _i, _f, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                       C.POINTER(C.c_double), C.POINTER(_i)],
     "fluid_set_jacobi_variant": [_ctx, _i],
     "fluid_division_mode": [_ctx, _f, _f, C.POINTER(_i)],
     "fluid_autotune_pending": [_ctx, C.POINTER(_i)],
@@ -167,6 +169,7 @@ COARSE_FACTORS = (1, 2, 4, 8, 16, 32, 64)
 TRANSFORM_MAX_MEMBERS = 64
 OBSERVE_MAX_POINTS = 1 << 20
 LATTICE_MAX_NODES = 4096
+LATTICE_GRAM_MAX_ENTRIES = 1 << 24
 
 _lib = None
 

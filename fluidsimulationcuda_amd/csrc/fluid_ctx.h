@@ -161,6 +161,27 @@ struct Observation {
     float* sigma() const { return reinterpret_cast<float*>(table + (size_t)points * 28); }
 };
 
+// Lattice observations (fluid_observation_gram_lattice): the point lists of the nodes, the operands of every point and the
+// results of every node, library-owned and outside the arena (fluid_solver.hip: ensure_lattice_gram), each allocated or grown
+// by the first call that needs the room and freed in fluid_destroy.  `coords` is the host copy of the network's positions
+// (fluid_set_observation_points keeps it: col, row per point) the lists are built from.  The lists are ONE buffer with a
+// pinned twin: [nodes + 1] ints, the start of every node's entries, then the entries, {point index, the bits of the float
+// weight}, a node's in increasing point index.  They are kept: `valid` says that they are the lists of the network in place
+// and of the lattice arguments and c below, and then a call builds and uploads nothing.
+struct LatticeGram {
+    std::vector<float> coords;            // [points] {col, row}
+    char *d_lists = nullptr, *h_lists = nullptr;
+    size_t list_bytes = 0;                // the room of each
+    double* d_operands = nullptr;         // [points][MP + 2] doubles: a_k (padding members 0), then d, then 0
+    size_t operand_bytes = 0;
+    double *d_out = nullptr, *h_out = nullptr;   // [nodes] partial-shaped results (fluid::observation_gram_entries doubles) and their twin
+    size_t out_bytes = 0;
+    bool valid = false;
+    int nodes_row = 0, nodes_col = 0, row0 = 0, col0 = 0, step = 0;
+    float c = 0.0f;
+    long long pairs = 0;                  // entries of the lists
+};
+
 struct fluid_ctx {
     int n = 0, w = 0, pitch = 0;
     size_t field_floats = 0;
@@ -197,6 +218,7 @@ struct fluid_ctx {
     TransformTables xform;                // weight tables of fluid_transform_members / fluid_select_members
     LatticeNodeTables lattice;            // node tables of fluid_transform_members_lattice
     Observation observe;                  // the observation network and the scratch of fluid_observation_gram
+    LatticeGram lgram;                    // point lists, operands and results of fluid_observation_gram_lattice
     unsigned int* tiles = nullptr;        // 3 x members x tile_rows x tile_pitch words: |x0| minima per tile for division mode 3
     unsigned int* h_scalar = nullptr;     // pinned host mirror
     hipEvent_t scalar_ready = nullptr;    // recorded behind the scalar's device-to-host copy

@@ -283,4 +283,21 @@ __host__ __device__ inline double taper_value(double r)
 // out[i * (n + 2) + j] = (float)taper_value(taper_radius(j - col, i - row, c)) for every cell of the (n + 2)^2 array: one launch
 void launch_taper_gaspari_cohn(hipStream_t s, float* out, int n, float col, float row, float c);
 
+// Lattice observations (include/fluid_amd.h "lattice observations").  The point lists of the nodes in device memory, built
+// and bounds-checked on the host: start[node] .. start[node + 1] index node's entries in `entry`, each {point index < pts.count,
+// the bits of the float weight w = (float)taper_value(..) != 0}, a node's in increasing point index.
+struct LatticeLists {
+    const int* start = nullptr;           // [nodes + 1]
+    const int2* entry = nullptr;
+    int nodes = 0;
+};
+// fluid_observation_gram_lattice: out[node * observation_gram_entries(mb.count) + ..] = the node's matrix, rhs and dd in the
+// layout launch_observation_gram leaves one result in, the sums of (w * a_k) * a_m, (w * a_k) * d, (w * d) * d over the
+// node's entries; a node without entries is not written.  Within a diagonal tile the entries with k > m are not the
+// header's (the weight rides on the row operand): the caller mirrors k <= m.  `operands`: pts.count * (gram_padded(mb.count)
+// + 2) doubles of scratch.  Two launches whatever the counts: every point is observed once, then one block per node.
+void launch_observation_gram_lattice(hipStream_t s, int st, const void* x, int pitch, Members mb, float inv, const ObservationPoints& pts,
+                                     bool centre, const float* obs, const float* sigma, double* operands, const LatticeLists& lists,
+                                     double* out);
+
 }  // namespace fluid

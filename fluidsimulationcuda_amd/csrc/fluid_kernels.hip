@@ -2056,6 +2056,160 @@ __global__ __launch_bounds__(256) void k_fold_observation_gram(const double* __r
     }
 }
 
+// ---- lattice observations (include/fluid_amd.h "lattice observations") ----------------------------------------------------
+// fluid_observation_gram_lattice, first launch: the operands of every point of the network, observed ONCE whatever the
+// number of nodes.  The first half of k_observation_gram, chunk by chunk: a block takes the CH = 64 points of its chunk,
+// wave w gathers and interpolates members w, w + 4, .., one lane per point then does the operand chain of the header (mean
+// chain in member order and its subtraction with CENTRE, the multiplication by 1 / sigma, the innovation with OBS) -- the
+// same operations in the same order, so a_k and d have k_observation_gram's bits.  The rows go to out[point][R], R = MP + 2
+// doubles: a_k for the MP padded members (padding members 0), then d (0 without OBS), then 0 -- the layout k_lattice_gram
+// stages, written with consecutive lanes on consecutive doubles.
+template <typename S, int MP, bool CENTRE, bool OBS>
+__global__ __launch_bounds__(256) void k_observation_operands(const S* __restrict__ x, int pitch, size_t ms, int members, float inv,
+                                                              const unsigned long long* __restrict__ tap, const float4* __restrict__ weight,
+                                                              const float* __restrict__ obs, const float* __restrict__ sigma, int points,
+                                                              double* __restrict__ out)
+{
+    constexpr int CH = kObsChunk, R = MP + 2, L = CH * MP / 256;
+    __shared__ __attribute__((aligned(16))) double stage[CH * R];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int first = (int)blockIdx.x * CH, nc = min(CH, points - first);
+    {
+        const int pt = first + lane;
+        const bool live = pt < points;
+        const unsigned long long o = live ? tap[pt] : 0ull;
+        const float4 w = live ? weight[pt] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+#pragma unroll
+        for (int r = 0; r < L; ++r) {
+            const int k = wave + 4 * r;
+            float a = 0.0f;
+            if (live && k < members) a = observe_point<S>(x + (size_t)k * ms, pitch, o, w, inv);
+            stage[lane * R + k] = (double)a;
+        }
+    }
+    __syncthreads();
+    if (t < nc) {
+        const int pt = first + t;
+        double* p = stage + t * R;
+        double mu = 0.0;
+        if constexpr (CENTRE) {
+            double s = p[0];
+            for (int m = 1; m < members; ++m) s = s + p[m];
+            mu = s / (double)members;
+        }
+        const double sg = sigma ? (double)sigma[pt] : 1.0;
+        if (CENTRE || sigma)
+            for (int m = 0; m < members; ++m) {
+                double v = p[m];
+                if constexpr (CENTRE) v = v - mu;
+                if (sigma) v = v * sg;
+                p[m] = v;
+            }
+        double dv = 0.0;
+        if constexpr (OBS) {
+            dv = (double)obs[pt];
+            if constexpr (CENTRE) dv = dv - mu;
+            if (sigma) dv = dv * sg;
+        }
+        p[MP] = dv;
+        p[MP + 1] = 0.0;
+    }
+    __syncthreads();
+    double* rows = out + (size_t)first * R;
+    for (int v = t; v < nc * R; v += 256) rows[v] = stage[v];
+}
+
+// fluid_observation_gram_lattice, second launch: the second half of k_observation_gram, one block per node, the node index
+// in the grid.  start[node] .. start[node + 1] are the node's entries {point index, bits of the float weight w}, in
+// increasing point index, built and bounds-checked on the host; a block walks them in chunks of CH = 64: the entries go to
+// LDS, then the points' rows of `operands` (k_observation_operands: R = MP + 2 doubles, read with consecutive lanes on
+// consecutive doubles) are gathered into the staging layout of k_observation_gram.  Lane (ta, tb) of the 8 x 8 lane grid owns
+// a T x T tile: per point it rounds w * a_k once for its T row operands and issues T * T v_fma_f64 with the unweighted
+// column operands, (w * a_k) * a_m as the header defines it -- so within a diagonal tile only k <= m is the header's entry,
+// and the host mirrors element by element.  The four waves take the points wave, wave + 4, .. of a chunk and are added in
+// wave order at the end.  The innovation sums ride in lanes below the diagonal, whose tiles are dropped, with d for the
+// COLUMN operand (the row operand is the one that carries w):
+//   lane (ta, 0), ta = 1 .. 7: b[0] := d, so acc[i][0] = sum (w * a_k) * d, k = T * ta + i: rhs of tile row ta;
+//   lane (2, 1):               row operands of tile row 0 and b[0] := d:                    rhs of tile row 0;
+//   lane (3, 1):               a[0] := d, b[0] := d, so acc[0][0] = sum (w * d) * d.
+// A node's result is a partial of k_observation_gram, E = MP * MP + MP + 1 doubles: the matrix (tiles with ta <= tb), rhs[MP],
+// dd; a node without entries stores nothing (the host writes its zeros).  Plain stores, no atomics, no matrix instructions;
+// the order of every addition is fixed by the node's list.
+template <int MP, bool OBS>
+__global__ __launch_bounds__(256) void k_lattice_gram(const double* __restrict__ operands, const int* __restrict__ start,
+                                                      const int2* __restrict__ entry, double* __restrict__ out)
+{
+    constexpr int T = MP / 8, CH = kObsChunk, R = MP + 2, E = MP * MP + MP + 1;
+    static_assert(MP * MP <= CH * R, "the node's matrix is folded in the staging memory");
+    __shared__ __attribute__((aligned(16))) double stage[CH * R];
+    __shared__ int2 ent[CH];
+    const int first = start[blockIdx.x], last = start[blockIdx.x + 1];
+    if (first >= last) return;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int l5 = lane & 31, q = l5 >> 2;
+    const int ta = 4 * (lane >> 5) + (q >> 1), tb = 4 * ((0x96 >> q) & 1) + (l5 & 3);
+    const bool rhs0 = OBS && ta == 2 && tb == 1, dd_lane = OBS && ta == 3 && tb == 1;
+    const bool d_for_b = OBS && ((tb == 0 && ta >= 1) || rhs0 || dd_lane);
+    const int arow = rhs0 ? 0 : ta;
+    double acc[T][T];
+#pragma unroll
+    for (int i = 0; i < T; ++i)
+#pragma unroll
+        for (int j = 0; j < T; ++j) acc[i][j] = -0.0;
+
+    for (int base = first; base < last; base += CH) {
+        const int nc = min(CH, last - base);
+        if (t < nc) ent[t] = entry[base + t];
+        __syncthreads();
+        for (int v = t; v < nc * R; v += 256) {
+            const int pt = v / R;
+            stage[v] = operands[(size_t)ent[pt].x * R + (v - pt * R)];
+        }
+        __syncthreads();
+        for (int c = wave; c < nc; c += 4) {
+            const double w = (double)__int_as_float(ent[c].y);
+            double a[T], b[T];
+            gram_operands<T>(stage + c * R + arow * T, a);
+            gram_operands<T>(stage + c * R + tb * T, b);
+            if constexpr (OBS) {
+                const double dv = stage[c * R + MP];
+                if (dd_lane) a[0] = dv;
+                if (d_for_b) b[0] = dv;
+            }
+#pragma unroll
+            for (int i = 0; i < T; ++i) a[i] = w * a[i];
+#pragma unroll
+            for (int i = 0; i < T; ++i)
+#pragma unroll
+                for (int j = 0; j < T; ++j) acc[i][j] = __builtin_fma(a[i], b[j], acc[i][j]);
+        }
+        __syncthreads();
+    }
+
+    // ((wave 0 + wave 1) + wave 2) + wave 3, every lane its own entries; the last wave stores the node's result
+    double* res = out + (size_t)blockIdx.x * E;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        if (wave == w) {
+#pragma unroll
+            for (int i = 0; i < T; ++i)
+#pragma unroll
+                for (int j = 0; j < T; ++j) {
+                    const int at = (ta * T + i) * MP + tb * T + j;
+                    if (w > 0) acc[i][j] = stage[at] + acc[i][j];
+                    if (w < 3) stage[at] = acc[i][j];
+                    else if (ta <= tb) res[at] = acc[i][j];
+                    else if constexpr (OBS) {
+                        if (tb == 0 && j == 0) res[MP * MP + ta * T + i] = acc[i][j];
+                        if (rhs0 && j == 0) res[MP * MP + i] = acc[i][j];
+                        if (dd_lane && i == 0 && j == 0) res[MP * MP + MP] = acc[i][j];
+                    }
+                }
+        }
+        if (w < 3) __syncthreads();
+    }
+}
+
 // Across the members, per cell (ghost cells included): mean and population variance as float fields in the layout of a
 // field, by the two-pass definition of include/fluid_amd.h -- all in double, member order, the first member's value (not
 // 0.0) as the start of both chains.  One lane per VW = 4 (fp16: 8) consecutive columns of a row, vector v of a row covering
@@ -3002,6 +3156,35 @@ void launch_observation_gram(hipStream_t s, int st, const void* x, int pitch, Me
 #undef FLUID_OBS_GRAM_LAUNCH
     hipLaunchKernelGGL(k_fold_observation_gram, dim3(cdiv((unsigned)observation_gram_entries(mb.count), 16)), dim3(256), 0, s, partials,
                        blocks, mp, mp / 8, obs ? 1 : 0, out);
+}
+
+void launch_observation_gram_lattice(hipStream_t s, int st, const void* x, int pitch, Members mb, float inv, const ObservationPoints& pts,
+                                     bool centre, const float* obs, const float* sigma, double* operands, const LatticeLists& lists,
+                                     double* out)
+{
+    const int mp = gram_padded(mb.count);
+    const unsigned chunks = cdiv((unsigned)pts.count, kObsChunk);
+#define FLUID_OBS_OPERANDS_LAUNCH(MP, CENTRE, OBS)                                                                                         \
+    FLUID_BY_STORAGE(st, hipLaunchKernelGGL((k_observation_operands<S, MP, CENTRE, OBS>), dim3(chunks), dim3(256), 0, s, (const S*)x,      \
+                                            pitch, mb.stride, mb.count, inv, pts.tap, (const float4*)pts.weight, obs, sigma, pts.count,    \
+                                            operands))
+#define FLUID_LATTICE_GRAM_CASE(MP)                                                                                                        \
+    case MP:                                                                                                                               \
+        if (centre && obs) FLUID_OBS_OPERANDS_LAUNCH(MP, true, true);                                                                      \
+        else if (centre) FLUID_OBS_OPERANDS_LAUNCH(MP, true, false);                                                                       \
+        else if (obs) FLUID_OBS_OPERANDS_LAUNCH(MP, false, true);                                                                          \
+        else FLUID_OBS_OPERANDS_LAUNCH(MP, false, false);                                                                                  \
+        if (obs) hipLaunchKernelGGL((k_lattice_gram<MP, true>), dim3(lists.nodes), dim3(256), 0, s, operands, lists.start, lists.entry, out);  \
+        else hipLaunchKernelGGL((k_lattice_gram<MP, false>), dim3(lists.nodes), dim3(256), 0, s, operands, lists.start, lists.entry, out);     \
+        break
+    switch (mp) {
+        FLUID_LATTICE_GRAM_CASE(8);
+        FLUID_LATTICE_GRAM_CASE(16);
+        FLUID_LATTICE_GRAM_CASE(32);
+        FLUID_LATTICE_GRAM_CASE(64);
+    }
+#undef FLUID_LATTICE_GRAM_CASE
+#undef FLUID_OBS_OPERANDS_LAUNCH
 }
 
 void launch_ensemble_stats(hipStream_t s, int st, const void* x, int pitch, int n, Members mb, float* mean, float* var)

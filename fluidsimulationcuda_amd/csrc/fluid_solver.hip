@@ -1866,6 +1866,11 @@ int fluid_destroy(fluid_ctx* c)
     if (c->observe.d_partials) (void)hipFree(c->observe.d_partials);
     if (c->observe.d_out) (void)hipFree(c->observe.d_out);
     if (c->observe.host) (void)hipHostFree(c->observe.host);
+    if (c->lgram.d_lists) (void)hipFree(c->lgram.d_lists);
+    if (c->lgram.h_lists) (void)hipHostFree(c->lgram.h_lists);
+    if (c->lgram.d_operands) (void)hipFree(c->lgram.d_operands);
+    if (c->lgram.d_out) (void)hipFree(c->lgram.d_out);
+    if (c->lgram.h_out) (void)hipHostFree(c->lgram.h_out);
     for (hipEvent_t ev : c->xform.copied)
         if (ev) (void)hipEventDestroy(ev);
     if (c->xform.dev) (void)hipFree(c->xform.dev);
@@ -3242,6 +3247,13 @@ int fluid_set_observation_points(fluid_ctx* c, const float* col, const float* ro
     if (o.table) (void)hipFree(o.table);
     o.table = table;
     o.points = npoints;
+    LatticeGram& g = c->lgram;                                          // the positions fluid_observation_gram_lattice builds its lists from
+    g.valid = false;
+    g.coords.resize((size_t)npoints * 2);
+    for (int p = 0; p < npoints; ++p) {
+        g.coords[2 * (size_t)p] = col[p];
+        g.coords[2 * (size_t)p + 1] = row[p];
+    }
     return FLUID_OK;
 }
 
@@ -3384,6 +3396,159 @@ int fluid_observation_gram(fluid_ctx* c, int field, int centre, const float* obs
     if (rhs)
         for (int k = 0; k < M; ++k) rhs[k] = o.host[(size_t)mp * mp + k];
     if (dd) *dd = o.host[(size_t)mp * mp + mp];
+    return FLUID_OK;
+}
+
+// ---- lattice observations: fluid_observation_gram_lattice ------------------------------------------------------------------
+// (include/fluid_amd.h "lattice observations".)  Which points a node sees is found here, on the host, from the copy of the
+// network's positions fluid_set_observation_points keeps: per point only the nodes whose row and column lie within 2c of it
+// (from the lattice geometry, one node of margin on each side) are tried, and the weight is the taper kernel's own function.
+// `fn(node, point, w)` is called for every pair with w != 0, points in increasing order.
+extern "C++" {
+template <typename F>
+static void lattice_pairs(const fluid_ctx* c, int nodes_row, int nodes_col, int row0, int col0, int step, float hw, F fn)
+{
+    const double reach = 2.0 * (double)hw, hwd = (double)hw, s = (double)step;
+    const size_t P = (size_t)c->observe.points;
+    auto range = [&](double x, int origin, int count, int* lo, int* hi) {    // nodes origin + i * step with |x - node| <= reach, and one more
+        const double a = std::floor((x - reach - (double)origin) / s) - 1.0, b = std::ceil((x + reach - (double)origin) / s) + 1.0;
+        *lo = a <= 0.0 ? 0 : a >= (double)count ? count : (int)a;
+        *hi = b < 0.0 ? -1 : b >= (double)(count - 1) ? count - 1 : (int)b;
+    };
+    for (size_t p = 0; p < P; ++p) {
+        const double col = (double)c->lgram.coords[2 * p], row = (double)c->lgram.coords[2 * p + 1];
+        int a_lo, a_hi, b_lo, b_hi;
+        range(row, row0, nodes_row, &a_lo, &a_hi);
+        range(col, col0, nodes_col, &b_lo, &b_hi);
+        for (int a = a_lo; a <= a_hi; ++a) {
+            const double dy = row - (double)((long long)row0 + (long long)a * step);
+            for (int b = b_lo; b <= b_hi; ++b) {
+                const double dx = col - (double)((long long)col0 + (long long)b * step);
+                const float w = (float)fluid::taper_value(fluid::taper_radius(dx, dy, hwd));
+                if (w != 0.0f) fn(a * nodes_col + b, (int)p, w);
+            }
+        }
+    }
+}
+}  // extern "C++"
+
+// one of the call's buffers, grown to `bytes`: the new ones are allocated before the old ones are freed, so a failure leaves
+// everything as it was (every earlier call ended in a wait: nothing reads the old ones)
+static int grow_lattice_gram(const char* call, const char* what, char** dev, char** host, size_t* room, size_t bytes)
+{
+    if (*room >= bytes) return FLUID_OK;
+    char *d = nullptr, *h = nullptr;
+    hipError_t e = hipMalloc((void**)&d, bytes);
+    if (e == hipSuccess && host) e = hipHostMalloc((void**)&h, bytes, hipHostMallocDefault);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        if (d) (void)hipFree(d);
+        return fail(e == hipErrorOutOfMemory ? FLUID_E_NOMEM : FLUID_E_HIP, "%s: allocating %zu bytes of %s: %s", call, bytes, what,
+                    hipGetErrorString(e));
+    }
+    if (*dev) (void)hipFree(*dev);
+    *dev = d;
+    if (host) {
+        if (*host) (void)hipHostFree(*host);
+        *host = h;
+    }
+    *room = bytes;
+    return FLUID_OK;
+}
+
+int fluid_observation_gram_lattice(fluid_ctx* c, int field, int centre, const float* obs, const float* inv_sigma, int nodes_row, int nodes_col,
+                                   int row0, int col0, int step, float hw, double* gram, double* rhs, double* dd, int* counts)
+{
+    const char* call = "fluid_observation_gram_lattice";
+    if (!gram) return fail(FLUID_E_INVALID, "%s: null array `gram`", call);
+    if (!obs && (rhs || dd)) return fail(FLUID_E_INVALID, "%s: `%s` is given but `obs` is null", call, rhs ? "rhs" : "dd");
+    if (!c) return fail(FLUID_E_INVALID, "%s: null context", call);
+    TRY(check_observe(c, call, field));
+    if (c->members > FLUID_TRANSFORM_MAX_MEMBERS)
+        return fail(FLUID_E_INVALID, "%s: this context has %d members, above FLUID_TRANSFORM_MAX_MEMBERS = %d", call, c->members,
+                    FLUID_TRANSFORM_MAX_MEMBERS);
+    if (nodes_row < 1) return fail(FLUID_E_INVALID, "%s: nodes_row = %d is below 1", call, nodes_row);
+    if (nodes_col < 1) return fail(FLUID_E_INVALID, "%s: nodes_col = %d is below 1", call, nodes_col);
+    if ((long long)nodes_row * (long long)nodes_col > FLUID_LATTICE_MAX_NODES)
+        return fail(FLUID_E_INVALID, "%s: %d x %d = %lld nodes, above FLUID_LATTICE_MAX_NODES = %d", call, nodes_row, nodes_col,
+                    (long long)nodes_row * (long long)nodes_col, FLUID_LATTICE_MAX_NODES);
+    if (step < 8 || step % 8 != 0) return fail(FLUID_E_INVALID, "%s: step = %d is not a positive multiple of 8", call, step);
+    if (!std::isfinite(hw) || !(hw > 0.0f)) return fail(FLUID_E_INVALID, "%s: c = %g is not finite or not above 0", call, (double)hw);
+    Observation& o = c->observe;
+    LatticeGram& g = c->lgram;
+    const size_t P = (size_t)o.points, B = (size_t)nodes_row * (size_t)nodes_col;
+    if (inv_sigma)
+        for (size_t p = 0; p < P; ++p)
+            if (!std::isfinite(inv_sigma[p])) return fail(FLUID_E_INVALID, "%s: inv_sigma[%zu] (point %zu) is not finite", call, p, p);
+
+    // the lists of the call before serve when the network, the lattice and c are the same
+    const bool cached = g.valid && g.nodes_row == nodes_row && g.nodes_col == nodes_col && g.row0 == row0 && g.col0 == col0 &&
+                        g.step == step && g.c == hw;
+    std::vector<int> start;                                              // start[node + 1]: the entries of the nodes up to and with `node`
+    long long pairs = g.pairs;
+    if (!cached) {
+        start.assign(B + 1, 0);
+        pairs = 0;
+        lattice_pairs(c, nodes_row, nodes_col, row0, col0, step, hw, [&](int node, int, float) {
+            ++start[(size_t)node + 1];
+            ++pairs;
+        });
+        if (pairs > (long long)FLUID_LATTICE_GRAM_MAX_ENTRIES)
+            return fail(FLUID_E_INVALID, "%s: the nodes see %lld (point, node) pairs, above FLUID_LATTICE_GRAM_MAX_ENTRIES = %d", call, pairs,
+                        FLUID_LATTICE_GRAM_MAX_ENTRIES);
+        for (size_t b = 0; b < B; ++b) start[b + 1] += start[b];
+    }
+    const int M = c->members, mp = fluid::gram_padded(M);
+    const size_t E = fluid::observation_gram_entries(M), start_bytes = ((B + 1) * sizeof(int) + 7) & ~(size_t)7;
+    const size_t list_bytes = start_bytes + (size_t)pairs * sizeof(int2);
+    if (g.list_bytes < list_bytes) g.valid = false;                      // (not cached, then: new lists are about to replace the old)
+    TRY(grow_lattice_gram(call, "point lists", &g.d_lists, &g.h_lists, &g.list_bytes, list_bytes));
+    TRY(grow_lattice_gram(call, "point operands", reinterpret_cast<char**>(&g.d_operands), nullptr, &g.operand_bytes,
+                          P * (size_t)(mp + 2) * sizeof(double)));
+    TRY(grow_lattice_gram(call, "node results", reinterpret_cast<char**>(&g.d_out), reinterpret_cast<char**>(&g.h_out), &g.out_bytes,
+                          B * E * sizeof(double)));
+    int* h_start = reinterpret_cast<int*>(g.h_lists);
+    int2* h_entry = reinterpret_cast<int2*>(g.h_lists + start_bytes);
+    if (!cached) {
+        g.valid = false;
+        std::vector<int> at(start.begin(), start.end() - 1);             // where the next entry of a node goes
+        bool inside = true;
+        lattice_pairs(c, nodes_row, nodes_col, row0, col0, step, hw, [&](int node, int p, float w) {
+            const int slot = at[(size_t)node]++;
+            if (slot >= start[(size_t)node + 1] || p < 0 || (size_t)p >= P) { inside = false; return; }
+            unsigned bits;
+            std::memcpy(&bits, &w, sizeof bits);
+            h_entry[slot] = make_int2(p, (int)bits);
+        });
+        for (size_t b = 0; b < B; ++b) inside = inside && at[b] == start[b + 1];
+        if (!inside) return fail(FLUID_E_INVALID, "%s: the point lists do not match their count (internal error)", call);
+        std::memcpy(h_start, start.data(), (B + 1) * sizeof(int));
+        HIP_TRY(hipMemcpyAsync(g.d_lists, g.h_lists, list_bytes, hipMemcpyHostToDevice, c->stream));
+        g.nodes_row = nodes_row; g.nodes_col = nodes_col; g.row0 = row0; g.col0 = col0; g.step = step; g.c = hw;
+        g.pairs = pairs;
+        g.valid = true;
+    }
+    if (obs) HIP_TRY(hipMemcpyAsync(o.obs(), obs, P * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (inv_sigma) HIP_TRY(hipMemcpyAsync(o.sigma(), inv_sigma, P * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    float inv = 1.0f;
+    TRY(settle_for_observing(c, field, &inv));
+    const fluid::LatticeLists lists = {reinterpret_cast<const int*>(g.d_lists), reinterpret_cast<const int2*>(g.d_lists + start_bytes), (int)B};
+    fluid::launch_observation_gram_lattice(c->stream, c->st, c->ptr(field), c->pitch, c->mb(), inv, observation_points(c), centre != 0,
+                                           obs ? o.obs() : nullptr, inv_sigma ? o.sigma() : nullptr, g.d_operands, lists, g.d_out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(g.h_out, g.d_out, B * E * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (size_t b = 0; b < B; ++b) {
+        const int count = h_start[b + 1] - h_start[b];
+        const double* r = g.h_out + b * E;
+        double* gm = gram + b * (size_t)M * M;
+        if (counts) counts[b] = count;
+        for (int k = 0; k < M; ++k)                // k <= m was computed (an empty node: nothing was); the rest is its mirror
+            for (int m = k; m < M; ++m) gm[(size_t)k * M + m] = gm[(size_t)m * M + k] = count ? r[(size_t)k * mp + m] : 0.0;
+        if (rhs)
+            for (int k = 0; k < M; ++k) rhs[b * M + k] = count ? r[(size_t)mp * mp + k] : 0.0;
+        if (dd) dd[b] = count ? r[(size_t)mp * mp + mp] : 0.0;
+    }
     return FLUID_OK;
 }
 

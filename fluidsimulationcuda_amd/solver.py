@@ -516,6 +516,38 @@ class FluidSolver:
         capi.check(capi.lib().fluid_transform_members_lattice(self._h, (C.c_int * len(ids))(*ids), len(ids), _mf(d), d.shape[0], d.shape[1],
                                                               row0, col0, int(step)))
 
+    # -- lattice observations: the localised Gram matrix of every node of a lattice, in one call
+    def observation_gram_lattice(self, field, shape, origin, step, c, obs=None, inv_sigma=None, centre=True):
+        """observation_gram per node of a lattice, every point weighted by the Gaspari-Cohn taper of half-width c about the
+        node: C[a][b][k][m] = sum over the points of (w a_k) a_m.  `shape` = (nodes_row, nodes_col), `origin`, `step`: the
+        lattice of transform_lattice, so result [a][b] lines up with increments[a][b].  Returns (C, counts), or with `obs`
+        (C, rhs, dd, counts): float64 arrays of shape (nr, nc, M, M), (nr, nc, M), (nr, nc) and the int32 number of points
+        each node sees, (nr, nc); a node that sees none has zeros.  Every point is observed once, two launches and one wait
+        whatever the node count; the same bits on every call (include/fluid_amd.h, "lattice observations")."""
+        points = self.observation_points()
+
+        def per_point(a, name):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(np.asarray(a, np.float32).ravel())
+            if a.size != points:
+                raise ValueError("%s must hold one value per point (%d), got %d" % (name, points, a.size))
+            return a
+
+        y, s = per_point(obs, "obs"), per_point(inv_sigma, "inv_sigma")
+        nr, nc = (int(v) for v in shape)
+        row0, col0 = (int(v) for v in origin)
+        m, dp = self.members, C.POINTER(C.c_double)
+        room = (max(nr, 0), max(nc, 0))                  # (a refused shape still needs arrays to hand over)
+        g = np.empty(room + (m, m), np.float64)
+        rhs, dd = np.empty(room + (m,), np.float64), np.empty(room, np.float64)
+        counts = np.empty(room, np.int32)
+        capi.check(capi.lib().fluid_observation_gram_lattice(
+            self._h, _fid(field), 1 if centre else 0, None if y is None else _mf(y), None if s is None else _mf(s), nr, nc, row0, col0,
+            int(step), float(c), g.ctypes.data_as(dp), None if y is None else rhs.ctypes.data_as(dp),
+            None if y is None else dd.ctypes.data_as(dp), counts.ctypes.data_as(C.POINTER(C.c_int))))
+        return (g, counts) if y is None else (g, rhs, dd, counts)
+
     def set_jacobi_variant(self, variant):
         capi.check(capi.lib().fluid_set_jacobi_variant(self._h, variant))
 

@@ -685,6 +685,63 @@ int fluid_taper_gaspari_cohn(fluid_ctx *ctx, float col, float row, float c, void
 int fluid_transform_members_lattice(fluid_ctx *ctx, const int *fields, int nfields, const float *increments, int nodes_row,
                                     int nodes_col, int row0, int col0, int step);
 
+/* ---- lattice observations: the localised Gram matrix, right-hand side and innovation norm of every node, in one call ----
+ * M = fluid_members(ctx), P = the resident network of fluid_set_observation_points, B = nodes_row * nodes_col.  The D_b of a
+ * lattice update come from the Gram matrix of the observations near node b, weighted by a taper about b.  One
+ * fluid_observation_gram call per node -- the taper folded into inv_sigma -- observes all P points in all M members B
+ * times and waits B times; this call observes every point once and returns every node's matrices after ONE wait, in two
+ * kernel launches whatever B, P and M are.  The lattice arguments are fluid_transform_members_lattice's, so result [a][b]
+ * lines up with increments[a][b]: node (a, b) has index a * nodes_col + b and sits on cell row row0 + a*step, column
+ * col0 + b*step; any int origin, `step` a positive multiple of 8, B <= FLUID_LATTICE_MAX_NODES.  `c`: the localisation
+ * half-width, as in fluid_taper_gaspari_cohn, finite and > 0; a node's support is the disc of radius 2c.  All arrays are
+ * host memory: `gram` B*M*M doubles, [node][k][m]; `rhs` B*M doubles or null; `dd` B doubles or null; `counts` B ints or
+ * null; `obs`, `inv_sigma` as in fluid_observation_gram, P floats each, inv_sigma null for 1.0; rhs and dd MUST be null
+ * when obs is null.  Synchronous like fluid_observation_gram.
+ * Definition, per node:
+ *  1. h_k[p], mean_d[p], a_k[p] and d[p] are exactly rules 1-3 of fluid_observation_gram: the same lazy state is settled
+ *     first, fp16 taps are widened and the pressure scale divided back, the mean is over the members at the point whatever
+ *     the node.  The operands of a point are the same in every node that sees it.
+ *  2. The weight of point p at the node, in IEEE double, every operation rounded once and none contracted:
+ *       dx = (double)col_p - (double)node_col;  dy = (double)row_p - (double)node_row;
+ *       r  = sqrt(dx*dx + dy*dy) / (double)c;
+ *     g = the Gaspari-Cohn value of fluid_taper_gaspari_cohn at r (the same function: the same Horner forms and constants,
+ *     0 for r >= 2, clamped to [0, 1]);  w = (double)(float)g.
+ *  3. A point takes part in a node when w != 0.  A point with w == 0 is not read for that node: a non-finite observation
+ *     or obs value there poisons nothing of that node.
+ *  4. Over the participating points: gram[k][m], k <= m, = sum of (w*a_k) * a_m;  rhs[k] = sum of (w*a_k) * d;  dd = sum of
+ *     (w*d) * d.  w*a_k and w*d are rounded once; the second product is fused into the addition or rounded on its own.
+ *     gram[m][k] is a copy of gram[k][m]: the matrix is bit-symmetric.
+ *  5. counts[node] = the number of participating points.  A node with none has every entry of its matrix, its rhs and its
+ *     dd equal to +0.0, and count 0.
+ *  6. No floating-point atomics, no matrix instructions.  A node's points are taken in increasing point index in chunks of
+ *     64, point i of a chunk by wave i mod 4, and the four waves' sums are added in wave order: the order of every addition
+ *     is fixed by the network, the lattice arguments, c, M, centre and whether obs is given -- the same bits call after
+ *     call and context after context, and the exact sum when every partial sum is representable.  Every sum starts from
+ *     its first term.
+ *  7. centre == 0: a non-finite h_k at a point poisons row k, column k and rhs[k] of the nodes the point takes part in, and
+ *     nothing else; a non-finite y_p poisons rhs and dd of those nodes only.  centre != 0: a non-finite h_k at a point
+ *     poisons every entry of those nodes, and no other node.
+ *  8. M in [1, FLUID_TRANSFORM_MAX_MEMBERS].
+ * Which points a node sees is found on the host at call time, from a host copy of the network's positions (8 bytes per
+ * point) and the lattice geometry: only the nodes within 2c of a point are tried.  The lists -- (point index, float weight)
+ * pairs per node --, the operands of the points ((M padded + 2) doubles per point) and the results are library-owned device
+ * memory outside the arena with pinned twins (fluid_arena_bytes_ensemble is unchanged), allocated or grown by the first
+ * call that needs the room and freed by fluid_destroy; a failed allocation is FLUID_E_NOMEM and leaves the context usable.
+ * The lists are kept: a call with the same network, lattice arguments and c as the one before rebuilds and uploads none
+ * of them; fluid_set_observation_points invalidates them.
+ * Refusals, all FLUID_E_INVALID with a message that names the call, found before anything is launched or any state
+ * changes, null pointers before the context is looked at: a null `gram`; rhs or dd given with obs null; a null context; a
+ * bad field id; no network set; row slabs; M > FLUID_TRANSFORM_MAX_MEMBERS (the message gives both numbers); nodes_row or
+ * nodes_col below 1; more than FLUID_LATTICE_MAX_NODES nodes (the message gives both numbers); a step below 8 or not a
+ * multiple of 8; a `c` that is not finite or is <= 0; a non-finite inv_sigma[p], named by its index; more than
+ * FLUID_LATTICE_GRAM_MAX_ENTRIES (point, node) pairs in total (the message gives both numbers; they are counted before
+ * anything is allocated).
+ * The launches belong to none of the fluid_timing categories. */
+#define FLUID_LATTICE_GRAM_MAX_ENTRIES (1 << 24)
+int fluid_observation_gram_lattice(fluid_ctx *ctx, int field, int centre, const float *obs, const float *inv_sigma,
+                                   int nodes_row, int nodes_col, int row0, int col0, int step, float c,
+                                   double *gram, double *rhs, double *dd, int *counts);
+
 int fluid_set_jacobi_variant(fluid_ctx *ctx, int variant);
 /* How FLUID_JACOBI_TB divides by `beta` in a solve with these coefficients (diagnostic; runs the on-device proof
  * if this beta has not been seen): 0 true division, 2 double-precision reciprocal, 3 two-term float reciprocal
