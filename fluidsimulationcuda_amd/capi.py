@@ -141,6 +141,9 @@ SIGNATURES = {
     "fluid_taper_gaspari_cohn": [_ctx, _f, _f, _f, C.c_void_p, C.POINTER(_i)],
     "fluid_observation_gram_lattice": [_ctx, _i, _i, _MF, _MF, _i, _i, _i, _i, _i, _f, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                        C.POINTER(C.c_double), C.POINTER(_i)],
+    "fluid_etkf_increments": [_ctx, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i), _f, _MF, C.POINTER(_i)],
+    "fluid_analyse_lattice": [_ctx, _i, _MF, _MF, _i, _i, _i, _i, _i, _f, _f, C.POINTER(_i), _i],
+    "fluid_analyse_lattice_status": [_ctx, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
     "fluid_set_jacobi_variant": [_ctx, _i],
     "fluid_division_mode": [_ctx, _f, _f, C.POINTER(_i)],
     "fluid_autotune_pending": [_ctx, C.POINTER(_i)],
@@ -170,6 +173,8 @@ TRANSFORM_MAX_MEMBERS = 64
 OBSERVE_MAX_POINTS = 1 << 20
 LATTICE_MAX_NODES = 4096
 LATTICE_GRAM_MAX_ENTRIES = 1 << 24
+ETKF_MAX_SWEEPS = 28
+ETKF_SOLVED, ETKF_EMPTY, ETKF_FAILED = 0, 1, 2
 
 _lib = None
 

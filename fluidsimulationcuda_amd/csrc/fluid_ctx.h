@@ -182,6 +182,20 @@ struct LatticeGram {
     long long pairs = 0;                  // entries of the lists
 };
 
+// The ETKF solve (fluid_etkf_increments, fluid_analyse_lattice): library-owned and outside the arena, freed in
+// fluid_destroy.  The host route's operands ([nodes] M x M doubles, [nodes] M doubles, [nodes] ints) and results ([nodes]
+// M x M floats, [nodes] ints) each are ONE buffer with a pinned twin, grown on demand (fluid_solver.hip: grow_lattice_gram); every
+// call of that route ends in a wait.  The fused route's status words, one per node, have a fixed size:
+// FLUID_LATTICE_MAX_NODES ints and their twin, allocated by the first analysis.  `in_flight`: an analysis has been
+// enqueued and nothing has waited for the stream since -- its launches may still read the point lists and their twin.
+struct EtkfBuffers {
+    char *d_in = nullptr, *h_in = nullptr, *d_out = nullptr, *h_out = nullptr;
+    size_t in_bytes = 0, out_bytes = 0;   // the room of each pair
+    int *d_status = nullptr, *h_status = nullptr;
+    int analysed = 0;                     // nodes of the last fluid_analyse_lattice, 0 before the first
+    bool in_flight = false;
+};
+
 struct fluid_ctx {
     int n = 0, w = 0, pitch = 0;
     size_t field_floats = 0;
@@ -219,6 +233,7 @@ struct fluid_ctx {
     LatticeNodeTables lattice;            // node tables of fluid_transform_members_lattice
     Observation observe;                  // the observation network and the scratch of fluid_observation_gram
     LatticeGram lgram;                    // point lists, operands and results of fluid_observation_gram_lattice
+    EtkfBuffers etkf;                     // operands, results and status words of the ETKF solve
     unsigned int* tiles = nullptr;        // 3 x members x tile_rows x tile_pitch words: |x0| minima per tile for division mode 3
     unsigned int* h_scalar = nullptr;     // pinned host mirror
     hipEvent_t scalar_ready = nullptr;    // recorded behind the scalar's device-to-host copy

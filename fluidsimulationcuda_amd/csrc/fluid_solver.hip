@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "fluid_ctx.h"
+#include "fluid_etkf.h"
 
 namespace fluid_detail {
 
@@ -1871,6 +1872,12 @@ int fluid_destroy(fluid_ctx* c)
     if (c->lgram.d_operands) (void)hipFree(c->lgram.d_operands);
     if (c->lgram.d_out) (void)hipFree(c->lgram.d_out);
     if (c->lgram.h_out) (void)hipHostFree(c->lgram.h_out);
+    if (c->etkf.d_in) (void)hipFree(c->etkf.d_in);
+    if (c->etkf.h_in) (void)hipHostFree(c->etkf.h_in);
+    if (c->etkf.d_out) (void)hipFree(c->etkf.d_out);
+    if (c->etkf.h_out) (void)hipHostFree(c->etkf.h_out);
+    if (c->etkf.d_status) (void)hipFree(c->etkf.d_status);
+    if (c->etkf.h_status) (void)hipHostFree(c->etkf.h_status);
     for (hipEvent_t ev : c->xform.copied)
         if (ev) (void)hipEventDestroy(ev);
     if (c->xform.dev) (void)hipFree(c->xform.dev);
@@ -3456,13 +3463,13 @@ static int grow_lattice_gram(const char* call, const char* what, char** dev, cha
     return FLUID_OK;
 }
 
-int fluid_observation_gram_lattice(fluid_ctx* c, int field, int centre, const float* obs, const float* inv_sigma, int nodes_row, int nodes_col,
-                                   int row0, int col0, int step, float hw, double* gram, double* rhs, double* dd, int* counts)
+// What fluid_observation_gram_lattice and fluid_analyse_lattice share, under the caller's name: the refusals beyond the
+// call's own pointers, the point lists (built, cached and uploaded here and nowhere else), and the two launches that leave
+// every node's result in LatticeGram::d_out.  Nothing is waited for, except where a buffer an analysis in flight may still
+// read is about to be rewritten or freed.
+static int enqueue_lattice_gram(fluid_ctx* c, const char* call, int field, int centre, const float* obs, const float* inv_sigma, int nodes_row,
+                                int nodes_col, int row0, int col0, int step, float hw)
 {
-    const char* call = "fluid_observation_gram_lattice";
-    if (!gram) return fail(FLUID_E_INVALID, "%s: null array `gram`", call);
-    if (!obs && (rhs || dd)) return fail(FLUID_E_INVALID, "%s: `%s` is given but `obs` is null", call, rhs ? "rhs" : "dd");
-    if (!c) return fail(FLUID_E_INVALID, "%s: null context", call);
     TRY(check_observe(c, call, field));
     if (c->members > FLUID_TRANSFORM_MAX_MEMBERS)
         return fail(FLUID_E_INVALID, "%s: this context has %d members, above FLUID_TRANSFORM_MAX_MEMBERS = %d", call, c->members,
@@ -3486,6 +3493,10 @@ int fluid_observation_gram_lattice(fluid_ctx* c, int field, int centre, const fl
                         g.step == step && g.c == hw;
     std::vector<int> start;                                              // start[node + 1]: the entries of the nodes up to and with `node`
     long long pairs = g.pairs;
+    if (!cached && c->etkf.in_flight) {                                  // an analysis may still read the lists about to be replaced
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        c->etkf.in_flight = false;
+    }
     if (!cached) {
         start.assign(B + 1, 0);
         pairs = 0;
@@ -3536,8 +3547,25 @@ int fluid_observation_gram_lattice(fluid_ctx* c, int field, int centre, const fl
     fluid::launch_observation_gram_lattice(c->stream, c->st, c->ptr(field), c->pitch, c->mb(), inv, observation_points(c), centre != 0,
                                            obs ? o.obs() : nullptr, inv_sigma ? o.sigma() : nullptr, g.d_operands, lists, g.d_out);
     HIP_TRY(hipGetLastError());
+    return FLUID_OK;
+}
+
+int fluid_observation_gram_lattice(fluid_ctx* c, int field, int centre, const float* obs, const float* inv_sigma, int nodes_row, int nodes_col,
+                                   int row0, int col0, int step, float hw, double* gram, double* rhs, double* dd, int* counts)
+{
+    const char* call = "fluid_observation_gram_lattice";
+    if (!gram) return fail(FLUID_E_INVALID, "%s: null array `gram`", call);
+    if (!obs && (rhs || dd)) return fail(FLUID_E_INVALID, "%s: `%s` is given but `obs` is null", call, rhs ? "rhs" : "dd");
+    if (!c) return fail(FLUID_E_INVALID, "%s: null context", call);
+    TRY(enqueue_lattice_gram(c, call, field, centre, obs, inv_sigma, nodes_row, nodes_col, row0, col0, step, hw));
+    LatticeGram& g = c->lgram;
+    const size_t B = (size_t)nodes_row * (size_t)nodes_col;
+    const int M = c->members, mp = fluid::gram_padded(M);
+    const size_t E = fluid::observation_gram_entries(M);
+    const int* h_start = reinterpret_cast<const int*>(g.h_lists);
     HIP_TRY(hipMemcpyAsync(g.h_out, g.d_out, B * E * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    c->etkf.in_flight = false;
     for (size_t b = 0; b < B; ++b) {
         const int count = h_start[b + 1] - h_start[b];
         const double* r = g.h_out + b * E;
@@ -3549,6 +3577,164 @@ int fluid_observation_gram_lattice(fluid_ctx* c, int field, int centre, const fl
             for (int k = 0; k < M; ++k) rhs[b * M + k] = count ? r[(size_t)mp * mp + k] : 0.0;
         if (dd) dd[b] = count ? r[(size_t)mp * mp + mp] : 0.0;
     }
+    return FLUID_OK;
+}
+
+// ---- one-call analysis: fluid_etkf_increments, fluid_analyse_lattice, fluid_analyse_lattice_status -------------------------
+// (include/fluid_amd.h "one-call analysis".)  One kernel solves every node (fluid_kernels.hip: k_etkf_solve); the host
+// route feeds it from and to host arrays through the buffers of EtkfBuffers and waits, the fused route points it at the
+// results fluid_observation_gram_lattice's launches leave on the device and at the node tables the lattice launch reads,
+// and waits for nothing.
+static int check_etkf(const fluid_ctx* c, const char* call, float rho)
+{
+    static_assert(FLUID_ETKF_MAX_SWEEPS == fluid::kEtkfMaxSweeps, "the header's cap is the kernel's");
+    TRY(refuse_slabs(c, call));                                          // (a slab context has one member: say what it is first)
+    if (c->members < 2) return fail(FLUID_E_INVALID, "%s: this context has %d members, below 2", call, c->members);
+    if (c->members > FLUID_TRANSFORM_MAX_MEMBERS)
+        return fail(FLUID_E_INVALID, "%s: this context has %d members, above FLUID_TRANSFORM_MAX_MEMBERS = %d", call, c->members,
+                    FLUID_TRANSFORM_MAX_MEMBERS);
+    if (!std::isfinite(rho) || !(rho > 0.0f)) return fail(FLUID_E_INVALID, "%s: rho = %g is not finite or not above 0", call, (double)rho);
+    return FLUID_OK;
+}
+
+int fluid_etkf_increments(fluid_ctx* c, int nodes, const double* gram, const double* rhs, const int* counts, float rho, float* increments,
+                          int* status)
+{
+    const char* call = "fluid_etkf_increments";
+    if (!gram) return fail(FLUID_E_INVALID, "%s: null array `gram`", call);
+    if (!rhs) return fail(FLUID_E_INVALID, "%s: null array `rhs`", call);
+    if (!increments) return fail(FLUID_E_INVALID, "%s: null array `increments`", call);
+    if (!c) return fail(FLUID_E_INVALID, "%s: null context", call);
+    if (nodes < 1 || nodes > FLUID_LATTICE_MAX_NODES)
+        return fail(FLUID_E_INVALID, "%s: nodes = %d outside [1, FLUID_LATTICE_MAX_NODES = %d]", call, nodes, FLUID_LATTICE_MAX_NODES);
+    TRY(check_etkf(c, call, rho));
+    const int M = c->members;
+    const size_t B = (size_t)nodes, MM = (size_t)M * M;
+    for (size_t b = 0; b < B; ++b) {
+        if (counts && counts[b] == 0) continue;                          // an empty node is not read
+        for (int k = 0; k < M; ++k) {
+            for (int m = k; m < M; ++m)
+                if (!std::isfinite(gram[b * MM + (size_t)k * M + m]))
+                    return fail(FLUID_E_INVALID, "%s: gram of node %zu, k = %d, m = %d is not finite", call, b, k, m);
+            if (!std::isfinite(rhs[b * M + k])) return fail(FLUID_E_INVALID, "%s: rhs of node %zu, k = %d is not finite", call, b, k);
+        }
+    }
+    EtkfBuffers& e = c->etkf;
+    const size_t gram_bytes = B * MM * sizeof(double), rhs_bytes = B * M * sizeof(double), word_bytes = B * sizeof(int);
+    const size_t inc_bytes = B * MM * sizeof(float);
+    TRY(grow_lattice_gram(call, "operands", &e.d_in, &e.h_in, &e.in_bytes, gram_bytes + rhs_bytes + word_bytes));
+    TRY(grow_lattice_gram(call, "results", &e.d_out, &e.h_out, &e.out_bytes, inc_bytes + word_bytes));
+    std::memcpy(e.h_in, gram, gram_bytes);
+    std::memcpy(e.h_in + gram_bytes, rhs, rhs_bytes);
+    if (counts) std::memcpy(e.h_in + gram_bytes + rhs_bytes, counts, word_bytes);
+    HIP_TRY(hipMemcpyAsync(e.d_in, e.h_in, gram_bytes + rhs_bytes + (counts ? word_bytes : 0), hipMemcpyHostToDevice, c->stream));
+    fluid::EtkfOperands in;
+    in.gram = reinterpret_cast<const double*>(e.d_in);
+    in.gram_node = MM;
+    in.gram_row = (size_t)M;
+    in.rhs = reinterpret_cast<const double*>(e.d_in + gram_bytes);
+    in.rhs_node = (size_t)M;
+    in.counts = counts ? reinterpret_cast<const int*>(e.d_in + gram_bytes + rhs_bytes) : nullptr;
+    fluid::EtkfResults out;
+    out.increments = reinterpret_cast<float*>(e.d_out);
+    out.status = reinterpret_cast<int*>(e.d_out + inc_bytes);
+    fluid::launch_etkf_solve(c->stream, M, (double)(M - 1) / (double)rho, in, out, nodes);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(e.h_out, e.d_out, inc_bytes + word_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    e.in_flight = false;
+    std::memcpy(increments, e.h_out, inc_bytes);
+    if (status) std::memcpy(status, e.h_out + inc_bytes, word_bytes);
+    return FLUID_OK;
+}
+
+// the status words of the fused route: one int per node of the largest lattice, and their pinned twin
+static int ensure_etkf_status(fluid_ctx* c, const char* call)
+{
+    EtkfBuffers& e = c->etkf;
+    if (e.d_status) return FLUID_OK;
+    const size_t bytes = (size_t)FLUID_LATTICE_MAX_NODES * sizeof(int);
+    int *dev = nullptr, *host = nullptr;
+    hipError_t err = hipMalloc((void**)&dev, bytes);
+    if (err == hipSuccess) err = hipHostMalloc((void**)&host, bytes, hipHostMallocDefault);
+    if (err != hipSuccess) {
+        (void)hipGetLastError();
+        if (dev) (void)hipFree(dev);
+        return fail(err == hipErrorOutOfMemory ? FLUID_E_NOMEM : FLUID_E_HIP, "%s: allocating %zu bytes of status words: %s", call, bytes,
+                    hipGetErrorString(err));
+    }
+    e.d_status = dev;
+    e.h_status = host;
+    return FLUID_OK;
+}
+
+int fluid_analyse_lattice(fluid_ctx* c, int field, const float* obs, const float* inv_sigma, int nodes_row, int nodes_col, int row0, int col0,
+                          int step, float hw, float rho, const int* fields, int nfields)
+{
+    const char* call = "fluid_analyse_lattice";
+    if (!obs) return fail(FLUID_E_INVALID, "%s: null array `obs`", call);
+    if (!fields) return fail(FLUID_E_INVALID, "%s: null array `fields`", call);
+    if (!c) return fail(FLUID_E_INVALID, "%s: null context", call);
+    TRY(check_transform(c, call, fields, nfields));
+    TRY(check_etkf(c, call, rho));
+    TRY(ensure_etkf_status(c, call));
+    // the two Gram launches: every node's C, rhs and dd in LatticeGram::d_out, its point count in the start offsets of d_lists
+    TRY(enqueue_lattice_gram(c, call, field, /*centre=*/1, obs, inv_sigma, nodes_row, nodes_col, row0, col0, step, hw));
+    const int M = c->members, MP = fluid::transform_padded(M), mp = fluid::gram_padded(M), nodes = nodes_row * nodes_col;
+    const size_t E = fluid::observation_gram_entries(M);
+    const size_t table_bytes = (size_t)nodes * M * MP * sizeof(double), bits_bytes = (size_t)nodes * M * sizeof(unsigned long long);
+    TRY(ensure_lattice(c, call, table_bytes + bits_bytes + (size_t)nodes * sizeof(unsigned long long)));
+    LatticeNodeTables& t = c->lattice;          // written on the device, in stream order: the pinned twin and its event stay out of it
+    LatticeGram& g = c->lgram;
+    fluid::EtkfOperands in;
+    in.gram = g.d_out;
+    in.gram_node = E;
+    in.gram_row = (size_t)mp;
+    in.rhs = g.d_out + (size_t)mp * mp;
+    in.rhs_node = E;
+    in.counts = reinterpret_cast<const int*>(g.d_lists);
+    in.starts = true;
+    fluid::EtkfResults out;
+    out.table = reinterpret_cast<double*>(t.dev);
+    out.bits = reinterpret_cast<unsigned long long*>(t.dev + table_bytes);
+    out.cols = out.bits + (size_t)nodes * M;
+    out.status = c->etkf.d_status;
+    fluid::launch_etkf_solve(c->stream, M, (double)(M - 1) / (double)rho, in, out, nodes);
+    HIP_TRY(hipGetLastError());
+    c->etkf.analysed = nodes;
+    c->etkf.in_flight = true;
+    fluid::LatticeTables dev;
+    dev.table = out.table;
+    dev.bits = out.bits;
+    dev.cols = out.cols;
+    const fluid::Lattice lat = {nodes_row, nodes_col, row0, col0, step};
+    for (int k = 0; k < nfields; ++k) {
+        const int f = fields[k];
+        const float scale = c->st != fluid::STORAGE_F32 ? c->field[f].fscale : 1.0f;           // as pack_range sees the field
+        TRY(materialize(c, f, /*keep_scale=*/scale != 1.0f));
+        // the general path: whether every increment is non-zero is not known here, and the bits do not depend on it
+        fluid::launch_transform_members_lattice(c->stream, c->st, c->ptr(f), c->pitch, c->n, c->mb(), 1.0f / scale, scale, dev, /*dense=*/false, lat);
+        HIP_TRY(hipGetLastError());
+        wrote(c, f, kEverywhere);                                    // nothing owed ...
+        c->field[f].fscale = scale;                                  // ... and the scale it had: the launch stored at it
+    }
+    return FLUID_OK;
+}
+
+int fluid_analyse_lattice_status(fluid_ctx* c, int* solved, int* empty, int* failed)
+{
+    const char* call = "fluid_analyse_lattice_status";
+    if (!c) return fail(FLUID_E_INVALID, "%s: null context", call);
+    EtkfBuffers& e = c->etkf;
+    if (e.analysed == 0) return fail(FLUID_E_INVALID, "%s: no fluid_analyse_lattice has run in this context", call);
+    HIP_TRY(hipMemcpyAsync(e.h_status, e.d_status, (size_t)e.analysed * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    e.in_flight = false;
+    int n[3] = {0, 0, 0};
+    for (int b = 0; b < e.analysed; ++b) n[e.h_status[b] == 0 ? 0 : e.h_status[b] == 1 ? 1 : 2] += 1;
+    if (solved) *solved = n[0];
+    if (empty) *empty = n[1];
+    if (failed) *failed = n[2];
     return FLUID_OK;
 }
 

@@ -548,6 +548,66 @@ class FluidSolver:
             None if y is None else dd.ctypes.data_as(dp), counts.ctypes.data_as(C.POINTER(C.c_int))))
         return (g, counts) if y is None else (g, rhs, dd, counts)
 
+    # -- one-call analysis: the ETKF solved per node on the device, and Gram -> solve -> lattice update without a wait
+    def etkf_increments(self, C_, rhs, counts=None, rho=1.0):
+        """The ETKF increment D = W - I + w 1^T of every node from its Gram matrix and right-hand side (what
+        observation_gram_lattice returns), S = (M - 1) / rho I + C solved by Jacobi rotations on the device, every node in
+        one launch: C_ (..., M, M) and rhs (..., M) float64, counts (...) ints or None, rho the multiplicative inflation.
+        Returns (D float32 (..., M, M), status int32 (...)): 0 solved, 1 empty (counts == 0: D = 0), 2 failed (D = 0).
+        Only the upper triangle of C_ is read; the same bits for a node whatever the batch (include/fluid_amd.h, "one-call
+        analysis")."""
+        m, dp = self.members, C.POINTER(C.c_double)
+        g = np.ascontiguousarray(np.asarray(C_, np.float64))
+        r = np.ascontiguousarray(np.asarray(rhs, np.float64))
+        if g.ndim < 2 or g.shape[-2:] != (m, m):
+            raise ValueError("C must have shape (..., %d, %d), got %s" % (m, m, g.shape))
+        lead = g.shape[:-2]
+        if r.shape != lead + (m,):
+            raise ValueError("rhs must have shape %s, got %s" % (lead + (m,), r.shape))
+        n = None
+        if counts is not None:
+            n = np.ascontiguousarray(np.asarray(counts, np.int32))
+            if n.shape != lead:
+                raise ValueError("counts must have shape %s, got %s" % (lead, n.shape))
+        nodes = int(np.prod(lead, dtype=np.int64))
+        d, status = np.empty(lead + (m, m), np.float32), np.empty(lead, np.int32)
+        capi.check(capi.lib().fluid_etkf_increments(self._h, nodes, g.ctypes.data_as(dp), r.ctypes.data_as(dp),
+                                                    None if n is None else n.ctypes.data_as(C.POINTER(C.c_int)), float(rho), _mf(d),
+                                                    status.ctypes.data_as(C.POINTER(C.c_int))))
+        return d, status
+
+    def analyse_lattice(self, field, shape, origin, step, c, obs, inv_sigma=None, rho=1.0, fields=("dens", "u", "v"), wait=True):
+        """One assimilation cycle of a localised filter: observation_gram_lattice(field, centre=True), etkf_increments and
+        transform_lattice(fields), bit for bit, but chained on the device -- two Gram launches, one solve, one lattice
+        launch per listed field; nothing crosses to the host.  `wait=False` returns once everything is enqueued;
+        analyse_status() says how the nodes ended (include/fluid_amd.h, "one-call analysis")."""
+        points = self.observation_points()
+
+        def per_point(a, name):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(np.asarray(a, np.float32).ravel())
+            if a.size != points:
+                raise ValueError("%s must hold one value per point (%d), got %d" % (name, points, a.size))
+            return a
+
+        y, s = per_point(obs, "obs"), per_point(inv_sigma, "inv_sigma")
+        nr, nc = (int(v) for v in shape)
+        row0, col0 = (int(v) for v in origin)
+        ids = [_fid(f) for f in fields]
+        capi.check(capi.lib().fluid_analyse_lattice(self._h, _fid(field), None if y is None else _mf(y), None if s is None else _mf(s),
+                                                    nr, nc, row0, col0, int(step), float(c), float(rho), (C.c_int * len(ids))(*ids),
+                                                    len(ids)))
+        if wait:
+            self.synchronize()
+
+    def analyse_status(self):
+        """Waits for the stream; {"solved", "empty", "failed"}: how many nodes of the last analyse_lattice ended in each
+        status."""
+        n = [C.c_int(), C.c_int(), C.c_int()]
+        capi.check(capi.lib().fluid_analyse_lattice_status(self._h, *(C.byref(v) for v in n)))
+        return {"solved": n[0].value, "empty": n[1].value, "failed": n[2].value}
+
     def set_jacobi_variant(self, variant):
         capi.check(capi.lib().fluid_set_jacobi_variant(self._h, variant))
 

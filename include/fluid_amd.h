@@ -742,6 +742,75 @@ int fluid_observation_gram_lattice(fluid_ctx *ctx, int field, int centre, const 
                                    int nodes_row, int nodes_col, int row0, int col0, int step, float c,
                                    double *gram, double *rhs, double *dd, int *counts);
 
+/* ---- one-call analysis: the ETKF solved at every node on the device, and the whole localised update in one call ------------
+ * M = fluid_members(ctx), 2 <= M <= FLUID_TRANSFORM_MAX_MEMBERS.  Between the lattice Gram call and the lattice update a
+ * localised filter solves one M x M symmetric eigenproblem per node.  fluid_etkf_increments does that for host arrays, every
+ * node in ONE kernel launch; fluid_analyse_lattice chains Gram, solve and update on the device without a copy or a wait.
+ *
+ * The solve, per node, in IEEE double, one definition for both calls:
+ *  1. Only gram[k][m] with k <= m is read; the rest is its mirror.  S = mirror(gram) with S_kk = (double)(M-1) / (double)rho
+ *     + gram_kk.  `rho` is the multiplicative inflation of Hunt et al. (2007), finite and > 0; 1 means none.
+ *  2. S = V L V^T by cyclic Jacobi rotations in the round-robin ordering: with n = M rounded up to even, a sweep is n - 1
+ *     steps, step s rotating the disjoint pairs {n-1, s} and {(s+i) mod (n-1), (s-i) mod (n-1)}, i = 1 .. n/2 - 1, together
+ *     (a pair with index M, the bye of an odd M, does nothing).  A pair p < q is skipped when |S_pq| <= 2^-53 *
+ *     sqrt(S_pp) * sqrt(S_qq); otherwise theta = (S_qq - S_pp) / (2 S_pq), t = sign(theta) / (|theta| + sqrt(theta^2 + 1))
+ *     (1 / (2 theta) once theta^2 would overflow), c = 1 / sqrt(t^2 + 1), s = t c.  A sweep in which every pair was skipped
+ *     ends the solve; FLUID_ETKF_MAX_SWEEPS sweeps without one fail the node.
+ *  3. l_i = S_ii.  W = V diag(sqrt((M-1) / l_i)) V^T, entry [k][m] the sum over i, in index order, of (V_ki * V_mi) *
+ *     sqrt((M-1) / l_i);  w = V diag(1 / l_i) V^T rhs: u_i = (sum over k of V_ki * rhs_k) / l_i, w_k = sum over i of V_ki * u_i.
+ *  4. D[k][m] = (W[k][m] - delta_km) + w[k], and the increment is (float)D[k][m]: the weight of OLD member k in the INCREMENT
+ *     of new member m, what fluid_transform_members_lattice takes.  For a centred C (C 1 = 0 and rhs . 1 = 0, what centre != 0
+ *     produces) and rho = 1 this equals the ETKF increment 1 1^T / M + A (W + w 1^T) - I with A = I - 1 1^T / M: 1 is then
+ *     an eigenvector of S with eigenvalue M-1, so W 1 = 1 and w . 1 = 0, and A drops out.  With rho != 1 that eigenvalue is
+ *     (M-1) / rho and W 1 = sqrt(rho) 1: D exceeds the centred form by (sqrt(rho) - 1) / M in every entry, that is, the
+ *     inflation acts on the ensemble mean as well as on the anomalies.  A caller who wants the anomalies alone inflated
+ *     subtracts that constant from the increments of fluid_etkf_increments; fluid_analyse_lattice applies D as defined.
+ *  5. Status per node: 0 solved.  1 empty: `counts` is given and counts[node] == 0; the node is neither read nor solved and
+ *     D = +0 everywhere -- the background is kept.  2 failed: a non-finite operand, an l_i that is not finite and > 0, the
+ *     sweep cap reached, or a D entry that is not finite as a float; D = +0 everywhere.  A failed node changes nothing of
+ *     any other node.
+ *  6. No eigenvector order or sign is specified; W depends on neither.  A node's M*M floats depend on (M, rho, its upper
+ *     triangle, its rhs) alone: the same bits for any node count and node index, call after call and context after
+ *     context.  No atomics, no matrix instructions; every rotation order and every order of summation is fixed by M.
+ *  7. gram = 0, rhs = 0 and rho = 1 give D == 0 in every entry.
+ *
+ * - fluid_etkf_increments: all arrays are host memory -- `gram` nodes*M*M doubles, `rhs` nodes*M doubles, `counts` nodes ints
+ *   or null (no node is empty), `increments` nodes*M*M floats, increments[(node*M + k)*M + m], `status` nodes ints or null.
+ *   Synchronous: one upload, one kernel launch whatever `nodes` is, one download, one wait.  It touches no field.  The
+ *   buffers are library-owned device memory outside the arena with pinned twins (fluid_arena_bytes_ensemble is unchanged),
+ *   grown on demand and freed by fluid_destroy; a failed allocation is FLUID_E_NOMEM and leaves the context usable.
+ *   Refusals, all FLUID_E_INVALID with a message that names the call, found before anything is launched, null pointers
+ *   before the context is looked at: a null `gram`, `rhs` or `increments`; a null context; nodes outside [1,
+ *   FLUID_LATTICE_MAX_NODES]; M < 2 or M > FLUID_TRANSFORM_MAX_MEMBERS (the message gives both numbers); a rho that is not
+ *   finite or is <= 0; a non-finite gram[k <= m] or rhs entry of a node that is not empty (the message names node, k and
+ *   m); row slabs.
+ * - fluid_analyse_lattice is, bit for bit in every listed field of every member, the sequence
+ *       fluid_observation_gram_lattice(ctx, field, 1, obs, inv_sigma, nodes_row .. step, c, gram, rhs, dd, counts);
+ *       fluid_etkf_increments(ctx, nodes_row * nodes_col, gram, rhs, counts, rho, increments, status);
+ *       fluid_transform_members_lattice(ctx, fields, nfields, increments, nodes_row .. step);
+ *   but nothing crosses to the host and nothing waits: the call enqueues the two Gram launches, the solve -- reading their
+ *   results and the lists' point counts where they lie, writing the node tables of the lattice update in place -- and one
+ *   lattice launch per listed field, and returns.  The lattice launch is always the general one (whether every increment
+ *   is non-zero is not known on the host; the bits do not depend on it).  A node without points and a failed node have no
+ *   term and store nothing; if every node is like that the launches store nothing and every bit is kept.  The point
+ *   lists are built, cached and invalidated exactly as fluid_observation_gram_lattice's -- they are the same lists.
+ *   `obs` is required; `field` may or may not be among `fields`.  Refusals: the union of the three calls', under this
+ *   call's name.
+ * - fluid_analyse_lattice_status waits for the stream and returns how many nodes of the last fluid_analyse_lattice ended
+ *   in each status (any of the three pointers may be null): the solve leaves one word per node, folded on the host.
+ *   FLUID_E_INVALID before the first analysis of the context.
+ * FLUID_ETKF_MAX_SWEEPS: a model of the kernel's ordering and threshold (tests/test_gpu_etkf.py: jacobi_model) needed at
+ * most 14 sweeps, the last one without a rotation, over that file's inputs at M = 2 .. 64 (14 at M = 64 on a rank-39 matrix,
+ * whose 25 equal eigenvalues keep rotating among themselves at rounding level; 9 to 11 on the others; 9 at M = 33, 7 at
+ * M = 9); the cap is twice that and not below 16.
+ * The launches belong to none of the fluid_timing categories. */
+#define FLUID_ETKF_MAX_SWEEPS 28
+int fluid_etkf_increments(fluid_ctx *ctx, int nodes, const double *gram, const double *rhs, const int *counts, float rho,
+                          float *increments, int *status);
+int fluid_analyse_lattice(fluid_ctx *ctx, int field, const float *obs, const float *inv_sigma, int nodes_row, int nodes_col,
+                          int row0, int col0, int step, float c, float rho, const int *fields, int nfields);
+int fluid_analyse_lattice_status(fluid_ctx *ctx, int *solved, int *empty, int *failed);
+
 int fluid_set_jacobi_variant(fluid_ctx *ctx, int variant);
 /* How FLUID_JACOBI_TB divides by `beta` in a solve with these coefficients (diagnostic; runs the on-device proof
  * if this beta has not been seen): 0 true division, 2 double-precision reciprocal, 3 two-term float reciprocal

@@ -1,0 +1,530 @@
+"""GPU: the one-call analysis -- fluid_etkf_increments, fluid_analyse_lattice, fluid_analyse_lattice_status
+(include/fluid_amd.h, "one-call analysis").
+
+The solve is checked against its definition: S = (M - 1) / rho I + mirror(C) decomposed by numpy.linalg.eigh in float64, then
+w = V diag(1 / l) V^T rhs, W = V diag(sqrt((M - 1) / l)) V^T and D = W - I + w 1^T (INTEGRATION.md section 5 with the header's
+rule 4).  Per entry
+    |D - D_ref| <= 2^-23 |D_ref| + 64 M 2^-53 kappa (sqrt(rho) + max |w_ref|),      kappa = 1 + rho ||C||_2 / (M - 1):
+the two float roundings, and the backward error of a stable eigen-solver pushed through S^-1/2 and S^-1, both conditioned by
+kappa because l_min >= (M - 1) / rho.  The constant 64 is not derived; `jacobi_model` below -- the kernel's own round-robin
+ordering and threshold in numpy -- run in long double is the arbiter: on these inputs the float64 model and eigh each stay
+within 1.2 units of M 2^-53 sqrt(rho) kappa of it (a row-cyclic float64 Jacobi: 2.7; tests/test_etkf_abi.py asserts 4, on
+the CPU).  The largest GPU value observed on an MI355X: see test_against_the_definition.
+
+`jacobi_model` also fixes FLUID_ETKF_MAX_SWEEPS: twice the largest sweep count it needs on the inputs below (the last
+sweep, the one without a rotation, included), and not below 16.
+
+The fused call is checked against the three calls it is defined as, byte for byte, on twin contexts."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+F32 = np.float32
+MAIN = ("u", "v", "dens", "u_prev", "v_prev", "dens_prev")
+MEMBERS = [2, 3, 9, 33, 64]
+RHOS = [1.0, 1.1, 2.0]
+KINDS = ("P=5", "P=40 scale 4", "P=200 scale 30", "P=64 scale 300", "diagonal", "zero")
+U = 2.0 ** -53
+
+
+def F():
+    import fluidsimulationcuda_amd as f
+    return f
+
+
+def solver(n, members, storage=0, **kw):
+    return F().FluidSolver(n, members=members, storage=storage, **kw)
+
+
+# ---- inputs, the definition, the model ----------------------------------------------------------------------------------------
+def node_inputs(members, seed=0):
+    """the six node kinds of one batch: (C (6, M, M), rhs (6, M)), float64; C from centred operand columns where it has any"""
+    rng = np.random.default_rng(1000 * members + seed)
+    gram, rhs = np.zeros((6, members, members)), np.zeros((6, members))
+    for b, (p, scale) in enumerate(((5, 1.0), (40, 4.0), (200, 30.0), (64, 300.0))):
+        a = scale * rng.standard_normal((p, members))
+        a -= a.mean(axis=1, keepdims=True)                 # centred: every row sums to zero over the members
+        d = scale * rng.standard_normal(p)
+        gram[b] = a.T @ a
+        gram[b] = np.triu(gram[b]) + np.triu(gram[b], 1).T
+        rhs[b] = a.T @ d
+    gram[4] = np.diag(rng.uniform(0.5, 50.0, members))
+    rhs[4] = rng.standard_normal(members)
+    return gram, rhs
+
+
+def reference(gram, rhs, rho):
+    """(D, w, kappa) of the definition with numpy.linalg.eigh, float64"""
+    m = gram.shape[0]
+    s = np.triu(gram) + np.triu(gram, 1).T + (np.float64(m - 1) / np.float64(F32(rho))) * np.eye(m)
+    lam, v = np.linalg.eigh(s)
+    w = v @ ((v.T @ rhs) / lam)
+    big = v @ np.diag(np.sqrt((m - 1) / lam)) @ v.T
+    kappa = 1.0 + float(F32(rho)) * np.linalg.norm(gram, 2) / (m - 1)
+    return big - np.eye(m) + w[:, None], w, kappa
+
+
+def tolerance(d_ref, w_ref, kappa, members, rho):
+    return 2.0 ** -23 * np.abs(d_ref) + unit(w_ref, kappa, members, rho) * 64.0
+
+
+def unit(w_ref, kappa, members, rho):
+    """the second term of the tolerance without its constant"""
+    return members * U * kappa * (np.sqrt(float(F32(rho))) + np.abs(w_ref).max())
+
+
+def round_robin(n, step):
+    """the pairs (p < q) of step `step` of a sweep over n (even) indices: {n-1, step} and {(step+i), (step-i)} mod n-1"""
+    ring = n - 1
+    i = np.arange(1, n // 2)
+    a = np.concatenate([[ring], (step + i) % ring])
+    b = np.concatenate([[step], (step - i) % ring])
+    return np.minimum(a, b), np.maximum(a, b)
+
+
+def jacobi_model(gram, rhs, rho, dtype=np.float64, cap=200):
+    """The kernel's solve in numpy, in `dtype`: the same pairs per step, the same threshold (2^-53; the type's own half ulp
+    in long double), the same rotation formulas, row phase then column phase, the pair's block set to its closed form.
+    Returns (D, sweeps) -- sweeps counts the last one, in which nothing rotated."""
+    m = gram.shape[0]
+    one = dtype(1)
+    eps = dtype(U) if dtype == np.float64 else np.finfo(dtype).eps / 2
+    s = (np.triu(gram) + np.triu(gram, 1).T).astype(dtype)
+    s[np.diag_indices(m)] += dtype(np.float64(m - 1) / np.float64(F32(rho)))
+    v = np.eye(m, dtype=dtype)
+    n = (m + 1) & ~1
+    sweeps = 0
+    with np.errstate(all="ignore"):
+        while sweeps < cap:
+            sweeps += 1
+            rotated = False
+            for step in range(n - 1):
+                p, q = round_robin(n, step)
+                live = q < m
+                p, q = p[live], q[live]
+                app, aqq, apq = s[p, p], s[q, q], s[p, q]
+                on = ~(np.abs(apq) <= eps * (np.sqrt(app) * np.sqrt(aqq)))
+                if not on.any():
+                    continue
+                rotated = True
+                p, q, app, aqq, apq = p[on], q[on], app[on], aqq[on], apq[on]
+                theta = (aqq - app) / (2 * apq)
+                t = one / (np.abs(theta) + np.sqrt(theta * theta + one))
+                t = np.where(theta < 0, -t, t)
+                c = one / np.sqrt(t * t + one)
+                sn = t * c
+                x, y = s[p, :].copy(), s[q, :].copy()
+                s[p, :] = c[:, None] * x - sn[:, None] * y
+                s[q, :] = sn[:, None] * x + c[:, None] * y
+                x, y = s[:, p].copy(), s[:, q].copy()
+                s[:, p] = c[None, :] * x - sn[None, :] * y
+                s[:, q] = sn[None, :] * x + c[None, :] * y
+                s[p, p], s[q, q] = app - t * apq, aqq + t * apq
+                s[p, q] = s[q, p] = 0
+                x, y = v[:, p].copy(), v[:, q].copy()
+                v[:, p] = c[None, :] * x - sn[None, :] * y
+                v[:, q] = sn[None, :] * x + c[None, :] * y
+            if not rotated:
+                break
+    lam = np.diag(s).copy()
+    proj = (v.T @ rhs.astype(dtype)) / lam
+    w = v @ proj
+    big = (v * np.sqrt(dtype(m - 1) / lam)[None, :]) @ v.T
+    return big - np.eye(m, dtype=dtype) + w[:, None], sweeps
+
+
+@pytest.fixture(scope="module")
+def cases():
+    """per M: (C, rhs, {rho: [(D_ref, w_ref, kappa) per node]}) -- computed once, shared, never changed"""
+    out = {}
+    for m in MEMBERS:
+        gram, rhs = node_inputs(m)
+        out[m] = (gram, rhs, {rho: [reference(gram[b], rhs[b], rho) for b in range(6)] for rho in RHOS})
+    return out
+
+
+# ---- 1. against the definition ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("members", MEMBERS)
+def test_against_the_definition(members, cases):
+    """Largest GPU error observed on an MI355X, over every M, rho and node kind, after the float term 2^-23 |D_ref| is taken
+    off, in units of M 2^-53 kappa (sqrt(rho) + max |w_ref|): 0.000 -- the tolerance allows 64, and none of it was needed:
+    every difference lay within the float term, the largest at 0.497 of its whole tolerance (the half ulp of the one
+    rounding to float the device makes).  tools/ensemble_etkf_timing.py records the same figure at 4096 nodes of real
+    Gram matrices: 0.003 units."""
+    gram, rhs, refs = cases[members]
+    worst, share = 0.0, 0.0
+    with solver(14, members) as s:
+        for rho in RHOS:
+            d, status = s.etkf_increments(gram, rhs, rho=rho)
+            assert d.dtype == F32 and d.shape == (6, members, members) and status.dtype == np.int32
+            assert (status == 0).all(), status
+            for b in range(6):
+                d_ref, w_ref, kappa = refs[rho][b]
+                err = np.abs(d[b].astype(np.float64) - d_ref)
+                over = float(((err - 2.0 ** -23 * np.abs(d_ref)) / unit(w_ref, kappa, members, rho)).max())
+                part = float((err / np.maximum(tolerance(d_ref, w_ref, kappa, members, rho), 1e-300)).max())
+                worst, share = max(worst, over), max(share, part)
+                print("M=%d rho=%g %s: %.3f units, %.3f of the tolerance" % (members, rho, KINDS[b], over, part))
+                assert (err <= tolerance(d_ref, w_ref, kappa, members, rho)).all(), (members, rho, KINDS[b], over)
+            if rho == 1.0:
+                assert (d[5].view(np.uint32) == 0).all(), "C = 0, rhs = 0, rho = 1: every entry +0"
+    print("M=%d: worst %.3f units of 64; the largest error is %.3f of its tolerance" % (members, worst, share))
+
+
+
+def test_rho_one_and_a_centred_gram_give_the_textbook_increment(cases):
+    """rule 4 of the header: for C 1 = 0, rhs . 1 = 0 and rho = 1, D = 1 1^T / M + A (W + w 1^T) - I"""
+    m = 9
+    gram, rhs, refs = cases[m]
+    with solver(14, m) as s:
+        d, _ = s.etkf_increments(gram[:4], rhs[:4])
+    for b in range(4):
+        lam, v = np.linalg.eigh((m - 1) * np.eye(m) + gram[b])
+        w = v @ ((v.T @ rhs[b]) / lam)
+        big = v @ np.diag(np.sqrt((m - 1) / lam)) @ v.T
+        a = np.eye(m) - np.ones((m, m)) / m
+        want = np.ones((m, m)) / m + a @ (big + w[:, None]) - np.eye(m)
+        d_ref, w_ref, kappa = refs[1.0][b]
+        assert (np.abs(d[b] - want) <= 2 * tolerance(d_ref, w_ref, kappa, m, 1.0)).all(), KINDS[b]
+
+
+# ---- 2. reproducibility ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("members", [3, 64])
+def test_the_same_bits_whatever_the_batch(members, cases):
+    gram, rhs, _ = cases[members]
+    rng = np.random.default_rng(7)
+    pick = np.concatenate([np.arange(6), rng.integers(0, 6, 294)])
+    rng.shuffle(pick)
+    with solver(14, members) as s, solver(14, members) as other:
+        base, _ = s.etkf_increments(gram, rhs, rho=1.1)
+        many, status = s.etkf_increments(gram[pick], rhs[pick], rho=1.1)            # 300 blocks: more than the chip has CUs
+        assert (status == 0).all()
+        assert np.array_equal(many.view(np.uint32), base[pick].view(np.uint32)), "every copy has its original's bytes"
+        for b in range(6):
+            one, _ = s.etkf_increments(gram[b:b + 1], rhs[b:b + 1], rho=1.1)
+            assert np.array_equal(one.view(np.uint32), base[b:b + 1].view(np.uint32)), "a batch of one"
+        again, _ = s.etkf_increments(gram[pick], rhs[pick], rho=1.1)
+        assert np.array_equal(again.view(np.uint32), many.view(np.uint32)), "a second call"
+        far, _ = other.etkf_increments(gram[pick], rhs[pick], rho=1.1)
+        assert np.array_equal(far.view(np.uint32), many.view(np.uint32)), "a second context"
+        shaped, st = s.etkf_increments(gram[pick].reshape(20, 15, members, members), rhs[pick].reshape(20, 15, members), rho=1.1)
+        assert shaped.shape == (20, 15, members, members) and st.shape == (20, 15)
+        assert np.array_equal(shaped.reshape(many.shape).view(np.uint32), many.view(np.uint32))
+
+
+# ---- 3. statuses and refusals ----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("members", [3, 33])
+def test_statuses(members, cases):
+    gram, rhs, _ = cases[members]
+    with solver(14, members) as s:
+        base, _ = s.etkf_increments(gram, rhs)
+        # empty nodes: not read (NaN and all), status 1, +0 bits
+        g, r = gram.copy(), rhs.copy()
+        counts = np.array([3, 0, 5, 0, 1, 0], np.int32)
+        g[1], r[3] = np.nan, np.inf
+        d, status = s.etkf_increments(g, r, counts=counts)
+        assert status.tolist() == [0, 1, 0, 1, 0, 1]
+        for b in range(6):
+            if counts[b]:
+                assert np.array_equal(d[b].view(np.uint32), base[b].view(np.uint32)), b
+            else:
+                assert (d[b].view(np.uint32) == 0).all(), b
+        # only k <= m is read: garbage below the diagonal changes nothing
+        g = gram.copy()
+        g[:, np.tril_indices(members, -1)[0], np.tril_indices(members, -1)[1]] = np.nan
+        d, status = s.etkf_increments(g, rhs)
+        assert (status == 0).all() and np.array_equal(d.view(np.uint32), base.view(np.uint32))
+        # built to fail: w overflows float (rhs of 1e300); an eigenvalue that is not positive (a large negative diagonal)
+        g, r = gram.copy(), rhs.copy()
+        r[1] = 1e300
+        g[3] = gram[3] - 1e12 * np.eye(members)
+        d, status = s.etkf_increments(g, r)
+        assert status.tolist() == [0, 2, 0, 2, 0, 0]
+        for b in range(6):
+            if status[b]:
+                assert (d[b].view(np.uint32) == 0).all(), b
+            else:
+                assert np.array_equal(d[b].view(np.uint32), base[b].view(np.uint32)), "a failed node poisons no neighbour"
+
+
+def test_refusals(cases):
+    from fluidsimulationcuda_amd import capi
+    L = capi.lib()
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
+    g = lambda a: a.ctypes.data_as(dp)
+    f = lambda a: a.ctypes.data_as(capi._MF)
+
+    def refused(rc, *words):
+        assert rc == capi.E_INVALID
+        msg = L.fluid_last_error()
+        assert b"fluid_etkf_increments" in msg
+        for w in words:
+            assert w in msg, msg
+
+    m = 3
+    gram, rhs, _ = cases[m]
+    gram, rhs = np.ascontiguousarray(gram[:2]), np.ascontiguousarray(rhs[:2])
+    out, st = np.full((2, m, m), 7.0, F32), np.full(2, 7, np.int32)
+    with solver(14, m) as s:
+        call = lambda nodes=2, gm=gram, r=rhs, counts=None, rho=1.0, o=out, h=s._h: L.fluid_etkf_increments(
+            h, nodes, None if gm is None else g(gm), None if r is None else g(r), None if counts is None else counts.ctypes.data_as(ip),
+            rho, None if o is None else f(o), st.ctypes.data_as(ip))
+        refused(call(gm=None, h=None), b"gram")
+        refused(call(r=None, h=None), b"rhs")
+        refused(call(o=None, h=None), b"increments")
+        refused(call(h=None), b"null context")
+        refused(call(nodes=0), b"nodes = 0", b"%d" % capi.LATTICE_MAX_NODES)
+        refused(call(nodes=capi.LATTICE_MAX_NODES + 1), b"%d" % (capi.LATTICE_MAX_NODES + 1))
+        for rho in (0.0, -1.0, float("nan"), float("inf")):
+            refused(call(rho=rho), b"rho")
+        bad = gram.copy()
+        bad[1, 0, 2] = np.nan
+        refused(call(gm=bad), b"node 1", b"k = 0", b"m = 2")
+        assert call(gm=bad, counts=np.array([1, 0], np.int32)) == capi.OK          # an empty node is not read
+        out[:], st[:] = 7.0, 7
+        badr = rhs.copy()
+        badr[0, 1] = np.inf
+        refused(call(r=badr), b"rhs", b"node 0", b"k = 1")
+        assert (out == 7.0).all() and (st == 7).all()
+    with solver(14, 1) as s:
+        one = np.ones((1, 1, 1))
+        refused(L.fluid_etkf_increments(s._h, 1, g(one), g(one[0]), None, 1.0, f(out), None), b"1 members", b"below 2")
+    with solver(6, capi.TRANSFORM_MAX_MEMBERS + 1) as s:
+        big = np.zeros((1, 65, 65))
+        room = np.zeros((65, 65), F32)
+        refused(L.fluid_etkf_increments(s._h, 1, g(big), g(big[0]), None, 1.0, f(room), None), b"65", b"64")
+    with F().FluidSolver(14, rank=0, nranks=2) as s:
+        one = np.ones((1, 1, 1))
+        refused(L.fluid_etkf_increments(s._h, 1, g(one), g(one[0]), None, 1.0, f(out), None), b"slab")
+
+
+# ---- 4. / 7. the fused call against its definition; nothing else moved -------------------------------------------------------------
+def start_fields(n, members, rng):
+    w = n + 2
+    i, j = np.mgrid[0:w, 0:w]
+    bump = lambda ci, cj, r: np.exp(-((i - ci) ** 2 + (j - cj) ** 2) / (2.0 * r * r))
+    out = {}
+    out["dens"] = np.stack([bump(rng.uniform(8, 22), rng.uniform(8, 22), rng.uniform(3, 6)) * rng.uniform(0.5, 2.0)
+                            for _ in range(members)]).astype(F32)
+    for name in ("u", "v"):
+        out[name] = rng.uniform(-1.0, 1.0, (members, w, w)).astype(F32)
+    for name in ("u_prev", "v_prev", "dens_prev"):
+        out[name] = rng.uniform(0.0, 0.5, (members, w, w)).astype(F32)
+    return out
+
+
+def network(rng, p=40):
+    """points clustered in rows 6 .. 28 and columns 1 .. 22: with c = 6 the nodes on row -8 see none"""
+    return rng.uniform(1.0, 22.0, p).astype(F32), rng.uniform(6.0, 28.0, p).astype(F32)
+
+
+def composed(s, field, shape, origin, step, c, obs, inv_sigma, rho, fields, counts_override=None):
+    """the definition: the three existing calls; returns (D, status, counts)"""
+    gram, rhs, dd, counts = s.observation_gram_lattice(field, shape, origin, step, c, obs=obs, inv_sigma=inv_sigma, centre=True)
+    if counts_override is not None:
+        counts = counts_override(gram, rhs, counts)
+    d, status = s.etkf_increments(gram, rhs, counts=counts, rho=rho)
+    s.transform_lattice(d, origin, step, fields=fields)
+    return d, status, counts
+
+
+def same_members(a, b, names, what):
+    for name in names:
+        x, y = a.download_members(name), b.download_members(name)
+        assert np.array_equal(x.view(np.uint32), y.view(np.uint32)), "%s: %s" % (what, name)
+
+
+@pytest.mark.parametrize("storage", [0, 1])
+@pytest.mark.parametrize("members", [2, 9, 64])
+def test_the_fused_call_is_the_three_calls(members, storage):
+    from fluidsimulationcuda_amd import capi
+    n = 30
+    rng = np.random.default_rng(100 * members + storage)
+    fields = start_fields(n, members, rng)
+    cols, rows = network(rng)
+    inv_sigma = rng.uniform(2.0, 8.0, cols.size).astype(F32)
+    y = rng.uniform(0.2, 1.5, cols.size).astype(F32)
+    arena = capi.lib().fluid_arena_bytes_ensemble(n, storage, members)
+    with solver(n, members, storage) as a, solver(n, members, storage) as b:
+        for s in (a, b):
+            s.upload_members(**fields)
+            s.step(2, use_sources=True)                    # fp16: the pressure scale is live; the sources are marked zero
+            s.set_observation_points(cols, rows)
+        for shape, origin, step, c, rho, listed in (((3, 3), (-8, 0), 16, 6.0, 1.1, ("dens", "u", "v")),
+                                                    ((1, 1), (13, 9), 8, 6.0, 1.0, ("u",)),
+                                                    ((3, 3), (-8, 0), 16, 6.0, 2.0, ("v", "u_prev"))):
+            what = "M=%d storage=%d lattice %s fields %s" % (members, storage, shape, listed)
+            keep = [name for name in capi.FIELD_NAMES if name not in listed]
+            before = {name: a.download_members(name) for name in keep}
+            for s in (a, b):
+                for name in keep:
+                    s.download_members(name)               # (the twin settles what `before` settled)
+            a.analyse_lattice("dens", shape, origin, step, c, y, inv_sigma=inv_sigma, rho=rho, fields=listed, wait=False)
+            d, status, counts = composed(b, "dens", shape, origin, step, c, y, inv_sigma, rho, listed)
+            got = a.analyse_status()
+            want = {"solved": int((status == 0).sum()), "empty": int((status == 1).sum()), "failed": int((status == 2).sum())}
+            assert got == want, what
+            if shape == (3, 3):
+                assert want["empty"] >= 3 and want["solved"] >= 2 and (counts[0] == 0).all(), counts
+            assert want["failed"] == 0 and np.abs(d).max() > 1e-4
+            same_members(a, b, MAIN, what)
+            for name in keep:                              # 7. a field that is not listed keeps its bytes
+                assert np.array_equal(a.download_members(name).view(np.uint32), before[name].view(np.uint32)), (what, name)
+            changed = [name for name in listed
+                       if not np.array_equal(a.download_members(name).view(np.uint32), fields[name].view(np.uint32))]
+            assert changed == list(listed)
+        assert capi.lib().fluid_arena_bytes_ensemble(n, storage, members) == arena
+        for s in (a, b):
+            s.step(1)
+        same_members(a, b, ("u", "v", "dens"), "a step after the analysis")
+
+
+def test_an_analysis_without_a_point_in_reach_keeps_every_bit():
+    n, members = 30, 3
+    rng = np.random.default_rng(5)
+    fields = start_fields(n, members, rng)
+    cols, rows = np.array([2.0, 3.5], F32), np.array([2.0, 4.0], F32)
+    from fluidsimulationcuda_amd import capi
+    L = capi.lib()
+    with solver(n, members) as s:
+        assert L.fluid_analyse_lattice_status(s._h, None, None, None) == capi.E_INVALID
+        assert b"fluid_analyse_lattice_status" in L.fluid_last_error()
+        s.upload_members(**fields)
+        s.set_observation_points(cols, rows)
+        before = {name: s.download_members(name) for name in MAIN}
+        s.analyse_lattice("dens", (2, 2), (24, 24), 8, 2.0, np.ones(2, F32))        # every node is farther than 2c from both points
+        assert s.analyse_status() == {"solved": 0, "empty": 4, "failed": 0}
+        for name in MAIN:
+            assert np.array_equal(s.download_members(name).view(np.uint32), before[name].view(np.uint32)), name
+
+
+# ---- 5. a poisoned point ---------------------------------------------------------------------------------------------------------
+def lower_node(q, nodes, step):
+    """rule 2 of the lattice update: the lower node of the lattice cell an index falls in"""
+    return 0 if nodes == 1 or q <= 0 else nodes - 2 if q >= (nodes - 1) * step else q // step
+
+
+def test_a_poisoned_point():
+    """The host route refuses a non-finite operand outright (the header lists it), so the composed twin does what a caller
+    has to do: it keeps the background at the nodes whose operands are not finite (count 0), having seen the refusal.
+    The fused route ends those nodes as failed on its own.  Both store nothing there: the bytes agree."""
+    n, members = 30, 9
+    shape, origin, step, c = (5, 5), (0, 0), 8, 3.0
+    rng = np.random.default_rng(55)
+    fields = start_fields(n, members, rng)
+    cols, rows = rng.uniform(1.0, 30.0, 60).astype(F32), rng.uniform(1.0, 30.0, 60).astype(F32)
+    cols[0], rows[0] = 14.25, 13.5                         # the point to poison: within 6 cells of the nodes on cells (16, 16) and (8, 16)
+    y = rng.uniform(0.2, 1.5, cols.size).astype(F32)
+    poisoned = {k: v.copy() for k, v in fields.items()}
+    poisoned["dens"][1, 14, 15] = np.nan                   # member 1, one tap of that point's stencil
+    listed = ("dens", "u", "v")
+    with solver(n, members) as a, solver(n, members) as b, solver(n, members) as clean:
+        for s, data in ((a, poisoned), (b, poisoned), (clean, fields)):
+            s.upload_members(**data)
+            s.set_observation_points(cols, rows)
+        a.analyse_lattice("dens", shape, origin, step, c, y, fields=listed)
+        clean.analyse_lattice("dens", shape, origin, step, c, y, fields=listed)
+        gram, rhs, _, counts = b.observation_gram_lattice("dens", shape, origin, step, c, obs=y, centre=True)
+        bad = ~np.isfinite(gram).all(axis=(2, 3))
+        assert bad[2, 2] and bad[1, 2] and bad.sum() <= 4
+        with pytest.raises(F().capi.FluidError, match="fluid_etkf_increments.*not finite"):
+            b.etkf_increments(gram, rhs, counts=counts)
+        d, status, _ = composed(b, "dens", shape, origin, step, c, y, None, 1.0, listed,
+                                counts_override=lambda g, r, n_: np.where(bad, 0, n_).astype(np.int32))
+        assert ((status == 1) == (bad | (counts == 0))).all()
+        st = a.analyse_status()
+        assert st["failed"] == int(bad.sum()) and st["empty"] == int((counts == 0).sum())
+        assert st == {**clean.analyse_status(), "failed": st["failed"], "solved": st["solved"]}
+        same_members(a, b, MAIN, "poisoned: fused against composed")
+        # cells on a failed node keep their bits; cells none of whose corners failed are the clean run's
+        w = n + 2
+        untouched = np.zeros((w, w), bool)
+        for i in range(w):
+            for j in range(w):
+                ra, cb = lower_node(i - origin[0], shape[0], step), lower_node(j - origin[1], shape[1], step)
+                untouched[i, j] = not bad[ra:ra + 2, cb:cb + 2].any()
+        untouched[14, 15] = False                          # (the NaN itself)
+        assert untouched.sum() > w * w // 4
+        for name in listed:
+            got, want, was = a.download_members(name), clean.download_members(name), poisoned[name]
+            assert np.array_equal(got[:, untouched].view(np.uint32), want[:, untouched].view(np.uint32)), name
+            for ra, cb in zip(*np.nonzero(bad)):
+                i, j = origin[0] + ra * step, origin[1] + cb * step
+                assert np.array_equal(got[:, i, j].view(np.uint32), was[:, i, j].view(np.uint32)), (name, i, j)
+
+
+# ---- 6. the analysis does its job --------------------------------------------------------------------------------------------------
+def test_the_analysis_moves_the_mean_towards_the_observations():
+    """A 1 x 1 lattice with every weight non-zero: the same D everywhere and H linear, so the ETKF mean minimises
+    (M - 1) |w|^2 + |d - Y w|^2 and dd_after <= dd_before - (M - 1) |w|^2 -- guaranteed, not tuned; the roundings in play are
+    2^-24 relative."""
+    n, members = 30, 9
+    shape, origin, step, c = (1, 1), (16, 16), 8, 40.0
+    rng = np.random.default_rng(6)
+    fields = start_fields(n, members, rng)
+    cols, rows = rng.uniform(4.0, 27.0, 30).astype(F32), rng.uniform(4.0, 27.0, 30).astype(F32)
+    inv_sigma = np.full(30, 10.0, F32)
+    with solver(n, members) as s:
+        s.upload_members(**fields)
+        s.set_observation_points(cols, rows)
+        y = (s.observe("dens").mean(axis=0) + 0.5).astype(F32)              # five sigma from the ensemble mean
+        gram, rhs, dd, counts = s.observation_gram_lattice("dens", shape, origin, step, c, obs=y, inv_sigma=inv_sigma)
+        assert counts[0, 0] == 30
+        d, status = s.etkf_increments(gram, rhs, counts=counts)
+        assert status[0, 0] == 0
+        wk = d[0, 0].astype(np.float64).sum(axis=1) / members
+        drop = (members - 1) * float(wk @ wk)
+        assert drop >= 0.01 * dd[0, 0], (drop, dd[0, 0])                     # the precondition
+        s.analyse_lattice("dens", shape, origin, step, c, y, inv_sigma=inv_sigma, fields=("dens",))
+        assert s.analyse_status() == {"solved": 1, "empty": 0, "failed": 0}
+        _, _, dd_after, _ = s.observation_gram_lattice("dens", shape, origin, step, c, obs=y, inv_sigma=inv_sigma)
+        print("dd %.6g -> %.6g; guaranteed drop %.6g" % (dd[0, 0], dd_after[0, 0], drop))
+        assert dd_after[0, 0] < dd[0, 0]
+
+
+def test_refusals_of_the_fused_call():
+    from fluidsimulationcuda_amd import capi
+    L = capi.lib()
+    f = lambda a: a.ctypes.data_as(capi._MF)
+    ints = lambda *v: (C.c_int * len(v))(*v)
+
+    def refused(rc, *words):
+        assert rc == capi.E_INVALID
+        msg = L.fluid_last_error()
+        assert b"fluid_analyse_lattice" in msg
+        for w in words:
+            assert w in msg, msg
+
+    n, members = 30, 3
+    rng = np.random.default_rng(8)
+    fields = start_fields(n, members, rng)
+    y = np.ones(2, F32)
+    with solver(n, members) as s, solver(n, members) as twin:
+        for c in (s, twin):
+            c.upload_members(**fields)
+            c.step(1, use_sources=True)
+        call = lambda field=2, obs=y, sigma=None, shape=(2, 2), step=8, hw=4.0, rho=1.0, ids=ints(0, 2), k=2, h=s._h: L.fluid_analyse_lattice(
+            h, field, None if obs is None else f(obs), None if sigma is None else f(sigma), shape[0], shape[1], 0, 0, step, hw, rho, ids, k)
+        refused(call(obs=None, h=None), b"obs")
+        refused(call(ids=None, h=None), b"fields")
+        refused(call(h=None), b"null context")
+        refused(call(), b"no observation network")
+        s.set_observation_points(np.array([3.0, 9.0], F32), np.array([4.0, 8.0], F32))
+        refused(call(field=12), b"bad field id")
+        refused(call(ids=ints(0, 0)), b"listed twice")
+        refused(call(k=0), b"nfields")
+        refused(call(shape=(0, 2)), b"nodes_row")
+        refused(call(shape=(65, 64)), b"FLUID_LATTICE_MAX_NODES")
+        refused(call(step=12), b"step")
+        refused(call(hw=0.0), b"c = 0")
+        refused(call(rho=0.0), b"rho")
+        refused(call(sigma=np.array([1.0, np.inf], F32)), b"inv_sigma[1]")
+        same_members(s, twin, MAIN, "the refusals changed nothing")
+        assert call() == capi.OK
+    with solver(n, 1) as s:
+        s.set_observation_points(np.array([3.0], F32), np.array([4.0], F32))
+        refused(L.fluid_analyse_lattice(s._h, 2, f(y), None, 1, 1, 0, 0, 8, 4.0, 1.0, ints(2), 1), b"below 2")
+    with F().FluidSolver(14, rank=0, nranks=2) as s:
+        refused(L.fluid_analyse_lattice(s._h, 2, f(y), None, 1, 1, 0, 0, 8, 4.0, 1.0, ints(2), 1), b"slab")
