@@ -9,6 +9,7 @@ import inspect
 import re
 
 import numpy as np
+import pytest
 
 from conftest import ROOT
 
@@ -123,3 +124,28 @@ def test_the_model_the_arbiter_and_the_sweep_cap():
                     assert err <= 4.0, (name, m, rho, E.KINDS[b], err)
     print("sweeps needed: %d; worst float64 error: %.2f units" % (most, worst))
     assert capi.ETKF_MAX_SWEEPS == max(16, 2 * most), (most, capi.ETKF_MAX_SWEEPS)
+
+
+@pytest.mark.parametrize("padded", [2, 4, 8, 16, 32, 64])
+def test_the_model_at_every_member_count(padded):
+    """The round-robin ordering is another one for every M, so the float64 model is run at every M in 2 .. 64 (one instance
+    per padded count, as in tests/test_gpu_member_counts.py) -- on the two node kinds that set the maxima of the full sweep,
+    "P=5" and "P=40 scale 4", and rho in (1, 2).  (All six kinds and all three rho, run once by hand: at most 14 sweeps,
+    which "P=40 scale 4" needs at M = 56 and at M = 64, and at most 1.25 units from eigh, at M = 3.)  The sweeps the model needs, the
+    last one included, stay within half of FLUID_ETKF_MAX_SWEEPS, and it stays within the 4 units of M 2^-53 sqrt(rho) kappa
+    of eigh that the test above asserts at its own counts: what the GPU test of every M rests its tolerance on."""
+    import test_gpu_etkf as E
+    from fluidsimulationcuda_amd import capi
+    assert capi.TRANSFORM_MAX_MEMBERS == 64
+    most, worst = (0, ()), (0.0, ())
+    for m in range(padded // 2 + 1, padded + 1):
+        gram, rhs = E.node_inputs(m)
+        for rho in (1.0, 2.0):
+            for b in (0, 1):
+                d_ref, _, kappa = E.reference(gram[b], rhs[b], rho)
+                d64, sweeps = E.jacobi_model(gram[b], rhs[b], rho)
+                err = float(np.abs(d64 - d_ref).max()) / (m * E.U * np.sqrt(rho) * kappa)
+                most, worst = max(most, (sweeps, (m, rho, E.KINDS[b]))), max(worst, (err, (m, rho, E.KINDS[b])))
+                assert sweeps <= capi.ETKF_MAX_SWEEPS // 2, (m, rho, E.KINDS[b], sweeps)
+                assert err <= 4.0, (m, rho, E.KINDS[b], err)
+    print("most sweeps: %d at %s; worst distance from eigh: %.2f units at %s" % (most + worst))

@@ -23,7 +23,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 F32 = np.float32
 MAIN = ("u", "v", "dens", "u_prev", "v_prev", "dens_prev")
-MEMBERS = [2, 3, 9, 33, 64]
+MEMBERS = [2, 3, 9, 17, 32, 33, 64]
 RHOS = [1.0, 1.1, 2.0]
 KINDS = ("P=5", "P=40 scale 4", "P=200 scale 30", "P=64 scale 300", "diagonal", "zero")
 U = 2.0 ** -53

@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 F32 = np.float32
 SIZES = [1, 6, 13, 30, 61, 254]             # rows shorter and longer than a wave, W % 4 != 0; 254: more than one block and
                                             # more than one partial per fold lane
-MEMBERS = [1, 2, 3, 5, 8, 9, 33, 64]        # every padded count and the counts just past one
+MEMBERS = [1, 2, 3, 5, 8, 9, 17, 32, 33, 64]   # every padded count and the counts just past one
 COARSE = np.array([-1, -0.5, -0.25, 0.0, -0.0, 0.25, 0.5, 1], F32)       # as in tests/test_gpu_lazy_state.py
 MAIN = ("u", "v", "dens", "u_prev", "v_prev", "dens_prev")
 COUNTS = ("sweeps", "solves", "jacobi_launches", "jacobi_field_launches", "pressure_sweeps")
@@ -174,7 +174,7 @@ def test_small_spread_on_a_large_mean():
 
 # ---- 3. general data within the summation bound ------------------------------------------------------------------------------------
 @pytest.mark.parametrize("storage", [0, 1], ids=["f32", "f16"])
-@pytest.mark.parametrize("n,members", [(61, 5), (30, 9), (254, 3), (13, 33), (30, 64)])
+@pytest.mark.parametrize("n,members", [(61, 5), (30, 9), (254, 3), (13, 33), (30, 64), (30, 32), (61, 17)])
 def test_general_data_within_the_summation_bound(n, members, storage):
     rng = np.random.default_rng(3000 * storage + 10 * n + members)
     w = n + 2
@@ -195,7 +195,7 @@ def test_general_data_within_the_summation_bound(n, members, storage):
 
 # ---- 4. determinism --------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("storage", [0, 1], ids=["f32", "f16"])
-@pytest.mark.parametrize("n,members", [(61, 33), (254, 64), (254, 5)])
+@pytest.mark.parametrize("n,members", [(61, 33), (254, 64), (254, 5), (30, 32), (61, 17)])
 def test_the_same_bits_every_time(n, members, storage):
     rng = np.random.default_rng(4000 * storage + n + members)
     w = n + 2

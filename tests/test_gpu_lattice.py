@@ -16,7 +16,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
-MEMBERS = [1, 2, 3, 5, 8, 9, 33, 64]        # every padded count 1, 2, 4 .. 64, and the counts just past a power of two
+MEMBERS = [1, 2, 3, 5, 8, 9, 17, 32, 33, 64]   # every padded count 1, 2, 4 .. 64, and the counts just past a power of two
 MAIN = ("u", "v", "dens", "u_prev", "v_prev", "dens_prev")
 DT = 0.016
 # (N, (nodes_row, nodes_col), step, (row0, col0)): W = 3, 8, 15, 32, 63 -- no multiple of a patch side but 8 and 32, one and
@@ -220,8 +220,8 @@ def test_the_cases_reach_every_branch_of_rule_2():
 
 
 def cases_of(members):
-    """every member count meets every N and every lattice; the two largest counts skip every other case of the middle sizes"""
-    if members < 33:
+    """every member count meets every N and every lattice; the three largest counts skip every other case of the middle sizes"""
+    if members < 32:
         return CASES
     return [c for k, c in enumerate(CASES) if c[0] in (1, 61) or k % 2 == (members == 64)]
 

@@ -19,7 +19,7 @@ F32 = np.float32
 COARSE = np.array([-1, -0.5, -0.25, 0.0, -0.0, 0.25, 0.5, 1], F32)
 MAIN = ("u", "v", "dens", "u_prev", "v_prev", "dens_prev")
 COUNTS = ("sweeps", "solves", "jacobi_launches", "jacobi_field_launches", "pressure_sweeps")
-MEMBERS = [1, 2, 3, 9, 33, 64]
+MEMBERS = [1, 2, 3, 9, 17, 32, 33, 64]
 DT = 0.016
 U = 2.0 ** -53
 
@@ -353,7 +353,8 @@ def check_general(got, h, obs, sg, centre, lat, c, cols, rows, what):
 
 
 GENERAL = [(30, 9, 5000, ((3, 2), (-3, 2), 8)), (13, 33, 513, ((3, 2), (-3, 2), 8)), (30, 64, 257, ((1, 3), (15, -1), 16)),
-           (6, 3, 65, ((1, 1), (3, 3), 8)), (13, 1, 64, ((3, 2), (2, 2), 8)), (30, 2, 1, ((1, 3), (14, 9), 8)), (13, 3, 257, ((5, 5), (-9, -40), 16))]
+           (6, 3, 65, ((1, 1), (3, 3), 8)), (13, 1, 64, ((3, 2), (2, 2), 8)), (30, 2, 1, ((1, 3), (14, 9), 8)), (13, 3, 257, ((5, 5), (-9, -40), 16)),
+           (13, 32, 513, ((3, 2), (-3, 2), 8))]
 
 
 @pytest.mark.parametrize("storage", [0, 1], ids=["f32", "f16"])

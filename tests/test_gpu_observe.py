@@ -18,7 +18,7 @@ F32 = np.float32
 SIZES = [1, 6, 13, 30, 61]
 MEMBERS = [1, 2, 3, 9, 64]
 POINTS = [1, 2, 63, 64, 65, 257, 5000]      # around a wave and a block of lanes, several blocks
-GRAM_MEMBERS = [1, 2, 3, 5, 8, 9, 33, 64]   # every padded count and the counts just past one
+GRAM_MEMBERS = [1, 2, 3, 5, 8, 9, 17, 32, 33, 64]   # every padded count and the counts just past one
 GRAM_POINTS = [1, 64, 65, 513, 5000]        # less than a chunk of 64 points, a chunk and one more, more blocks than fold lanes
 COARSE = np.array([-1, -0.5, -0.25, 0.0, -0.0, 0.25, 0.5, 1], F32)
 MAIN = ("u", "v", "dens", "u_prev", "v_prev", "dens_prev")
@@ -537,7 +537,7 @@ def test_gram_exact_on_dyadic_data(members, storage):
             assert np.array_equal(a.download_members("dens").view(np.uint32), x.view(np.uint32)), "the call changed the field"
 
 
-@pytest.mark.parametrize("members", [2, 64])
+@pytest.mark.parametrize("members", [2, 32, 64])
 def test_gram_exact_with_several_chunks_per_block(members):
     """more chunks of 64 points than the grid has blocks (512 at 64 members, 1024 below): a block strides over its chunks"""
     rng = np.random.default_rng(5500 + members)
@@ -561,7 +561,7 @@ def test_gram_exact_with_several_chunks_per_block(members):
 
 # ---- 6. general data within the summation bound --------------------------------------------------------------------------------
 @pytest.mark.parametrize("storage", [0, 1], ids=["f32", "f16"])
-@pytest.mark.parametrize("n,members,p", [(61, 5, 513), (30, 9, 5000), (13, 33, 257), (30, 64, 513), (6, 3, 65), (13, 1, 64)])
+@pytest.mark.parametrize("n,members,p", [(61, 5, 513), (30, 9, 5000), (13, 33, 257), (13, 32, 257), (30, 64, 513), (6, 3, 65), (13, 1, 64)])
 def test_gram_general_data_within_the_summation_bound(n, members, p, storage):
     rng = np.random.default_rng(6000 * storage + 10 * n + members)
     w = n + 2

@@ -13,7 +13,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 F32 = np.float32
 SIZES = [1, 6, 13, 30, 61]                  # W % 4 != 0, rows shorter and longer than a wave
-MEMBERS = [1, 2, 3, 5, 8, 9, 33, 64]        # every padded count 1, 2, 4 .. 64, and the counts just past a power of two
+MEMBERS = [1, 2, 3, 5, 8, 9, 17, 32, 33, 64]   # every padded count 1, 2, 4 .. 64, and the counts just past a power of two
 MAIN = ("u", "v", "dens", "u_prev", "v_prev", "dens_prev")
 DT = 0.016
 
