@@ -144,6 +144,8 @@ SIGNATURES = {
     "fluid_etkf_increments": [_ctx, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i), _f, _MF, C.POINTER(_i)],
     "fluid_analyse_lattice": [_ctx, _i, _MF, _MF, _i, _i, _i, _i, _i, _f, _f, C.POINTER(_i), _i],
     "fluid_analyse_lattice_status": [_ctx, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
+    "fluid_member_spread": [_ctx, C.POINTER(_i), _i, C.c_void_p, C.c_size_t],
+    "fluid_relax_spread": [_ctx, C.POINTER(_i), _i, C.c_void_p, C.c_size_t, _f],
     "fluid_set_jacobi_variant": [_ctx, _i],
     "fluid_division_mode": [_ctx, _f, _f, C.POINTER(_i)],
     "fluid_autotune_pending": [_ctx, C.POINTER(_i)],

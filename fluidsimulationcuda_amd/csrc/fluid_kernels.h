@@ -156,6 +156,14 @@ void launch_member_moments(hipStream_t s, int st, const void* x, int pitch, int 
 // Per cell over the members (every row and column, ghosts included): mean and population variance as float fields in
 // the layout of a field; their pad columns are not written.  One launch; the members are walked inside the kernel.
 void launch_ensemble_stats(hipStream_t s, int st, const void* x, int pitch, int n, Members mb, float* mean, float* var);
+// Relaxation to prior spread (include/fluid_amd.h "relaxation to prior spread"), mb.count >= 2, any count.  `out`, `prior`: a
+// dense (n + 2)^2 float array, row-major with the ghost ring, aligned to 4 bytes.  `inv`, `scale`: as for
+// launch_transform_members_local.  spread: out = (float)sqrt(q / (mb.count - 1)), q the second chain of launch_ensemble_stats
+// over widen(x) * inv.  relax: every cell with q != 0 and f = 1 + alpha * (prior - sa) / sa != 1 becomes narrow((float)(mean_d +
+// f * d_m)) times scale in every member, in place; the other cells keep their bits.  One launch each; pads are not touched.
+void launch_member_spread(hipStream_t s, int st, const void* x, int pitch, int n, Members mb, float inv, float* out);
+void launch_relax_spread(hipStream_t s, int st, void* x, int pitch, int n, Members mb, float inv, float scale, const float* prior,
+                         float alpha);
 // All mb.count members of a field (x: the first of them) <-> a dense float array, member m of it m * dstride floats behind
 // `dense`, each the (n + 2)^2 row-major array with its ghost ring.  One launch each; pad columns are not touched.
 // pack: dense = widen(x) * inv (fp16 storage; fp32 copies the words); unpack: x = narrow(dense), to nearest even.

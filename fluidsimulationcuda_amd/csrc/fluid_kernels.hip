@@ -2320,6 +2320,254 @@ __global__ __launch_bounds__(256) void k_ensemble_stats(const S* __restrict__ x,
 }
 
 // ---------------------------------------------------------------------------
+// relaxation to prior spread (include/fluid_amd.h "relaxation to prior spread"): the per-cell sample standard deviation of a
+// field over the members as a dense float array, and the in-place rescaling of a field's anomalies towards such an array.
+// Both are k_ensemble_stats with another end: lanes cut the same way (one lane per vector of columns, vector 0 the ghost
+// column 0 alone, edge vectors masked, member bases in 64-bit scalar arithmetic, kStatsUnroll members' loads in flight),
+// the same two chains s and q in double and member order, for any member count.  Two differences in shape, both measured
+// (DESIGN.md section 9).  A vector is 4 columns in both storage types -- 16-byte accesses of float fields, 8-byte ones of
+// half fields.  And there is ONE arithmetic path: a wave nearly always holds whole vectors and a row's two edge vectors,
+// and two instantiations of the walk, as in k_ensemble_stats, make every such wave run the members twice; here only the
+// accesses branch on `whole`, an edge vector loading its valid columns one by one and computing zeros in the others.
+// The dense side is a member of a dense pack: row `row` starts row * (n + 2) floats behind the array, aligned to 4 bytes
+// only (dense4_t).  Values are read as the pack shows them, widen(x) * inv for an fp16 field held at a scale.  The
+// relaxation walks the members a third time to re-read, rescale and store them, and stores narrow(y) times the scale, as
+// k_transform_members_local does.  A cell with q == 0 or f == 1 keeps its bits: an edge vector does not store it, a whole
+// vector stores back the words it loaded for it; a lane without any other cell leaves before the third walk, and so does
+// a wave of such lanes.  No LDS, no atomics.
+// ---------------------------------------------------------------------------
+typedef float dense4_t __attribute__((ext_vector_type(4), aligned(4)));
+
+// columns per lane: 4 for both storage types (fp16: 8-byte accesses).  The 8 of k_ensemble_stats doubles the double
+// arithmetic and the registers of a lane and halves the lanes: measured, never faster
+template <typename S> struct SpreadVec { static constexpr int VW = 4; };
+
+// one member's vector as stored (16 bytes, fp16: 8; an edge vector: its valid columns one by one, the others 0)
+template <typename S> struct SpreadRaw { S c[SpreadVec<S>::VW]; };
+
+template <typename S>
+__device__ __forceinline__ SpreadRaw<S> spread_load(const S* __restrict__ p, int valid, bool whole)
+{
+    constexpr int VW = SpreadVec<S>::VW;
+    typedef S vec_t __attribute__((ext_vector_type(VW)));
+    SpreadRaw<S> r;
+    if (whole) {
+        const vec_t a = *reinterpret_cast<const vec_t*>(p);
+#pragma unroll
+        for (int e = 0; e < VW; ++e) r.c[e] = a[e];
+    } else {
+#pragma unroll
+        for (int e = 0; e < VW; ++e) r.c[e] = ((valid >> e) & 1) ? p[e] : (S)0;
+    }
+    return r;
+}
+
+// the value the pack shows
+template <typename S>
+__device__ __forceinline__ double spread_value(S c, float inv)
+{
+    if constexpr (sizeof(S) == 4) return (double)c;
+    else return (double)(keep_f32((float)c) * inv);
+}
+
+// s, then mu = s / members and q, per column of the lane's vector: the chains of stats_cell
+template <typename S>
+__device__ __forceinline__ void spread_moments(const S* __restrict__ x, size_t ms, int members, size_t at, int valid, bool whole, float inv,
+                                               double (&mu)[SpreadVec<S>::VW], double (&q)[SpreadVec<S>::VW])
+{
+    constexpr int VW = SpreadVec<S>::VW;
+    const double dm = (double)members;
+    double s[VW];
+    SpreadRaw<S> d[kStatsUnroll];
+    d[0] = spread_load<S>(x + at, valid, whole);
+#pragma unroll
+    for (int e = 0; e < VW; ++e) s[e] = spread_value<S>(d[0].c[e], inv);
+    int m = 1;
+    for (; m + kStatsUnroll <= members; m += kStatsUnroll) {
+#pragma unroll
+        for (int r = 0; r < kStatsUnroll; ++r) d[r] = spread_load<S>(x + (size_t)(m + r) * ms + at, valid, whole);
+#pragma unroll
+        for (int r = 0; r < kStatsUnroll; ++r)
+#pragma unroll
+            for (int e = 0; e < VW; ++e) s[e] = s[e] + spread_value<S>(d[r].c[e], inv);
+    }
+    for (; m < members; ++m) {
+        d[0] = spread_load<S>(x + (size_t)m * ms + at, valid, whole);
+#pragma unroll
+        for (int e = 0; e < VW; ++e) s[e] = s[e] + spread_value<S>(d[0].c[e], inv);
+    }
+#pragma unroll
+    for (int e = 0; e < VW; ++e) mu[e] = s[e] / dm;
+    d[0] = spread_load<S>(x + at, valid, whole);
+#pragma unroll
+    for (int e = 0; e < VW; ++e) { const double t = spread_value<S>(d[0].c[e], inv) - mu[e]; q[e] = t * t; }
+    m = 1;
+    for (; m + kStatsUnroll <= members; m += kStatsUnroll) {
+#pragma unroll
+        for (int r = 0; r < kStatsUnroll; ++r) d[r] = spread_load<S>(x + (size_t)(m + r) * ms + at, valid, whole);
+#pragma unroll
+        for (int r = 0; r < kStatsUnroll; ++r)
+#pragma unroll
+            for (int e = 0; e < VW; ++e) { const double t = spread_value<S>(d[r].c[e], inv) - mu[e]; q[e] = q[e] + t * t; }
+    }
+    for (; m < members; ++m) {
+        d[0] = spread_load<S>(x + (size_t)m * ms + at, valid, whole);
+#pragma unroll
+        for (int e = 0; e < VW; ++e) { const double t = spread_value<S>(d[0].c[e], inv) - mu[e]; q[e] = q[e] + t * t; }
+    }
+}
+
+// this lane's vector: false past the last one.  `at`: element 0 of the vector in a member (for vector 0 in the left pad,
+// which it skips: only element VW - 1 is valid); `dat`: the same element in a dense (n + 2)^2 array, negative for vector 0
+// of row 0 (adding a valid e brings it back)
+template <typename S>
+__device__ __forceinline__ bool spread_vector(int pitch, int n, int vecs, size_t* at, ptrdiff_t* dat, int* valid)
+{
+    constexpr int VW = SpreadVec<S>::VW;
+    const unsigned t = blockIdx.x * 256u + threadIdx.x;          // (n + 2) * vecs < 2^32 for every N the library accepts
+    if (t >= (unsigned)(n + 2) * (unsigned)vecs) return false;
+    const int row = (int)(t / (unsigned)vecs), v = (int)(t % (unsigned)vecs);
+    const int c0 = 1 + VW * (v - 1);
+    int ok = 0;
+#pragma unroll
+    for (int e = 0; e < VW; ++e)
+        if (c0 + e >= 0 && c0 + e <= n + 1) ok |= 1 << e;
+    *valid = ok;
+    *at = (size_t)row * (size_t)pitch + (size_t)(XOFF + c0);
+    *dat = (ptrdiff_t)row * (ptrdiff_t)(n + 2) + (ptrdiff_t)c0;
+    return true;
+}
+
+template <typename S>
+__device__ __forceinline__ void spread_cell(const S* __restrict__ x, size_t ms, int members, size_t at, ptrdiff_t dat, int valid, bool whole, float inv,
+                                            float* __restrict__ out)
+{
+    constexpr int VW = SpreadVec<S>::VW;
+    const double dm1 = (double)(members - 1);
+    double mu[VW], q[VW];
+    spread_moments<S>(x, ms, members, at, valid, whole, inv, mu, q);
+    float sd[VW];
+#pragma unroll
+    for (int e = 0; e < VW; ++e) sd[e] = (float)sqrt(q[e] / dm1);
+    if (whole) {
+#pragma unroll
+        for (int e = 0; e < VW; e += 4) {
+            dense4_t d;
+            d.x = sd[e]; d.y = sd[e + 1]; d.z = sd[e + 2]; d.w = sd[e + 3];
+            *reinterpret_cast<dense4_t*>(out + (dat + e)) = d;
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < VW; ++e)
+            if ((valid >> e) & 1) out[dat + e] = sd[e];
+    }
+}
+
+// total = (n + 2) * vecs work items, as k_ensemble_stats; members >= 2
+template <typename S>
+__global__ __launch_bounds__(256) void k_member_spread(const S* __restrict__ x, int pitch, int n, size_t ms, int members, int vecs, float inv,
+                                                       float* __restrict__ out)
+{
+    constexpr int VW = SpreadVec<S>::VW;
+    size_t at;
+    ptrdiff_t dat;
+    int valid;
+    if (!spread_vector<S>(pitch, n, vecs, &at, &dat, &valid)) return;
+    spread_cell<S>(x, ms, members, at, dat, valid, valid == (1 << VW) - 1, inv, out);
+}
+
+// rule 6 of the header: product and sum each rounded once, then to float, then narrowed and back at the field's scale
+template <typename S>
+__device__ __forceinline__ S relaxed(S old, float inv, float scale, double mu, double f)
+{
+#pragma clang fp contract(off)
+    const double d = spread_value<S>(old, inv) - mu;
+    const double p = __dmul_rn(f, d);
+    const float y = (float)__dadd_rn(mu, p);
+    if constexpr (sizeof(S) == 4) return y;
+    else return (S)keep_f32(as_stored<S>(y) * scale);
+}
+
+// one member's vector re-read, rescaled in the columns of `act` and stored; `act` is not 0
+template <typename S>
+__device__ __forceinline__ void relax_store(S* __restrict__ p, const SpreadRaw<S>& old, int act, bool whole, float inv, float scale,
+                                            const double (&mu)[SpreadVec<S>::VW], const double (&f)[SpreadVec<S>::VW])
+{
+    constexpr int VW = SpreadVec<S>::VW;
+    typedef S vec_t __attribute__((ext_vector_type(VW)));
+    S y[VW];
+#pragma unroll
+    for (int e = 0; e < VW; ++e) y[e] = relaxed<S>(old.c[e], inv, scale, mu[e], f[e]);
+    if (whole) {
+        vec_t v;
+#pragma unroll
+        for (int e = 0; e < VW; ++e) v[e] = ((act >> e) & 1) ? y[e] : old.c[e];
+        *reinterpret_cast<vec_t*>(p) = v;
+    } else {
+#pragma unroll
+        for (int e = 0; e < VW; ++e)
+            if ((act >> e) & 1) p[e] = y[e];
+    }
+}
+
+template <typename S>
+__device__ __forceinline__ void relax_cell(S* __restrict__ x, size_t ms, int members, size_t at, ptrdiff_t dat, int valid, bool whole, float inv,
+                                           float scale, const float* __restrict__ prior, double alpha)
+{
+#pragma clang fp contract(off)
+    constexpr int VW = SpreadVec<S>::VW;
+    const double dm1 = (double)(members - 1);
+    double mu[VW], q[VW], f[VW];
+    float sb[VW];
+    if (whole) {
+#pragma unroll
+        for (int e = 0; e < VW; e += 4) {
+            const dense4_t d = *reinterpret_cast<const dense4_t*>(prior + (dat + e));
+            sb[e] = d.x; sb[e + 1] = d.y; sb[e + 2] = d.z; sb[e + 3] = d.w;
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < VW; ++e) sb[e] = ((valid >> e) & 1) ? prior[dat + e] : 0.0f;
+    }
+    spread_moments<S>(x, ms, members, at, valid, whole, inv, mu, q);
+    int act = 0;
+#pragma unroll
+    for (int e = 0; e < VW; ++e) {
+        const double sa = sqrt(q[e] / dm1);
+        double t = (double)sb[e] - sa;
+        t = __dmul_rn(alpha, t);
+        t = t / sa;
+        f[e] = __dadd_rn(1.0, t);
+        if (((valid >> e) & 1) && q[e] != 0.0 && f[e] != 1.0) act |= 1 << e;      // (a NaN q or f is live: its cell becomes NaN)
+    }
+    if (act == 0) return;
+    int m = 0;
+    for (; m + kStatsUnroll <= members; m += kStatsUnroll) {
+        SpreadRaw<S> d[kStatsUnroll];
+#pragma unroll
+        for (int r = 0; r < kStatsUnroll; ++r) d[r] = spread_load<S>(x + (size_t)(m + r) * ms + at, valid, whole);
+#pragma unroll
+        for (int r = 0; r < kStatsUnroll; ++r) relax_store<S>(x + (size_t)(m + r) * ms + at, d[r], act, whole, inv, scale, mu, f);
+    }
+    for (; m < members; ++m) {
+        const SpreadRaw<S> d = spread_load<S>(x + (size_t)m * ms + at, valid, whole);
+        relax_store<S>(x + (size_t)m * ms + at, d, act, whole, inv, scale, mu, f);
+    }
+}
+
+template <typename S>
+__global__ __launch_bounds__(256) void k_relax_spread(S* __restrict__ x, int pitch, int n, size_t ms, int members, int vecs, float inv,
+                                                      float scale, const float* __restrict__ prior, double alpha)
+{
+    constexpr int VW = SpreadVec<S>::VW;
+    size_t at;
+    ptrdiff_t dat;
+    int valid;
+    if (!spread_vector<S>(pitch, n, vecs, &at, &dat, &valid)) return;
+    relax_cell<S>(x, ms, members, at, dat, valid, valid == (1 << VW) - 1, inv, scale, prior, alpha);
+}
+
+// ---------------------------------------------------------------------------
 // moving whole ensembles: all members of a field <-> a dense float array (include/fluid_amd.h "moving ensembles").
 // The dense side is one member after the other, each the reference's (n + 2)^2 row-major array, member m starting
 // m * dstride floats behind `dense`: always float, aligned to 4 bytes only, and the offset of a row within 16 bytes
@@ -2335,8 +2583,6 @@ __global__ __launch_bounds__(256) void k_ensemble_stats(const S* __restrict__ x,
 // download does on the host, exact); fp32 storage moves the words as they are.  unpack: x = narrow(dense), one
 // round-to-nearest-even behind the empty-asm fence (st1).
 // ---------------------------------------------------------------------------
-typedef float dense4_t __attribute__((ext_vector_type(4), aligned(4)));
-
 template <typename S, typename I>
 __device__ __forceinline__ bool member_vector(int pitch, int n, int vecs, I* at, I* dat, int* valid)
 {
@@ -3201,6 +3447,24 @@ static inline int row_vectors(int st, int n)
 {
     const int vw = 16 / (int)storage_bytes(st);
     return 1 + (n + 1 + vw - 1) / vw;
+}
+
+// vectors per row of k_member_spread / k_relax_spread: ghost column 0, then columns 1 .. n + 1 in vectors of 4 (SpreadVec)
+static inline int spread_vectors(int n) { return 1 + (n + 1 + 3) / 4; }
+
+void launch_member_spread(hipStream_t s, int st, const void* x, int pitch, int n, Members mb, float inv, float* out)
+{
+    const int vecs = spread_vectors(n);
+    FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_member_spread<S>, dim3(cdiv((unsigned)(n + 2) * (unsigned)vecs, 256)), dim3(256), 0, s,
+                                            (const S*)x, pitch, n, mb.stride, mb.count, vecs, inv, out));
+}
+
+void launch_relax_spread(hipStream_t s, int st, void* x, int pitch, int n, Members mb, float inv, float scale, const float* prior,
+                         float alpha)
+{
+    const int vecs = spread_vectors(n);
+    FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_relax_spread<S>, dim3(cdiv((unsigned)(n + 2) * (unsigned)vecs, 256)), dim3(256), 0, s, (S*)x,
+                                            pitch, n, mb.stride, mb.count, vecs, inv, scale, prior, (double)alpha));
 }
 
 void launch_pack_members(hipStream_t s, int st, const void* x, int pitch, int n, Members mb, float inv, float* dense, size_t dstride)

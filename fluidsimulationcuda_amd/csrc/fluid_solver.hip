@@ -3136,6 +3136,68 @@ int fluid_transform_members_lattice(fluid_ctx* c, const int* fields, int nfields
     return FLUID_OK;
 }
 
+// ---- relaxation to prior spread: fluid_member_spread / fluid_relax_spread ------------------------------------------------
+// (include/fluid_amd.h "relaxation to prior spread".)  The list is checked as a transform's is, without its member cap: the
+// kernels walk the members in a loop.  Every listed field is settled as pack_range settles it, a scale KEPT: the spread
+// alters nothing, and the relaxation stores at the scale, as the lattice update does.  One launch per field, no wait; the
+// launches belong to none of the timing categories.
+static int check_spread(const fluid_ctx* c, const char* call, const int* fields, int nfields, const char* name, const void* dev,
+                        size_t* stride)
+{
+    if (nfields < 1 || nfields > FLUID_NFIELDS) return fail(FLUID_E_INVALID, "%s: nfields %d outside [1, %d]", call, nfields, FLUID_NFIELDS);
+    for (int k = 0; k < nfields; ++k) {
+        if (!c->valid_field(fields[k])) return fail(FLUID_E_INVALID, "%s: bad field id %d (fields[%d])", call, fields[k], k);
+        for (int j = 0; j < k; ++j)
+            if (fields[j] == fields[k]) return fail(FLUID_E_INVALID, "%s: field %d is listed twice (fields[%d] and fields[%d])", call, fields[k], j, k);
+    }
+    TRY(refuse_slabs(c, call));                                          // (a slab context has one member: say what it is first)
+    if (c->members < 2) return fail(FLUID_E_INVALID, "%s: this context has %d member(s); a spread needs at least 2", call, c->members);
+    const size_t cells = member_cells(c);
+    if (*stride == 0) *stride = cells;
+    if (*stride < cells) return fail(FLUID_E_INVALID, "%s: field_stride %zu is below (N + 2)^2 = %zu", call, *stride, cells);
+    size_t bytes = 0;
+    if (!dense_span(cells, nfields, *stride, &bytes)) return fail(FLUID_E_INVALID, "%s: field_stride %zu is too large", call, *stride);
+    return check_device_span(c, call, name, dev, bytes);
+}
+
+int fluid_member_spread(fluid_ctx* c, const int* fields, int nfields, void* out_dev, size_t field_stride)
+{
+    const char* call = "fluid_member_spread";
+    if (!fields) return fail(FLUID_E_INVALID, "%s: null array `fields`", call);
+    if (!out_dev) return fail(FLUID_E_INVALID, "%s: null device pointer `out_dev`", call);
+    if (!c) return fail(FLUID_E_INVALID, "%s: null context", call);
+    TRY(check_spread(c, call, fields, nfields, "out_dev", out_dev, &field_stride));
+    for (int k = 0; k < nfields; ++k) {
+        const int f = fields[k];
+        const float inv = c->st != fluid::STORAGE_F32 ? 1.0f / c->field[f].fscale : 1.0f;      // as pack_range sees the field
+        TRY(materialize(c, f, /*keep_scale=*/inv != 1.0f));
+        fluid::launch_member_spread(c->stream, c->st, c->ptr(f), c->pitch, c->n, c->mb(), inv, static_cast<float*>(out_dev) + (size_t)k * field_stride);
+        HIP_TRY(hipGetLastError());
+    }
+    return FLUID_OK;
+}
+
+int fluid_relax_spread(fluid_ctx* c, const int* fields, int nfields, const void* prior_dev, size_t field_stride, float alpha)
+{
+    const char* call = "fluid_relax_spread";
+    if (!fields) return fail(FLUID_E_INVALID, "%s: null array `fields`", call);
+    if (!prior_dev) return fail(FLUID_E_INVALID, "%s: null device pointer `prior_dev`", call);
+    if (!c) return fail(FLUID_E_INVALID, "%s: null context", call);
+    if (!std::isfinite(alpha) || alpha < 0.0f) return fail(FLUID_E_INVALID, "%s: alpha = %g is not finite or is negative", call, (double)alpha);
+    TRY(check_spread(c, call, fields, nfields, "prior_dev", prior_dev, &field_stride));
+    for (int k = 0; k < nfields; ++k) {
+        const int f = fields[k];
+        const float scale = c->st != fluid::STORAGE_F32 ? c->field[f].fscale : 1.0f;           // as pack_range sees the field
+        TRY(materialize(c, f, /*keep_scale=*/scale != 1.0f));
+        fluid::launch_relax_spread(c->stream, c->st, c->ptr(f), c->pitch, c->n, c->mb(), 1.0f / scale, scale,
+                                   static_cast<const float*>(prior_dev) + (size_t)k * field_stride, alpha);
+        HIP_TRY(hipGetLastError());
+        wrote(c, f, kEverywhere);                                    // nothing owed ...
+        c->field[f].fscale = scale;                                  // ... and the scale it had: the launch stored at it
+    }
+    return FLUID_OK;
+}
+
 // The staging buffer of the bulk host copies: g = max(1, min(M, 64 MiB / member bytes)) dense members.  The 64 MiB is a
 // choice, not a measurement -- a buffer that fits the Infinity Cache beside the fields a group is packed from;
 // tools/ensemble_io_timing.py records what the bulk copies cost with it.

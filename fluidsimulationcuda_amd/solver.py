@@ -608,6 +608,50 @@ class FluidSolver:
         capi.check(capi.lib().fluid_analyse_lattice_status(self._h, *(C.byref(v) for v in n)))
         return {"solved": n[0].value, "empty": n[1].value, "failed": n[2].value}
 
+    # -- relaxation to prior spread: the per-cell ensemble standard deviation, and the anomalies rescaled towards an earlier one
+    def _spread_tensor(self, t, nfields, name):
+        """The address of an (nfields, N+2, N+2) float32 device tensor, checked: a wrong shape, type or layout is an error here."""
+        import torch
+        w = self.n + 2
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch tensor on the device, got %s" % (name, type(t).__name__))
+        if t.dtype != torch.float32 or not t.is_cuda:
+            raise ValueError("%s must be a float32 tensor on the device, got %s on %s" % (name, t.dtype, t.device))
+        if tuple(t.shape) != (nfields, w, w):
+            raise ValueError("%s must have shape (%d, %d, %d), got %s" % (name, nfields, w, w, tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError("%s must be contiguous" % name)
+        return int(t.data_ptr())
+
+    def spread(self, fields=("u", "v", "dens"), out=None, wait=True):
+        """The sample standard deviation over the members, per cell of each listed field (ghost ring included), as an
+        (nfields, N+2, N+2) float32 device tensor: sqrt(q / (members - 1)) in double, q the two-pass sum of squares of
+        ensemble_stats, on what pack would show.  One launch per field; any members >= 2.  `out`: such a tensor to fill,
+        None allocates one; `wait`: as for pack (include/fluid_amd.h, "relaxation to prior spread")."""
+        ids = [_fid(f) for f in fields]
+        if out is None:
+            import torch
+            out = torch.empty((len(ids), self.n + 2, self.n + 2), dtype=torch.float32, device="cuda")
+        address = self._spread_tensor(out, len(ids), "out")
+        self._handover(wait)
+        capi.check(capi.lib().fluid_member_spread(self._h, (C.c_int * len(ids))(*ids), len(ids), address, 0))
+        if wait:
+            self.synchronize()
+        return out
+
+    def relax_spread(self, prior, alpha, fields=("u", "v", "dens"), wait=True):
+        """Relaxation to prior spread (RTPS), in place, one launch per listed field: every cell's anomalies about the
+        ensemble mean are scaled by 1 + alpha * (prior - sd) / sd, sd the cell's spread now and `prior` what spread()
+        returned for the same fields before the analysis.  alpha = 0 changes nothing, alpha = 1 restores the prior spread;
+        cells without spread keep their bits.  `prior`: an (nfields, N+2, N+2) float32 device tensor, contiguous; `wait`: as
+        for pack (include/fluid_amd.h, "relaxation to prior spread")."""
+        ids = [_fid(f) for f in fields]
+        address = self._spread_tensor(prior, len(ids), "prior")
+        self._handover(wait)
+        capi.check(capi.lib().fluid_relax_spread(self._h, (C.c_int * len(ids))(*ids), len(ids), address, 0, float(alpha)))
+        if wait:
+            self.synchronize()
+
     def set_jacobi_variant(self, variant):
         capi.check(capi.lib().fluid_set_jacobi_variant(self._h, variant))
 

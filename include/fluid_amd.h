@@ -811,6 +811,63 @@ int fluid_analyse_lattice(fluid_ctx *ctx, int field, const float *obs, const flo
                           int row0, int col0, int step, float c, float rho, const int *fields, int nfields);
 int fluid_analyse_lattice_status(fluid_ctx *ctx, int *solved, int *empty, int *failed);
 
+/* ---- relaxation to prior spread: keeping a cycled ensemble from collapsing, per cell --------------------------------------
+ * M = fluid_members(ctx), M >= 2, W = N + 2.  The `rho` of the solve is one number for the whole grid and acts only where a
+ * node saw observations (and on the mean: one-call analysis, rule 4).  Relaxation to prior spread (RTPS, Whitaker & Hamill
+ * 2012) rescales each cell's anomalies after the analysis so that the ensemble standard deviation moves a fraction alpha of
+ * the way back to what it was before:
+ *     x'_m = mean + (1 + alpha * (sd_b - sd_a) / sd_a) * (x_m - mean)
+ * per cell, per field, over all M members.  A cycle is fluid_member_spread -> fluid_analyse_lattice -> fluid_relax_spread,
+ * nothing crossing to the host.  Both calls take ANY M >= 2 the context has: they are NOT capped at
+ * FLUID_TRANSFORM_MAX_MEMBERS, the kernels walk the members in a loop as the statistics do.
+ *
+ * `fields`: nfields distinct field ids, host memory, nfields in [1, FLUID_NFIELDS].  `out_dev` / `prior_dev`: nfields dense
+ * DEVICE arrays of W*W floats each, row-major with the ghost ring -- the layout `taper_dev` has --, the array of fields[i]
+ * starting i * field_stride floats behind the pointer; field_stride = 0: W*W; any other value must be at least W*W (the
+ * floats in between are not touched).  Alignment: 4 bytes.  One kernel launch per listed field whatever M is, enqueued on the
+ * context's stream, no wait; `fields` belongs to the caller again when the call returns, the device arrays when the stream
+ * has passed the launches.  All arithmetic below is IEEE double, every operation rounded once, none contracted.
+ *
+ * - fluid_member_spread, per listed field, per cell of the W x W array (ghost ring included; pad columns are neither read
+ *   nor written):
+ *    1. The field's lazy state is settled for all members first, as fluid_pack_members settles it: x_k is the float the
+ *       pack would show for member k right before the call -- with fp16 storage the stored value widened exactly, a
+ *       pressure scale divided back in float.  Nothing a later step or download sees is altered.
+ *    2. mean_d, d_m and q are exactly those of fluid_ensemble_stats: s = (double)x_0; s += (double)x_m in member order;
+ *       mean_d = s / (double)M; d_m = (double)x_m - mean_d; q = d_0*d_0; q += d_m*d_m in member order.
+ *    3. sd = sqrt(q / (double)(M - 1)): one division, one correctly rounded square root -- the SAMPLE standard deviation,
+ *       the normalisation of the ETKF (fluid_ensemble_stats gives the population variance, q / M).
+ *    4. out[i][j] = (float)sd.
+ *    5. A non-finite x_k makes that cell NaN and affects no other cell.
+ * - fluid_relax_spread, per listed field, per cell, in place:
+ *    1. x_k is read as rule 1 of fluid_transform_members_lattice reads it and stored by its rule 6 (rule 6 of
+ *       fluid_transform_members_local): an fp16 field held at a pressure scale KEEPS the scale, values are read divided
+ *       back and stored as narrow(y) times the scale, with the same +-inf beyond 65504 / scale.
+ *    2. mean_d, d_m and q as above.
+ *    3. q == 0: the cell keeps every bit in every member -- there is no spread to scale; a cell that is -0 everywhere stays
+ *       -0.
+ *    4. Otherwise sa = sqrt(q / (double)(M - 1)); sb = (double)prior[i][j]; t = sb - sa; t = (double)alpha * t; t = t / sa;
+ *       f = 1.0 + t.
+ *    5. f == 1.0: the cell keeps every bit in every member.  So alpha = 0 with finite priors is the identity, bit for bit.
+ *    6. Otherwise, per member m: p = f * d_m; y_d = mean_d + p -- product and sum each rounded once and NOT contracted into
+ *       one fused operation --; y = (float)y_d; the store is narrow(y).
+ *    7. A member's new value depends on mean_d, f and its own old value only; all M old values of a cell are read for
+ *       mean_d and q before any is stored.
+ *    8. A NaN result is a NaN of unspecified sign and payload.  A non-finite x_k makes that cell non-finite in every member
+ *       and touches no other cell.  A non-finite or negative prior value gives what rules 4-6 give, in that cell only.
+ *   `alpha` is finite and >= 0; values above 1 are legal.
+ * The order of operations is part of the contract: the same bits for every launch shape; no atomics, no matrix
+ * instructions, no LDS.
+ * Refusals, all FLUID_E_INVALID with a message that names the call and, where it applies, the list position, found before
+ * anything is launched or any state changes, null pointers before the context is looked at: a null `fields`, `out_dev` or
+ * `prior_dev`, a null context; nfields outside [1, FLUID_NFIELDS]; a bad field id; a field listed twice; M < 2 (the message
+ * gives M); a field_stride that is neither 0 nor at least W*W; an alpha that is not finite or is negative; a device pointer
+ * that is not device memory of the context's device, or whose whole extent, (nfields - 1) * field_stride + W*W floats, does
+ * not lie inside one allocation (asked of the runtime on the host, as for a pack); row slabs.
+ * The launches belong to none of the fluid_timing categories. */
+int fluid_member_spread(fluid_ctx *ctx, const int *fields, int nfields, void *out_dev, size_t field_stride);
+int fluid_relax_spread(fluid_ctx *ctx, const int *fields, int nfields, const void *prior_dev, size_t field_stride, float alpha);
+
 int fluid_set_jacobi_variant(fluid_ctx *ctx, int variant);
 /* How FLUID_JACOBI_TB divides by `beta` in a solve with these coefficients (diagnostic; runs the on-device proof
  * if this beta has not been seen): 0 true division, 2 double-precision reciprocal, 3 two-term float reciprocal
