@@ -136,6 +136,8 @@ SIGNATURES = {
     "fluid_observe_members": [_ctx, _i, C.c_void_p, C.c_size_t],
     "fluid_observe_members_host": [_ctx, _i, _MF],
     "fluid_observation_gram": [_ctx, _i, _i, _MF, _MF, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)],
+    "fluid_set_observation_network": [_ctx, _MF, _MF, C.POINTER(_i), _i],
+    "fluid_observation_network_fields": [_ctx, C.POINTER(C.c_uint)],
     "fluid_transform_members_local": [_ctx, C.POINTER(_i), _i, _MF, C.c_void_p, C.POINTER(_i)],
     "fluid_transform_members_lattice": [_ctx, C.POINTER(_i), _i, _MF, _i, _i, _i, _i, _i],
     "fluid_taper_gaspari_cohn": [_ctx, _f, _f, _f, C.c_void_p, C.POINTER(_i)],
@@ -173,6 +175,7 @@ MAX_MEMBERS = 21845
 COARSE_FACTORS = (1, 2, 4, 8, 16, 32, 64)
 TRANSFORM_MAX_MEMBERS = 64
 OBSERVE_MAX_POINTS = 1 << 20
+FIELD_OF_POINT = -2                  # FLUID_FIELD_OF_POINT: every point of a typed network observes its own field
 LATTICE_MAX_NODES = 4096
 LATTICE_GRAM_MAX_ENTRIES = 1 << 24
 ETKF_MAX_SWEEPS = 28

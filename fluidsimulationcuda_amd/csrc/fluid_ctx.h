@@ -149,10 +149,17 @@ struct LatticeNodeTables {
 // Observing ensembles (fluid_set_observation_points, fluid_observe_members, fluid_observation_gram): the network and the
 // scratch of its Gram call, library-owned and outside the arena (fluid_solver.hip: fluid_set_observation_points,
 // ensure_observation_gram), freed in fluid_destroy.  The network is ONE allocation of 32 bytes per point: four floats of
-// weights, the 64-bit tap offset, and one float each for the observed values and 1 / sigma a Gram call copies in.
+// weights, the 64-bit tap offset, and one float each for the observed values and 1 / sigma a Gram call copies in.  A TYPED
+// network (fluid_set_observation_network with per-point fields) has one more byte per point behind them, 33 in all: the id
+// of the field the point observes, the index into the launch's fluid::FieldSources.  `fields` is its host copy, `mask` the
+// fields some point observes; an untyped network has neither.
 struct Observation {
-    char* table = nullptr;                // [points] float4 weights | [points] tap offsets | [points] obs | [points] 1 / sigma
+    char* table = nullptr;                // [points] float4 weights | [points] tap offsets | [points] obs | [points] 1 / sigma | typed: [points] field ids
     int points = 0;
+    bool typed = false;
+    unsigned mask = 0;                    // bit f: some point observes field f (0: untyped)
+    std::vector<unsigned char> fields;    // [points], typed only
+    const unsigned char* field_of_point() const { return typed ? reinterpret_cast<const unsigned char*>(table + (size_t)points * 32) : nullptr; }
     double *d_partials = nullptr, *d_out = nullptr, *host = nullptr;    // per-block partials, the folded result, its pinned twin
     int partial_blocks = 0;               // what d_partials has room for
     const float* weight() const { return reinterpret_cast<const float*>(table); }

@@ -202,15 +202,34 @@ void launch_member_gram(hipStream_t s, int st, const void* x, int pitch, int n, 
 // Observing ensembles (include/fluid_amd.h "observing ensembles").  The network is a table in device memory, one record per
 // point: `tap`, the element offset of x[i0][j0] within a member (i0 * pitch + XOFF + j0), and four floats of `weight`
 // (16-byte aligned), {s0, s1, t0, t1} of the header's definition -- computed on the host, where the points are validated.
+// A TYPED network (include/fluid_amd.h "typed networks") has one more byte per point: `field`, the id of the field the point
+// observes, null for an untyped one.
 struct ObservationPoints {
     const unsigned long long* tap = nullptr;
     const float* weight = nullptr;
     int count = 0;
+    const unsigned char* field = nullptr;
 };
+// What the points of a typed network read, per field id: `base`, the address of member 0 of the field, and `inv`, its own
+// 1 / scale (as for the pack).  Built by the host per launch, after every field is settled; passed to the kernel by value
+// and copied into LDS at block start, where a lane looks its point's entry up once per chunk of points.  Entries of fields
+// no point observes are never read.
+constexpr int kObservedFields = 12;
+struct FieldSource {                      // (no initialisers: it lives in LDS)
+    unsigned long long base;
+    float inv, unused;                    // (16 bytes: one LDS read per lookup)
+};
+struct FieldSources {
+    FieldSource of[kObservedFields];
+};
+// The three observing launches below take (`x`, `inv`) -- every point observes that field -- or, `typed` non-null, the table
+// pts.field indexes (`x` and `inv` are then not read).  These are different kernels: the one-field instantiations have no
+// per-point lookup.
 // out[m * ostride + p - first_point] = the observation of member m (m < mb.count) at point p, first_point <= p < first_point +
-// npoints: one launch whatever the counts, the member in the grid.  `inv`: as for the pack.
-void launch_observe_members(hipStream_t s, int st, const void* x, int pitch, Members mb, float inv, const ObservationPoints& pts,
-                            int first_point, int npoints, float* out, size_t ostride);
+// npoints: one launch whatever the counts, the member in the grid.  `inv`: as for the pack.  Typed: member m is member
+// first_member + m of every field of the table (one field: the caller offsets `x`).
+void launch_observe_members(hipStream_t s, int st, const void* x, int pitch, Members mb, float inv, const FieldSources* typed, int first_member,
+                            const ObservationPoints& pts, int first_point, int npoints, float* out, size_t ostride);
 // fluid_observation_gram: out[observation_gram_entries(mb.count)] = the padded MP x MP matrix as launch_member_gram leaves it
 // (MP = gram_padded(mb.count), entries below the diagonal not written), then rhs[MP], then dd -- the last two only with `obs`.
 // `obs`, `sigma`: pts.count floats of device memory each, or null (no innovation; 1 / sigma = 1).  mb.count in [1,
@@ -222,8 +241,8 @@ inline size_t observation_gram_entries(int members)
     return mp * mp + mp + 1;
 }
 int observation_gram_blocks(int points, int members);
-void launch_observation_gram(hipStream_t s, int st, const void* x, int pitch, Members mb, float inv, const ObservationPoints& pts,
-                             bool centre, const float* obs, const float* sigma, double* partials, double* out);
+void launch_observation_gram(hipStream_t s, int st, const void* x, int pitch, Members mb, float inv, const FieldSources* typed,
+                             const ObservationPoints& pts, bool centre, const float* obs, const float* sigma, double* partials, double* out);
 
 // Localised updates (include/fluid_amd.h "localised updates").
 // The box of a launch, half-open, in cells of the (n + 2)^2 array: rows [row_lo, row_hi), columns [col_lo, col_hi).
@@ -304,8 +323,8 @@ struct LatticeLists {
 // node's entries; a node without entries is not written.  Within a diagonal tile the entries with k > m are not the
 // header's (the weight rides on the row operand): the caller mirrors k <= m.  `operands`: pts.count * (gram_padded(mb.count)
 // + 2) doubles of scratch.  Two launches whatever the counts: every point is observed once, then one block per node.
-void launch_observation_gram_lattice(hipStream_t s, int st, const void* x, int pitch, Members mb, float inv, const ObservationPoints& pts,
-                                     bool centre, const float* obs, const float* sigma, double* operands, const LatticeLists& lists,
+void launch_observation_gram_lattice(hipStream_t s, int st, const void* x, int pitch, Members mb, float inv, const FieldSources* typed,
+                                     const ObservationPoints& pts, bool centre, const float* obs, const float* sigma, double* operands, const LatticeLists& lists,
                                      double* out);
 
 }  // namespace fluid

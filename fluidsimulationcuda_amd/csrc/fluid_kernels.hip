@@ -1892,16 +1892,62 @@ __device__ __forceinline__ float observe_point(const S* __restrict__ x, int pitc
     return w.x * a + w.y * e;
 }
 
+// Where the taps of a point come from (include/fluid_amd.h "typed networks"), the last template argument of the three kernels
+// that read a field through the network.  OneField: every point observes x -- the kernels as they were, no per-point lookup.
+// FieldOfPoint: point p observes field index[p]; `table` arrives by value with the kernel's arguments and goes into LDS at
+// block start (twelve lanes, one 16-byte entry each, then a barrier), where a lane looks its point's entry up once per chunk,
+// next to its tap and weights: the index is per lane, so the lookup is a vector one, and LDS serves 64 lanes on at most twelve
+// addresses in one broadcast read.  observe_point is the same for both: it gets a base and an inv.
+template <typename S>
+struct OneField {
+    static constexpr bool typed = false;
+    const S* x;                            // member 0 of the launch
+    float inv;
+};
+struct FieldOfPoint {
+    static constexpr bool typed = true;
+    const unsigned char* index;            // [points] field ids < kObservedFields
+    FieldSources table;
+    unsigned first;                        // member 0 of the launch is member `first` of every field
+};
+
+template <typename SRC>
+__device__ __forceinline__ void stage_sources(const SRC& src, FieldSource* lds)
+{
+    if constexpr (SRC::typed) {
+        if (threadIdx.x < kObservedFields) lds[threadIdx.x] = src.table.of[threadIdx.x];
+        __syncthreads();
+    }
+}
+
+// member 0 of the launch in the field point `pt` observes, and that field's 1 / scale
+template <typename S, typename SRC>
+__device__ __forceinline__ const S* source_of(const SRC& src, const FieldSource* lds, size_t ms, unsigned pt, float* inv)
+{
+    if constexpr (SRC::typed) {
+        const FieldSource e = lds[src.index[pt]];
+        *inv = e.inv;
+        return reinterpret_cast<const S*>(e.base) + (size_t)src.first * ms;
+    } else {
+        *inv = src.inv;
+        return src.x;
+    }
+}
+
 // fluid_observe_members: one lane per point, the member in the grid (blockIdx.y); four gathered taps, one coalesced store.
 // Points [p0, p0 + np) of the table; out[member * ostride + (point - p0)].
-template <typename S>
-__global__ __launch_bounds__(256) void k_observe_members(const S* __restrict__ x, int pitch, size_t ms, float inv,
-                                                         const unsigned long long* __restrict__ tap, const float4* __restrict__ weight, int p0,
-                                                         int np, float* __restrict__ out, size_t ostride)
+template <typename S, typename SRC>
+__global__ __launch_bounds__(256) void k_observe_members(SRC src, int pitch, size_t ms, const unsigned long long* __restrict__ tap,
+                                                         const float4* __restrict__ weight, int p0, int np, float* __restrict__ out,
+                                                         size_t ostride)
 {
+    __shared__ FieldSource sources[kObservedFields];
+    stage_sources(src, sources);
     const unsigned i = blockIdx.x * 256u + threadIdx.x;
     if (i >= (unsigned)np) return;
     const unsigned p = (unsigned)p0 + i;
+    float inv;
+    const S* x = source_of<S>(src, sources, ms, p, &inv);
     out[(size_t)blockIdx.y * ostride + i] = observe_point<S>(x + (size_t)blockIdx.y * ms, pitch, tap[p], weight[p], inv);
 }
 
@@ -1922,8 +1968,8 @@ __global__ __launch_bounds__(256) void k_observe_members(const S* __restrict__ x
 // members, CENTRE, OBS).
 constexpr int kObsChunk = 64;
 
-template <typename S, int MP, bool CENTRE, bool OBS>
-__global__ __launch_bounds__(256) void k_observation_gram(const S* __restrict__ x, int pitch, size_t ms, int members, float inv,
+template <typename S, int MP, bool CENTRE, bool OBS, typename SRC>
+__global__ __launch_bounds__(256) void k_observation_gram(SRC src, int pitch, size_t ms, int members,
                                                           const unsigned long long* __restrict__ tap, const float4* __restrict__ weight,
                                                           const float* __restrict__ obs, const float* __restrict__ sigma, int points,
                                                           unsigned chunks, double* __restrict__ partials)
@@ -1931,6 +1977,8 @@ __global__ __launch_bounds__(256) void k_observation_gram(const S* __restrict__ 
     constexpr int T = MP / 8, CH = kObsChunk, R = MP + 2, L = CH * MP / 256, E = MP * MP + MP + 1;
     static_assert(MP * MP <= CH * R, "the block's matrix is folded in the staging memory");
     __shared__ __attribute__((aligned(16))) double stage[CH * R];
+    __shared__ FieldSource sources[kObservedFields];
+    stage_sources(src, sources);
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int l5 = lane & 31, q = l5 >> 2;
     const int ta = 4 * (lane >> 5) + (q >> 1), tb = 4 * ((0x96 >> q) & 1) + (l5 & 3);
@@ -1948,6 +1996,8 @@ __global__ __launch_bounds__(256) void k_observation_gram(const S* __restrict__ 
         const bool live = pt < points;
         const unsigned long long o = live ? tap[pt] : 0ull;
         const float4 w = live ? weight[pt] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        float inv = 0.0f;
+        const S* x = live ? source_of<S>(src, sources, ms, (unsigned)pt, &inv) : nullptr;
 #pragma unroll
         for (int r = 0; r < L; ++r) {
             const int k = wave + 4 * r;
@@ -2064,14 +2114,16 @@ __global__ __launch_bounds__(256) void k_fold_observation_gram(const double* __r
 // same operations in the same order, so a_k and d have k_observation_gram's bits.  The rows go to out[point][R], R = MP + 2
 // doubles: a_k for the MP padded members (padding members 0), then d (0 without OBS), then 0 -- the layout k_lattice_gram
 // stages, written with consecutive lanes on consecutive doubles.
-template <typename S, int MP, bool CENTRE, bool OBS>
-__global__ __launch_bounds__(256) void k_observation_operands(const S* __restrict__ x, int pitch, size_t ms, int members, float inv,
+template <typename S, int MP, bool CENTRE, bool OBS, typename SRC>
+__global__ __launch_bounds__(256) void k_observation_operands(SRC src, int pitch, size_t ms, int members,
                                                               const unsigned long long* __restrict__ tap, const float4* __restrict__ weight,
                                                               const float* __restrict__ obs, const float* __restrict__ sigma, int points,
                                                               double* __restrict__ out)
 {
     constexpr int CH = kObsChunk, R = MP + 2, L = CH * MP / 256;
     __shared__ __attribute__((aligned(16))) double stage[CH * R];
+    __shared__ FieldSource sources[kObservedFields];
+    stage_sources(src, sources);
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int first = (int)blockIdx.x * CH, nc = min(CH, points - first);
     {
@@ -2079,6 +2131,8 @@ __global__ __launch_bounds__(256) void k_observation_operands(const S* __restric
         const bool live = pt < points;
         const unsigned long long o = live ? tap[pt] : 0ull;
         const float4 w = live ? weight[pt] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        float inv = 0.0f;
+        const S* x = live ? source_of<S>(src, sources, ms, (unsigned)pt, &inv) : nullptr;
 #pragma unroll
         for (int r = 0; r < L; ++r) {
             const int k = wave + 4 * r;
@@ -3362,12 +3416,28 @@ void launch_member_gram(hipStream_t s, int st, const void* x, int pitch, int n, 
     hipLaunchKernelGGL(k_fold_gram, dim3(mp * mp / 16), dim3(256), 0, s, partials, blocks, mp, mp / 8, out);
 }
 
-void launch_observe_members(hipStream_t s, int st, const void* x, int pitch, Members mb, float inv, const ObservationPoints& pts,
-                            int first_point, int npoints, float* out, size_t ostride)
+// The observing kernels' source argument, inside FLUID_BY_STORAGE: `typed` non-null is the table pts.field indexes, the launch's
+// member 0 being member `first_member` of every field; otherwise (x, inv).  LAUNCH names the type SRC and the value src.
+#define FLUID_BY_SOURCE(typed, first_member, ...)                                 \
+    do {                                                                          \
+        if (typed) {                                                              \
+            using SRC = FieldOfPoint;                                             \
+            const SRC src = {pts.field, *(typed), (unsigned)(first_member)};      \
+            __VA_ARGS__;                                                          \
+        } else {                                                                  \
+            using SRC = OneField<S>;                                              \
+            const SRC src = {(const S*)x, inv};                                   \
+            __VA_ARGS__;                                                          \
+        }                                                                         \
+    } while (0)
+
+void launch_observe_members(hipStream_t s, int st, const void* x, int pitch, Members mb, float inv, const FieldSources* typed, int first_member,
+                            const ObservationPoints& pts, int first_point, int npoints, float* out, size_t ostride)
 {
     const dim3 grid(cdiv((unsigned)npoints, 256), mb.count);
-    FLUID_BY_STORAGE(st, hipLaunchKernelGGL(k_observe_members<S>, grid, dim3(256), 0, s, (const S*)x, pitch, mb.stride, inv, pts.tap,
-                                            (const float4*)pts.weight, first_point, npoints, out, ostride));
+    FLUID_BY_STORAGE(st, FLUID_BY_SOURCE(typed, first_member,
+                                         hipLaunchKernelGGL((k_observe_members<S, SRC>), grid, dim3(256), 0, s, src, pitch, mb.stride, pts.tap,
+                                                            (const float4*)pts.weight, first_point, npoints, out, ostride)));
 }
 
 // as gram_blocks: at most two (MP = 64) or four resident blocks per CU, at least one chunk of 64 points per block
@@ -3376,15 +3446,16 @@ int observation_gram_blocks(int points, int members)
     return (int)std::min<unsigned>(cdiv((unsigned)points, kObsChunk), gram_padded(members) == 64 ? 512u : 1024u);
 }
 
-void launch_observation_gram(hipStream_t s, int st, const void* x, int pitch, Members mb, float inv, const ObservationPoints& pts,
-                             bool centre, const float* obs, const float* sigma, double* partials, double* out)
+void launch_observation_gram(hipStream_t s, int st, const void* x, int pitch, Members mb, float inv, const FieldSources* typed,
+                             const ObservationPoints& pts, bool centre, const float* obs, const float* sigma, double* partials, double* out)
 {
     const int mp = gram_padded(mb.count), blocks = observation_gram_blocks(pts.count, mb.count);
     const unsigned chunks = cdiv((unsigned)pts.count, kObsChunk);
 #define FLUID_OBS_GRAM_LAUNCH(MP, CENTRE, OBS)                                                                                             \
-    FLUID_BY_STORAGE(st, hipLaunchKernelGGL((k_observation_gram<S, MP, CENTRE, OBS>), dim3(blocks), dim3(256), 0, s, (const S*)x, pitch,   \
-                                            mb.stride, mb.count, inv, pts.tap, (const float4*)pts.weight, obs, sigma, pts.count, chunks,   \
-                                            partials))
+    FLUID_BY_STORAGE(st, FLUID_BY_SOURCE(typed, 0,                                                                                         \
+                                         hipLaunchKernelGGL((k_observation_gram<S, MP, CENTRE, OBS, SRC>), dim3(blocks), dim3(256), 0, s, src,     \
+                                                            pitch, mb.stride, mb.count, pts.tap, (const float4*)pts.weight, obs, sigma, pts.count, \
+                                                            chunks, partials)))
 #define FLUID_OBS_GRAM_CASE(MP)                                     \
     case MP:                                                        \
         if (centre && obs) FLUID_OBS_GRAM_LAUNCH(MP, true, true);   \
@@ -3404,16 +3475,17 @@ void launch_observation_gram(hipStream_t s, int st, const void* x, int pitch, Me
                        blocks, mp, mp / 8, obs ? 1 : 0, out);
 }
 
-void launch_observation_gram_lattice(hipStream_t s, int st, const void* x, int pitch, Members mb, float inv, const ObservationPoints& pts,
-                                     bool centre, const float* obs, const float* sigma, double* operands, const LatticeLists& lists,
+void launch_observation_gram_lattice(hipStream_t s, int st, const void* x, int pitch, Members mb, float inv, const FieldSources* typed,
+                                     const ObservationPoints& pts, bool centre, const float* obs, const float* sigma, double* operands, const LatticeLists& lists,
                                      double* out)
 {
     const int mp = gram_padded(mb.count);
     const unsigned chunks = cdiv((unsigned)pts.count, kObsChunk);
 #define FLUID_OBS_OPERANDS_LAUNCH(MP, CENTRE, OBS)                                                                                         \
-    FLUID_BY_STORAGE(st, hipLaunchKernelGGL((k_observation_operands<S, MP, CENTRE, OBS>), dim3(chunks), dim3(256), 0, s, (const S*)x,      \
-                                            pitch, mb.stride, mb.count, inv, pts.tap, (const float4*)pts.weight, obs, sigma, pts.count,    \
-                                            operands))
+    FLUID_BY_STORAGE(st, FLUID_BY_SOURCE(typed, 0,                                                                                         \
+                                         hipLaunchKernelGGL((k_observation_operands<S, MP, CENTRE, OBS, SRC>), dim3(chunks), dim3(256), 0, s, src, \
+                                                            pitch, mb.stride, mb.count, pts.tap, (const float4*)pts.weight, obs, sigma, pts.count, \
+                                                            operands)))
 #define FLUID_LATTICE_GRAM_CASE(MP)                                                                                                        \
     case MP:                                                                                                                               \
         if (centre && obs) FLUID_OBS_OPERANDS_LAUNCH(MP, true, true);                                                                      \

@@ -3270,25 +3270,37 @@ int fluid_upload_members(fluid_ctx* c, int field, const float* host)
 // (fluid_ctx.h: Observation), built and validated on the host; the observing calls settle the field as a pack does and
 // launch on the context's stream.  The launches belong to none of the timing categories.  Every refusal is found before
 // anything is launched or changed.
-int fluid_set_observation_points(fluid_ctx* c, const float* col, const float* row, int npoints)
+// fluid_set_observation_points and fluid_set_observation_network (include/fluid_amd.h "typed networks"), under the caller's
+// name: a null `field` is the untyped network, a table of 32 bytes per point; per-point fields add one byte per point.
+static int set_network(fluid_ctx* c, const char* call, const float* col, const float* row, const int* field, int npoints)
 {
-    if (npoints != 0 && !col) return fail(FLUID_E_INVALID, "fluid_set_observation_points: null array `col`");
-    if (npoints != 0 && !row) return fail(FLUID_E_INVALID, "fluid_set_observation_points: null array `row`");
-    if (!c) return fail(FLUID_E_INVALID, "fluid_set_observation_points: null context");
+    if (npoints != 0 && !col) return fail(FLUID_E_INVALID, "%s: null array `col`", call);
+    if (npoints != 0 && !row) return fail(FLUID_E_INVALID, "%s: null array `row`", call);
+    if (!c) return fail(FLUID_E_INVALID, "%s: null context", call);
     if (npoints < 0 || npoints > FLUID_OBSERVE_MAX_POINTS)
-        return fail(FLUID_E_INVALID, "fluid_set_observation_points: npoints %d outside [0, FLUID_OBSERVE_MAX_POINTS = %d]", npoints,
-                    FLUID_OBSERVE_MAX_POINTS);
-    TRY(refuse_slabs(c, "fluid_set_observation_points"));
+        return fail(FLUID_E_INVALID, "%s: npoints %d outside [0, FLUID_OBSERVE_MAX_POINTS = %d]", call, npoints, FLUID_OBSERVE_MAX_POINTS);
+    TRY(refuse_slabs(c, call));
     const double hi = (double)c->n + 0.5;
     for (int p = 0; p < npoints; ++p) {
         const float xy[2] = {col[p], row[p]};
         for (int a = 0; a < 2; ++a)
             if (!std::isfinite(xy[a]) || (double)xy[a] < 0.5 || (double)xy[a] > hi)
-                return fail(FLUID_E_INVALID, "fluid_set_observation_points: point %d: %s = %g is not a finite value in [0.5, N + 0.5 = %g]", p,
-                            a ? "row" : "col", (double)xy[a], hi);
+                return fail(FLUID_E_INVALID, "%s: point %d: %s = %g is not a finite value in [0.5, N + 0.5 = %g]", call, p, a ? "row" : "col",
+                            (double)xy[a], hi);
     }
+    static_assert(FLUID_NFIELDS == fluid::kObservedFields, "a point's field id indexes fluid::FieldSources");
+    const bool typed = field && npoints > 0;
+    unsigned mask = 0;
+    if (typed)
+        for (int p = 0; p < npoints; ++p) {
+            if (field[p] < 0 || field[p] >= FLUID_NFIELDS)
+                return fail(FLUID_E_INVALID, "%s: point %d: field = %d is outside [0, FLUID_NFIELDS = %d)", call, p, field[p], (int)FLUID_NFIELDS);
+            mask |= 1u << field[p];
+        }
     Observation& o = c->observe;
     char* table = nullptr;
+    std::vector<unsigned char> ids;                                     // the points' field ids, typed only
+    const size_t table_bytes = (size_t)npoints * (typed ? 33 : 32);
     if (npoints > 0) {
         const size_t P = (size_t)npoints;
         std::vector<char> host(P * 24);
@@ -3303,19 +3315,27 @@ int fluid_set_observation_points(fluid_ctx* c, const float* col, const float* ro
             weight[4 * p + 3] = t1;
             tap[p] = (unsigned long long)i0 * (unsigned long long)c->pitch + (unsigned long long)(fluid::XOFF + j0);
         }
-        hipError_t e = hipMalloc((void**)&table, P * 32);
+        if (typed) {
+            ids.resize(P);
+            for (size_t p = 0; p < P; ++p) ids[p] = (unsigned char)field[p];
+        }
+        hipError_t e = hipMalloc((void**)&table, table_bytes);
         if (e == hipSuccess) e = hipMemcpyAsync(table, host.data(), host.size(), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess && typed) e = hipMemcpyAsync(table + P * 32, ids.data(), P, hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) {                                          // the old network stays in place
             if (table) (void)hipFree(table);
             (void)hipGetLastError();
-            return fail(e == hipErrorOutOfMemory ? FLUID_E_NOMEM : FLUID_E_HIP, "fluid_set_observation_points: a table of %zu bytes: %s", P * 32,
+            return fail(e == hipErrorOutOfMemory ? FLUID_E_NOMEM : FLUID_E_HIP, "%s: a table of %zu bytes: %s", call, table_bytes,
                         hipGetErrorString(e));
         }
     } else if (o.table) HIP_TRY(hipStreamSynchronize(c->stream));      // launches that still read the old table
     if (o.table) (void)hipFree(o.table);
     o.table = table;
     o.points = npoints;
+    o.typed = typed;
+    o.mask = mask;
+    o.fields.swap(ids);
     LatticeGram& g = c->lgram;                                          // the positions fluid_observation_gram_lattice builds its lists from
     g.valid = false;
     g.coords.resize((size_t)npoints * 2);
@@ -3323,6 +3343,25 @@ int fluid_set_observation_points(fluid_ctx* c, const float* col, const float* ro
         g.coords[2 * (size_t)p] = col[p];
         g.coords[2 * (size_t)p + 1] = row[p];
     }
+    return FLUID_OK;
+}
+
+int fluid_set_observation_points(fluid_ctx* c, const float* col, const float* row, int npoints)
+{
+    return set_network(c, "fluid_set_observation_points", col, row, nullptr, npoints);
+}
+
+int fluid_set_observation_network(fluid_ctx* c, const float* col, const float* row, const int* field, int npoints)
+{
+    return set_network(c, "fluid_set_observation_network", col, row, field, npoints);
+}
+
+int fluid_observation_network_fields(fluid_ctx* c, unsigned* mask)
+{
+    if (!mask) return fail(FLUID_E_INVALID, "fluid_observation_network_fields: null pointer `mask`");
+    if (!c) return fail(FLUID_E_INVALID, "fluid_observation_network_fields: null context");
+    TRY(refuse_slabs(c, "fluid_observation_network_fields"));
+    *mask = c->observe.mask;
     return FLUID_OK;
 }
 
@@ -3338,19 +3377,49 @@ int fluid_observation_points(fluid_ctx* c, int* npoints)
 // what the three observing calls refuse beyond their own pointers
 static int check_observe(const fluid_ctx* c, const char* call, int field)
 {
-    if (!c->valid_field(field)) return fail(FLUID_E_INVALID, "%s: bad field id %d", call, field);
+    if (field != FLUID_FIELD_OF_POINT && !c->valid_field(field)) return fail(FLUID_E_INVALID, "%s: bad field id %d", call, field);
     TRY(refuse_slabs(c, call));
     if (c->observe.points == 0) return fail(FLUID_E_INVALID, "%s: no observation network is set (fluid_set_observation_points)", call);
+    if (field == FLUID_FIELD_OF_POINT && !c->observe.typed)
+        return fail(FLUID_E_INVALID, "%s: field = FLUID_FIELD_OF_POINT needs a typed network (fluid_set_observation_network with per-point fields)",
+                    call);
     return FLUID_OK;
 }
 
-static fluid::ObservationPoints observation_points(const fluid_ctx* c) { return {c->observe.tap(), c->observe.weight(), c->observe.points}; }
-
-// as pack_range sees the field: the lazy state settled, a scale kept and divided back in the kernel
-static int settle_for_observing(fluid_ctx* c, int field, float* inv)
+static fluid::ObservationPoints observation_points(const fluid_ctx* c)
 {
-    *inv = c->st != fluid::STORAGE_F32 ? 1.0f / c->field[field].fscale : 1.0f;
-    return materialize(c, field, /*keep_scale=*/*inv != 1.0f);
+    return {c->observe.tap(), c->observe.weight(), c->observe.points, c->observe.field_of_point()};
+}
+
+// What an observing launch reads: one field and its 1 / scale, or -- FLUID_FIELD_OF_POINT -- the table the points' field ids
+// index.  As pack_range sees a field: the lazy state settled, a scale kept and divided back in the kernel.  The table is
+// built after EVERY field of the network is settled, because settling one field may hand another one's buffer on.
+struct ObservedFrom {
+    const void* x = nullptr;
+    float inv = 1.0f;
+    fluid::FieldSources table = {};
+    bool typed = false;
+    const fluid::FieldSources* sources() const { return typed ? &table : nullptr; }
+};
+
+static int settle_for_observing(fluid_ctx* c, int field, ObservedFrom* from)
+{
+    auto inv_of = [&](int f) { return c->st != fluid::STORAGE_F32 ? 1.0f / c->field[f].fscale : 1.0f; };
+    if (field != FLUID_FIELD_OF_POINT) {
+        from->inv = inv_of(field);
+        TRY(materialize(c, field, /*keep_scale=*/from->inv != 1.0f));
+        from->x = c->ptr(field);
+        return FLUID_OK;
+    }
+    from->typed = true;
+    for (int f = 0; f < FLUID_NFIELDS; ++f)
+        if (c->observe.mask >> f & 1u) {
+            from->table.of[f].inv = inv_of(f);
+            TRY(materialize(c, f, /*keep_scale=*/from->table.of[f].inv != 1.0f));
+        }
+    for (int f = 0; f < FLUID_NFIELDS; ++f)
+        if (c->observe.mask >> f & 1u) from->table.of[f].base = reinterpret_cast<unsigned long long>(c->ptr(f));
+    return FLUID_OK;
 }
 
 int fluid_observe_members(fluid_ctx* c, int field, void* out_dev, size_t member_stride)
@@ -3364,9 +3433,9 @@ int fluid_observe_members(fluid_ctx* c, int field, void* out_dev, size_t member_
     size_t bytes = 0;
     if (!dense_span(P, c->members, member_stride, &bytes)) return fail(FLUID_E_INVALID, "fluid_observe_members: member_stride %zu is too large", member_stride);
     TRY(check_device_span(c, "fluid_observe_members", "out_dev", out_dev, bytes));
-    float inv = 1.0f;
-    TRY(settle_for_observing(c, field, &inv));
-    fluid::launch_observe_members(c->stream, c->st, c->ptr(field), c->pitch, c->mb(), inv, observation_points(c), 0, (int)P,
+    ObservedFrom from;
+    TRY(settle_for_observing(c, field, &from));
+    fluid::launch_observe_members(c->stream, c->st, from.x, c->pitch, c->mb(), from.inv, from.sources(), 0, observation_points(c), 0, (int)P,
                                   static_cast<float*>(out_dev), member_stride);
     HIP_TRY(hipGetLastError());
     return FLUID_OK;
@@ -3380,18 +3449,20 @@ int fluid_observe_members_host(fluid_ctx* c, int field, float* host)
     if (!c) return fail(FLUID_E_INVALID, "fluid_observe_members_host: null context");
     TRY(check_observe(c, "fluid_observe_members_host", field));
     TRY(ensure_stage(c, "fluid_observe_members_host"));
-    float inv = 1.0f;
-    TRY(settle_for_observing(c, field, &inv));
+    ObservedFrom from;
+    TRY(settle_for_observing(c, field, &from));
     const size_t P = (size_t)c->observe.points, room = (size_t)c->stage.members * member_cells(c);
     const int group = (int)std::max<size_t>(1, std::min<size_t>((size_t)c->members, room / P));
     const size_t piece = std::min(P, room);
     const fluid::ObservationPoints pts = observation_points(c);
     for (int first = 0; first < c->members; first += group) {
         const int count = std::min(group, c->members - first);
-        const char* x = static_cast<const char*>(c->ptr(field)) + (size_t)first * c->field_bytes;
+        // one field: the group's first member by its address; the points' own fields: by its index, applied to every field's base
+        const char* x = from.typed ? nullptr : static_cast<const char*>(from.x) + (size_t)first * c->field_bytes;
         for (size_t p0 = 0; p0 < P; p0 += piece) {                       // (one piece unless the network outgrows the buffer: count is 1 then)
             const size_t np = std::min(piece, P - p0);
-            fluid::launch_observe_members(c->stream, c->st, x, c->pitch, {count, c->field_floats}, inv, pts, (int)p0, (int)np, c->stage.dev, np);
+            fluid::launch_observe_members(c->stream, c->st, x, c->pitch, {count, c->field_floats}, from.inv, from.sources(), first, pts, (int)p0,
+                                          (int)np, c->stage.dev, np);
             HIP_TRY(hipGetLastError());
             if (np == P)
                 HIP_TRY(hipMemcpyAsync(host + (size_t)first * P, c->stage.dev, (size_t)count * P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -3438,7 +3509,7 @@ int fluid_observation_gram(fluid_ctx* c, int field, int centre, const float* obs
     if (!gram) return fail(FLUID_E_INVALID, "fluid_observation_gram: null array `gram`");
     if (!obs && (rhs || dd)) return fail(FLUID_E_INVALID, "fluid_observation_gram: `%s` is given but `obs` is null", rhs ? "rhs" : "dd");
     if (!c) return fail(FLUID_E_INVALID, "fluid_observation_gram: null context");
-    if (!c->valid_field(field)) return fail(FLUID_E_INVALID, "fluid_observation_gram: bad field id %d", field);
+    if (field != FLUID_FIELD_OF_POINT && !c->valid_field(field)) return fail(FLUID_E_INVALID, "fluid_observation_gram: bad field id %d", field);
     if (c->members > FLUID_TRANSFORM_MAX_MEMBERS)
         return fail(FLUID_E_INVALID, "fluid_observation_gram: this context has %d members, above FLUID_TRANSFORM_MAX_MEMBERS = %d", c->members,
                     FLUID_TRANSFORM_MAX_MEMBERS);
@@ -3452,9 +3523,9 @@ int fluid_observation_gram(fluid_ctx* c, int field, int centre, const float* obs
     TRY(ensure_observation_gram(c));
     if (obs) HIP_TRY(hipMemcpyAsync(o.obs(), obs, P * sizeof(float), hipMemcpyHostToDevice, c->stream));
     if (inv_sigma) HIP_TRY(hipMemcpyAsync(o.sigma(), inv_sigma, P * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    float inv = 1.0f;
-    TRY(settle_for_observing(c, field, &inv));
-    fluid::launch_observation_gram(c->stream, c->st, c->ptr(field), c->pitch, c->mb(), inv, observation_points(c), centre != 0,
+    ObservedFrom from;
+    TRY(settle_for_observing(c, field, &from));
+    fluid::launch_observation_gram(c->stream, c->st, from.x, c->pitch, c->mb(), from.inv, from.sources(), observation_points(c), centre != 0,
                                    obs ? o.obs() : nullptr, inv_sigma ? o.sigma() : nullptr, o.d_partials, o.d_out);
     HIP_TRY(hipGetLastError());
     const int M = c->members, mp = fluid::gram_padded(M);
@@ -3603,10 +3674,10 @@ static int enqueue_lattice_gram(fluid_ctx* c, const char* call, int field, int c
     }
     if (obs) HIP_TRY(hipMemcpyAsync(o.obs(), obs, P * sizeof(float), hipMemcpyHostToDevice, c->stream));
     if (inv_sigma) HIP_TRY(hipMemcpyAsync(o.sigma(), inv_sigma, P * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    float inv = 1.0f;
-    TRY(settle_for_observing(c, field, &inv));
+    ObservedFrom from;
+    TRY(settle_for_observing(c, field, &from));
     const fluid::LatticeLists lists = {reinterpret_cast<const int*>(g.d_lists), reinterpret_cast<const int2*>(g.d_lists + start_bytes), (int)B};
-    fluid::launch_observation_gram_lattice(c->stream, c->st, c->ptr(field), c->pitch, c->mb(), inv, observation_points(c), centre != 0,
+    fluid::launch_observation_gram_lattice(c->stream, c->st, from.x, c->pitch, c->mb(), from.inv, from.sources(), observation_points(c), centre != 0,
                                            obs ? o.obs() : nullptr, inv_sigma ? o.sigma() : nullptr, g.d_operands, lists, g.d_out);
     HIP_TRY(hipGetLastError());
     return FLUID_OK;

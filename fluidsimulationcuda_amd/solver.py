@@ -25,6 +25,14 @@ def _fid(f):
     return int(f)
 
 
+def _ofid(f):
+    """The field of an observing call: a name or id, or None / "point" for capi.FIELD_OF_POINT -- every point of a typed
+    network observes its own field."""
+    if f is None or f == "point":
+        return capi.FIELD_OF_POINT
+    return _fid(f)
+
+
 def _host(a, n):
     a = np.ascontiguousarray(a, dtype=np.float32)
     if a.shape != (n + 2, n + 2):
@@ -232,20 +240,40 @@ class FluidSolver:
             raise ValueError("cols and rows must have the same length, got %d and %d" % (c.size, r.size))
         capi.check(capi.lib().fluid_set_observation_points(self._h, _mf(c), _mf(r), int(c.size)))
 
+    def set_observation_network(self, cols, rows, fields=None):
+        """set_observation_points with the field each point observes: `fields`, one name or id per point, makes the
+        network TYPED -- the observing calls then take field=None (or "point") and read every point from its own field, in
+        one call.  fields=None: set_observation_points (include/fluid_amd.h, "typed networks")."""
+        if fields is None:
+            return self.set_observation_points(cols, rows)
+        c = np.ascontiguousarray(np.asarray(cols, np.float32).ravel())
+        r = np.ascontiguousarray(np.asarray(rows, np.float32).ravel())
+        f = np.ascontiguousarray(np.array([_fid(v) for v in fields], np.int32))
+        if not c.size == r.size == f.size:
+            raise ValueError("cols, rows and fields must have the same length, got %d, %d and %d" % (c.size, r.size, f.size))
+        capi.check(capi.lib().fluid_set_observation_network(self._h, _mf(c), _mf(r), f.ctypes.data_as(C.POINTER(C.c_int)), int(c.size)))
+
+    def observation_fields(self):
+        """The names of the fields some point of a typed network observes; empty for an untyped network or none."""
+        mask = C.c_uint()
+        capi.check(capi.lib().fluid_observation_network_fields(self._h, C.byref(mask)))
+        return {name for k, name in enumerate(capi.FIELD_NAMES) if mask.value >> k & 1}
+
     def observation_points(self):
         """The number of points of the network; 0 when none is set."""
         p = C.c_int()
         capi.check(capi.lib().fluid_observation_points(self._h, C.byref(p)))
         return p.value
 
-    def observe(self, field):
+    def observe(self, field=None):
         """Every member's value at every point of the network as a (members, points) float32 array: the bilinear sample
-        the solver's advection uses, on what pack would show (include/fluid_amd.h, "observing ensembles")."""
+        the solver's advection uses, on what pack would show (include/fluid_amd.h, "observing ensembles").  field=None or
+        "point", here and in every observing call: each point of a typed network from the field it observes."""
         out = np.empty((self.members, self.observation_points()), np.float32)
-        capi.check(capi.lib().fluid_observe_members_host(self._h, _fid(field), _mf(out)))
+        capi.check(capi.lib().fluid_observe_members_host(self._h, _ofid(field), _mf(out)))
         return out
 
-    def observe_device(self, field, out=None, member_stride=0, wait=True):
+    def observe_device(self, field=None, out=None, member_stride=0, wait=True):
         """observe() into a dense device array, in one launch: out[m * member_stride + p] (member_stride=0: the number of
         points).  `out`, `wait`: as for pack; None: a (members, points) float32 torch tensor is allocated (member_stride
         must then be 0)."""
@@ -256,12 +284,12 @@ class FluidSolver:
             import torch
             out = torch.empty((self.members, points), dtype=torch.float32, device="cuda")
         self._handover(wait)
-        capi.check(capi.lib().fluid_observe_members(self._h, _fid(field), device_address(out), int(member_stride)))
+        capi.check(capi.lib().fluid_observe_members(self._h, _ofid(field), device_address(out), int(member_stride)))
         if wait:
             self.synchronize()
         return out
 
-    def observation_gram(self, field, obs=None, inv_sigma=None, centre=True):
+    def observation_gram(self, field=None, obs=None, inv_sigma=None, centre=True):
         """The Gram matrix of the members in observation space: C[k][m] = sum over the points of a_k a_m, a_k = (h_k - mean)
         / sigma (the mean over the members subtracted with `centre`; inv_sigma: 1 / sigma per point, None for 1).  With
         `obs`, the observed values y: returns (C, rhs, dd), rhs[k] = sum a_k d and dd = sum d d for the innovation d =
@@ -281,7 +309,7 @@ class FluidSolver:
         dp = C.POINTER(C.c_double)
         g = np.empty((self.members, self.members), np.float64)
         rhs, dd = np.empty(self.members, np.float64), C.c_double()
-        capi.check(capi.lib().fluid_observation_gram(self._h, _fid(field), 1 if centre else 0, None if y is None else _mf(y),
+        capi.check(capi.lib().fluid_observation_gram(self._h, _ofid(field), 1 if centre else 0, None if y is None else _mf(y),
                                                      None if s is None else _mf(s), g.ctypes.data_as(dp),
                                                      None if y is None else rhs.ctypes.data_as(dp), None if y is None else C.byref(dd)))
         return g if y is None else (g, rhs, dd.value)
@@ -543,7 +571,7 @@ class FluidSolver:
         rhs, dd = np.empty(room + (m,), np.float64), np.empty(room, np.float64)
         counts = np.empty(room, np.int32)
         capi.check(capi.lib().fluid_observation_gram_lattice(
-            self._h, _fid(field), 1 if centre else 0, None if y is None else _mf(y), None if s is None else _mf(s), nr, nc, row0, col0,
+            self._h, _ofid(field), 1 if centre else 0, None if y is None else _mf(y), None if s is None else _mf(s), nr, nc, row0, col0,
             int(step), float(c), g.ctypes.data_as(dp), None if y is None else rhs.ctypes.data_as(dp),
             None if y is None else dd.ctypes.data_as(dp), counts.ctypes.data_as(C.POINTER(C.c_int))))
         return (g, counts) if y is None else (g, rhs, dd, counts)
@@ -595,7 +623,7 @@ class FluidSolver:
         nr, nc = (int(v) for v in shape)
         row0, col0 = (int(v) for v in origin)
         ids = [_fid(f) for f in fields]
-        capi.check(capi.lib().fluid_analyse_lattice(self._h, _fid(field), None if y is None else _mf(y), None if s is None else _mf(s),
+        capi.check(capi.lib().fluid_analyse_lattice(self._h, _ofid(field), None if y is None else _mf(y), None if s is None else _mf(s),
                                                     nr, nc, row0, col0, int(step), float(c), float(rho), (C.c_int * len(ids))(*ids),
                                                     len(ids)))
         if wait:

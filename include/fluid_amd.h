@@ -550,6 +550,46 @@ int fluid_observe_members_host(fluid_ctx *ctx, int field, float *host);
 int fluid_observation_gram(fluid_ctx *ctx, int field, int centre, const float *obs, const float *inv_sigma,
                            double *gram, double *rhs, double *dd);
 
+/* ---- typed networks: observation points that each observe their own field -----------------------------------------------
+ * A real network on a fluid is mixed: density probes in one place, u and v probes in another.  The matrix of a filter is
+ * the sum over ALL its points, of whatever variable: C = sum over p of w_p a_k[p] a_m[p].  A TYPED network gives every point
+ * the field it observes, and the five observing calls then read each point from its own field in ONE call.
+ *
+ * - fluid_set_observation_network is fluid_set_observation_points in every respect -- the same validation of `col` and
+ *   `row`, it replaces the previous network, npoints = 0 clears it, a failed allocation is FLUID_E_NOMEM and keeps the old
+ *   network, it invalidates the point lists of the lattice calls -- with one addition: `field`, a host array of npoints field
+ *   ids in [0, FLUID_NFIELDS), field[p] the field that point p observes.  The network is then typed; its table takes 33
+ *   bytes per point, against the 32 of an untyped one.  A null `field` makes the call identical to
+ *   fluid_set_observation_points: the network is untyped, as every network set through that call is.
+ * - fluid_observation_network_fields: bit f of *mask is set when some point observes field f; *mask = 0 for an untyped
+ *   network and when no network is set.  Host logic only.
+ * - FLUID_FIELD_OF_POINT for `field` in fluid_observe_members, fluid_observe_members_host, fluid_observation_gram,
+ *   fluid_observation_gram_lattice and fluid_analyse_lattice, on a typed network: in rule 1 of each definition h_k[p] is the
+ *   same bilinear sample, operation for operation, taken from field field[p] -- the taps are what fluid_pack_members would
+ *   show for THAT field.  Everything after rule 1 is untouched: the mean chain over the members at the point, 1 / sigma,
+ *   the innovation, the chunks of 64 points and the wave order, the folds, the lattice weights and lists (which do not
+ *   depend on the fields: the cache is kept), the solve and the update.  The order of every addition is unchanged: it is
+ *   still fixed by the point index, so the results also depend on the per-point fields, and on nothing else that is new.
+ * - Every distinct field of the network is settled first, as a pack settles it (zeros by definition, a pending increment,
+ *   a deferred source); fields that no point observes are not touched, and nothing a later step or download sees is altered.
+ *   With fp16 storage each field that is held at a pressure scale keeps it, and its taps are divided back in float by that
+ *   field's OWN scale: the per-field scale of one launch may differ from point to point.
+ * - A concrete field id on a typed network behaves exactly as on an untyped network with the same positions: all points
+ *   sample that field and the per-point fields are ignored.  On untyped networks nothing changes, bit for bit; those calls
+ *   launch kernels without any per-point lookup.
+ * - Poisoning.  centre == 0: a non-finite value in member k of field f poisons row k, column k and rhs[k] only, and only
+ *   through points that observe f and whose 2 x 2 stencil holds the value -- for the lattice calls only in the nodes those
+ *   points take part in.  centre != 0: as before, through such points only.
+ * Refusals, all FLUID_E_INVALID with a message that names the call, found before anything is launched or changed, null
+ * pointers before the context is looked at: everything fluid_set_observation_points refuses, under
+ * fluid_set_observation_network's name; a field[p] outside [0, FLUID_NFIELDS) (the message names p and the value);
+ * FLUID_FIELD_OF_POINT with an untyped network (the message says that a typed network is needed) or with no network (the
+ * message of the call as before); a null `mask`; a null context; row slabs.  Any other negative or too-large field id is
+ * the "bad field id" refusal as before. */
+#define FLUID_FIELD_OF_POINT (-2)
+int fluid_set_observation_network(fluid_ctx *ctx, const float *col, const float *row, const int *field, int npoints);
+int fluid_observation_network_fields(fluid_ctx *ctx, unsigned *mask);
+
 /* ---- localised updates: the increment of a transform under a per-cell taper, over a box of cells ------------------
  * M = fluid_members(ctx), W = N + 2.  With at most FLUID_TRANSFORM_MAX_MEMBERS members against N*N states a global
  * ensemble update is rank-deficient and full of spurious long-range covariances; every practical scheme (LETKF, EnSRF)
