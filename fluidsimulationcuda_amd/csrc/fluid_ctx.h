@@ -82,77 +82,97 @@ struct FieldState {
     float fscale = 1.0f;
 };
 
-// Per-member constants (the fluid_*_members calls) reach the kernels through tables in device memory: a ring of device
-// memory with a pinned host twin, library-owned and outside the arena, allocated at the first such call.  A table is copied
-// host twin -> device on the context's stream, so it is in place before the launches that read it and is not overwritten
-// before the launches queued ahead of the next copy have run; the host twin's bytes are reused only after the event behind
-// their copy has completed.  A table whose bytes equal one still in the ring is not copied again (fluid_solver.hip:
-// member_consts): a stepping loop with the same arrays every call uploads nothing and waits for nothing.
-struct ConstRing {
+// What the ensemble calls need beyond the fields is library-owned and outside the arena, and every piece of it is one of
+// these: `bytes` of device memory and, where a call asked for one, a pinned host twin of the same size.  ONE function
+// allocates and grows them (fluid_solver.hip: reserve), at the first call that needs the room: enough room is left
+// alone; otherwise the new pair is allocated first, the context's stream is waited for -- launches enqueued so far may
+// still read the old pair -- and only then the old pair is freed.  A grown buffer does not keep its contents.  A failure
+// (FLUID_E_NOMEM for an allocation the device or the host refuses) frees what the call had allocated and leaves the
+// buffer, and so the context, as it was.  An owner of several buffers reserves them one by one, so a call that failed
+// part-way is completed by the next.  The destructor frees both: it runs when fluid_destroy, after its waits, deletes the
+// context.
+struct Scratch {
     char *dev = nullptr, *host = nullptr;
-    size_t bytes = 0, head = 0;
+    size_t bytes = 0;                     // the room of each
+    Scratch() = default;
+    Scratch(const Scratch&) = delete;
+    Scratch& operator=(const Scratch&) = delete;
+    ~Scratch() { release(); }
+    void release()
+    {
+        if (dev) (void)hipFree(dev);
+        if (host) (void)hipHostFree(host);
+        dev = host = nullptr;
+        bytes = 0;
+    }
+    template <class T> T* d(size_t byte_offset = 0) const { return reinterpret_cast<T*>(dev + byte_offset); }
+    template <class T> T* h(size_t byte_offset = 0) const { return reinterpret_cast<T*>(host + byte_offset); }
+};
+
+// Per-member constants (the fluid_*_members calls) reach the kernels through tables in device memory: a ring with a
+// pinned twin.  A table is copied host twin -> device on the context's stream, so it is in place before the launches that
+// read it and is not overwritten before the launches queued ahead of the next copy have run; the host twin's bytes are
+// reused only after the event behind their copy has completed.  A table whose bytes equal one still in the ring is not
+// copied again (fluid_solver.hip: member_consts): a stepping loop with the same arrays every call uploads nothing and
+// waits for nothing.
+struct ConstRing {
+    Scratch ring;
+    size_t head = 0;
     struct Blob { size_t off, len; unsigned long long hash; hipEvent_t copied; };
     std::vector<Blob> live;                 // tables in the ring, oldest first
     std::vector<hipEvent_t> free_events;
 };
 
 // What the ensemble diagnostics (fluid_*_members maxima, fluid_member_moments, fluid_ensemble_stats, fluid_member_gram) need
-// beyond the fields: library-owned, outside the arena, each part allocated at the first call that needs it (fluid_solver.hip:
-// ensure_member_results, ensure_stats, ensure_gram) and freed in fluid_destroy.
+// beyond the fields.  The twin of `moments` also takes the members' result words on their way to the host.
 struct EnsembleReduce {
-    unsigned int* d_max = nullptr;        // one result word per member (k_residual / k_absmax2 with a result stride of 1)
-    double2* d_moments = nullptr;         // one {sum, sum of squares} per member
-    double2* d_partials = nullptr;        // members x moment_blocks() per-block pairs
-    char* host = nullptr;                 // pinned twin of the larger of the two result arrays
-    float *d_mean = nullptr, *d_var = nullptr;   // the two statistics fields, field_floats floats each, pads zero
+    Scratch max;                          // [members] result words (k_residual / k_absmax2 with a result stride of 1)
+    Scratch moments;                      // [members] double2 {sum, sum of squares}, and its twin
+    Scratch partials;                     // [members][moment_blocks()] per-block double2 pairs
+    Scratch mean, var;                    // the two statistics fields, field_floats floats each: zeroed once, so the pads stay zero
     bool have_stats = false;              // a fluid_ensemble_stats has filled them
-    // fluid_member_gram (ensure_gram): gram_blocks() per-block MP x MP matrices, MP = gram_padded(members), the folded
-    // matrix and its pinned twin
-    double *d_gram_partials = nullptr, *d_gram = nullptr, *gram_host = nullptr;
+    // fluid_member_gram, MP = gram_padded(members):
+    Scratch gram_partials;                // [gram_blocks()] per-block MP x MP double matrices
+    Scratch gram;                         // the folded MP x MP matrix, and its twin
 };
 
 // The bulk host copies (fluid_download_members / fluid_upload_members) go through a dense float staging buffer on the
-// device: library-owned, outside the arena, allocated by the first such call and freed in fluid_destroy (fluid_solver.hip:
-// ensure_stage).  It holds `members` whole members; a call moves its members group by group in stream order.
+// device.  It holds `members` whole members; a call moves its members group by group in stream order.
 struct MemberStage {
-    float* dev = nullptr;
+    Scratch buf;
     int members = 0;
+    float* dev() const { return buf.d<float>(); }
 };
 
-// The weight tables of fluid_transform_members / fluid_select_members: kSlots tables of `slot` bytes each in device memory
-// with a pinned host twin, library-owned and outside the arena, allocated by the first such call and freed in
-// fluid_destroy (fluid_solver.hip: ensure_transform).  A call fills the next host slot and copies it to its device slot on
-// the context's stream: the copy runs behind every launch enqueued so far, so the device bytes need no wait, and the host
-// bytes are reused only after the event behind their own copy -- kSlots calls ago -- has completed.  (The ConstRing is
-// sized for the per-member records: 64 KiB at small M, where one 64-member table is 32.5 KiB.)
+// The weight tables of fluid_transform_members / fluid_select_members: kSlots slots of one padded table each, with a twin.
+// A call fills the next host slot and copies it to its device slot on the context's stream: the copy runs behind every
+// launch enqueued so far, so the device bytes need no wait, and the host bytes are reused only after the event behind
+// their own copy -- kSlots calls ago -- has completed.  (The ConstRing is sized for the per-member records: 64 KiB at
+// small M, where one 64-member table is 32.5 KiB.)
 struct TransformTables {
     static constexpr int kSlots = 8;
-    char *dev = nullptr, *host = nullptr;
-    size_t slot = 0;
+    Scratch tables;
     int next = 0;
     hipEvent_t copied[kSlots] = {};
     bool in_use[kSlots] = {};
 };
 
-// The node tables of fluid_transform_members_lattice: ONE device buffer with a pinned host twin, library-owned and outside
-// the arena, allocated or grown by the first call that needs the room and freed in fluid_destroy (fluid_solver.hip:
-// ensure_lattice).  Per call: [nodes][M][MP] doubles, then [nodes][M] words of non-zero bits, then [nodes] words of their
-// OR.  The copy runs on the context's stream behind the launches of the call before, so the device bytes need no wait;
-// the host bytes are refilled only after the event behind their last copy has completed.
+// The node tables of fluid_transform_members_lattice: ONE buffer with a twin.  Per call: [nodes][M][MP] doubles, then
+// [nodes][M] words of non-zero bits, then [nodes] words of their OR.  The copy runs on the context's stream behind the
+// launches of the call before, so the device bytes need no wait; the host bytes are refilled only after the event behind
+// their last copy has completed.  (fluid_analyse_lattice writes the device tables itself and leaves twin and event alone.)
 struct LatticeNodeTables {
-    char *dev = nullptr, *host = nullptr;
-    size_t bytes = 0;                     // the room of each
+    Scratch tables;
     hipEvent_t copied = nullptr;
-    bool in_use = false;                  // `copied` has been recorded
+    bool in_use = false;                  // `copied` has been recorded since the tables last grew
 };
 
 // Observing ensembles (fluid_set_observation_points, fluid_observe_members, fluid_observation_gram): the network and the
-// scratch of its Gram call, library-owned and outside the arena (fluid_solver.hip: fluid_set_observation_points,
-// ensure_observation_gram), freed in fluid_destroy.  The network is ONE allocation of 32 bytes per point: four floats of
-// weights, the 64-bit tap offset, and one float each for the observed values and 1 / sigma a Gram call copies in.  A TYPED
-// network (fluid_set_observation_network with per-point fields) has one more byte per point behind them, 33 in all: the id
-// of the field the point observes, the index into the launch's fluid::FieldSources.  `fields` is its host copy, `mask` the
-// fields some point observes; an untyped network has neither.
+// scratch of its Gram call.  The network is ONE allocation of 32 bytes per point, replaced as a whole by the call that sets
+// it and freed in fluid_destroy: four floats of weights, the 64-bit tap offset, and one float each for the observed values
+// and 1 / sigma a Gram call copies in.  A TYPED network (fluid_set_observation_network with per-point fields) has one more
+// byte per point behind them, 33 in all: the id of the field the point observes, the index into the launch's
+// fluid::FieldSources.  `fields` is its host copy, `mask` the fields some point observes; an untyped network has neither.
 struct Observation {
     char* table = nullptr;                // [points] float4 weights | [points] tap offsets | [points] obs | [points] 1 / sigma | typed: [points] field ids
     int points = 0;
@@ -160,8 +180,8 @@ struct Observation {
     unsigned mask = 0;                    // bit f: some point observes field f (0: untyped)
     std::vector<unsigned char> fields;    // [points], typed only
     const unsigned char* field_of_point() const { return typed ? reinterpret_cast<const unsigned char*>(table + (size_t)points * 32) : nullptr; }
-    double *d_partials = nullptr, *d_out = nullptr, *host = nullptr;    // per-block partials, the folded result, its pinned twin
-    int partial_blocks = 0;               // what d_partials has room for
+    Scratch partials;                     // [observation_gram_blocks()] per-block results of the network in place, or of a larger one before it
+    Scratch result;                       // the folded result, fluid::observation_gram_entries doubles, and its twin
     const float* weight() const { return reinterpret_cast<const float*>(table); }
     const unsigned long long* tap() const { return reinterpret_cast<const unsigned long long*>(table + (size_t)points * 16); }
     float* obs() const { return reinterpret_cast<float*>(table + (size_t)points * 24); }
@@ -169,36 +189,29 @@ struct Observation {
 };
 
 // Lattice observations (fluid_observation_gram_lattice): the point lists of the nodes, the operands of every point and the
-// results of every node, library-owned and outside the arena (fluid_solver.hip: ensure_lattice_gram), each allocated or grown
-// by the first call that needs the room and freed in fluid_destroy.  `coords` is the host copy of the network's positions
-// (fluid_set_observation_points keeps it: col, row per point) the lists are built from.  The lists are ONE buffer with a
-// pinned twin: [nodes + 1] ints, the start of every node's entries, then the entries, {point index, the bits of the float
-// weight}, a node's in increasing point index.  They are kept: `valid` says that they are the lists of the network in place
-// and of the lattice arguments and c below, and then a call builds and uploads nothing.
+// results of every node.  `coords` is the host copy of the network's positions (fluid_set_observation_points keeps it: col,
+// row per point) the lists are built from.  The lists are ONE buffer with a twin: [nodes + 1] ints, the start of every
+// node's entries, then the entries, {point index, the bits of the float weight}, a node's in increasing point index.  They
+// are kept: `valid` says that they are the lists of the network in place and of the lattice arguments and c below, and
+// then a call builds and uploads nothing.
 struct LatticeGram {
     std::vector<float> coords;            // [points] {col, row}
-    char *d_lists = nullptr, *h_lists = nullptr;
-    size_t list_bytes = 0;                // the room of each
-    double* d_operands = nullptr;         // [points][MP + 2] doubles: a_k (padding members 0), then d, then 0
-    size_t operand_bytes = 0;
-    double *d_out = nullptr, *h_out = nullptr;   // [nodes] partial-shaped results (fluid::observation_gram_entries doubles) and their twin
-    size_t out_bytes = 0;
+    Scratch lists;
+    Scratch operands;                     // [points][MP + 2] doubles: a_k (padding members 0), then d, then 0
+    Scratch out;                          // [nodes] partial-shaped results (fluid::observation_gram_entries doubles) and their twin
     bool valid = false;
     int nodes_row = 0, nodes_col = 0, row0 = 0, col0 = 0, step = 0;
     float c = 0.0f;
     long long pairs = 0;                  // entries of the lists
 };
 
-// The ETKF solve (fluid_etkf_increments, fluid_analyse_lattice): library-owned and outside the arena, freed in
-// fluid_destroy.  The host route's operands ([nodes] M x M doubles, [nodes] M doubles, [nodes] ints) and results ([nodes]
-// M x M floats, [nodes] ints) each are ONE buffer with a pinned twin, grown on demand (fluid_solver.hip: grow_lattice_gram); every
-// call of that route ends in a wait.  The fused route's status words, one per node, have a fixed size:
-// FLUID_LATTICE_MAX_NODES ints and their twin, allocated by the first analysis.  `in_flight`: an analysis has been
-// enqueued and nothing has waited for the stream since -- its launches may still read the point lists and their twin.
+// The ETKF solve (fluid_etkf_increments, fluid_analyse_lattice).  The host route's operands ([nodes] M x M doubles, [nodes]
+// M doubles, [nodes] ints) and results ([nodes] M x M floats, [nodes] ints) each are ONE buffer with a twin; every call of
+// that route ends in a wait.  The fused route's status words, one per node, have a fixed size: FLUID_LATTICE_MAX_NODES
+// ints and their twin.  `in_flight`: an analysis has been enqueued and nothing has waited for the stream since -- its
+// launches may still read the point lists and their twin.
 struct EtkfBuffers {
-    char *d_in = nullptr, *h_in = nullptr, *d_out = nullptr, *h_out = nullptr;
-    size_t in_bytes = 0, out_bytes = 0;   // the room of each pair
-    int *d_status = nullptr, *h_status = nullptr;
+    Scratch in, out, status;
     int analysed = 0;                     // nodes of the last fluid_analyse_lattice, 0 before the first
     bool in_flight = false;
 };

@@ -94,25 +94,56 @@ int check_b(int b)
     return FLUID_OK;
 }
 
+// ---- library-owned scratch (fluid_ctx.h: Scratch) -------------------------------------------------------------------------
+// `s` has room for `bytes`, with a pinned twin if one is wanted; *grew: it was allocated anew, and holds nothing.  The one
+// place where such memory is allocated, grown and -- short of the context's end -- freed; the contract is in fluid_ctx.h.
+int reserve(fluid_ctx* c, Scratch& s, size_t bytes, bool twin, const char* call, const char* what, bool* grew = nullptr)
+{
+    if (grew) *grew = false;
+    if (s.bytes >= bytes && (s.host || !twin)) return FLUID_OK;
+    char *dev = nullptr, *host = nullptr;
+    hipError_t e = hipMalloc((void**)&dev, bytes);
+    if (e == hipSuccess && twin) e = hipHostMalloc((void**)&host, bytes, hipHostMallocDefault);
+    if (e == hipSuccess && s.dev) e = hipStreamSynchronize(c->stream);     // launches enqueued so far may still read the old pair
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        if (dev) (void)hipFree(dev);
+        if (host) (void)hipHostFree(host);
+        return fail(e == hipErrorOutOfMemory ? FLUID_E_NOMEM : FLUID_E_HIP, "%s: allocating %zu bytes of %s: %s", call, bytes, what,
+                    hipGetErrorString(e));
+    }
+    s.release();
+    s.dev = dev;
+    s.host = host;
+    s.bytes = bytes;
+    if (grew) *grew = true;
+    return FLUID_OK;
+}
+
+// an event a buffer's owner records behind the copies out of its twin, made when first needed (fluid_destroy destroys it)
+int ensure_event(hipEvent_t* ev)
+{
+    if (!*ev) HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+    return FLUID_OK;
+}
+
 // ---- tables of per-member constants (fluid_ctx.h: ConstRing) -------------------------------------------------------
 constexpr size_t kConstAlign = 256, kConstSlots = 8, kConstBlobs = 64;
 size_t const_pad(size_t len) { return (len + kConstAlign - 1) / kConstAlign * kConstAlign; }
 
-// the ring, allocated once: at the first fluid_*_members call of a context with more than one member
+// the ring and its events, complete after the first fluid_*_members call of a context with more than one member: a call
+// that failed part-way leaves what it made to the next one, which makes what is missing
 int ensure_consts(fluid_ctx* c)
 {
     ConstRing& r = c->consts;
-    if (r.dev) return FLUID_OK;
     // the largest table is a batch's: 3 solves x members records; room for kConstSlots of them
     const size_t bytes = std::max<size_t>(64u << 10, kConstSlots * const_pad(3 * (size_t)c->members * sizeof(fluid::TbMemberK)));
-    HIP_TRY(hipMalloc((void**)&r.dev, bytes));
-    HIP_TRY(hipHostMalloc((void**)&r.host, bytes, hipHostMallocDefault));
-    for (size_t k = 0; k < kConstBlobs; ++k) {
-        hipEvent_t ev;
-        HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    TRY(reserve(c, r.ring, bytes, true, "per-member constants", "tables"));
+    while (r.live.size() + r.free_events.size() < kConstBlobs) {
+        hipEvent_t ev = nullptr;
+        TRY(ensure_event(&ev));
         r.free_events.push_back(ev);
     }
-    r.bytes = bytes;
     return FLUID_OK;
 }
 
@@ -121,15 +152,15 @@ int ensure_consts(fluid_ctx* c)
 int member_consts(fluid_ctx* c, const void* data, size_t len, const void** dev)
 {
     ConstRing& r = c->consts;
-    if (!r.dev || const_pad(len) * kConstSlots > r.bytes) return fail(FLUID_E_INVALID, "per-member constants: no table (internal)");
+    if (!r.ring.dev || const_pad(len) * kConstSlots > r.ring.bytes) return fail(FLUID_E_INVALID, "per-member constants: no table (internal)");
     unsigned long long hash = 1469598103934665603ull;
     for (size_t k = 0; k < len; ++k) hash = (hash ^ static_cast<const unsigned char*>(data)[k]) * 1099511628211ull;
     for (const ConstRing::Blob& b : r.live)
-        if (b.len == len && b.hash == hash && std::memcmp(r.host + b.off, data, len) == 0) {
-            *dev = r.dev + b.off;
+        if (b.len == len && b.hash == hash && std::memcmp(r.ring.host + b.off, data, len) == 0) {
+            *dev = r.ring.dev + b.off;
             return FLUID_OK;
         }
-    if (r.head + const_pad(len) > r.bytes) r.head = 0;
+    if (r.head + const_pad(len) > r.ring.bytes) r.head = 0;
     const size_t lo = r.head, hi = lo + const_pad(len);
     // The tables this one overwrites (and the oldest, if all events are out) leave the ring.  Their device bytes are safe
     // without a wait: the copy below runs behind every launch enqueued so far.  Their host bytes must have been read:
@@ -145,14 +176,14 @@ int member_consts(fluid_ctx* c, const void* data, size_t len, const void** dev)
         r.free_events.push_back(b.copied);
         r.live.erase(r.live.begin() + (ptrdiff_t)k);
     }
-    std::memcpy(r.host + lo, data, len);
-    HIP_TRY(hipMemcpyAsync(r.dev + lo, r.host + lo, len, hipMemcpyHostToDevice, c->stream));
+    std::memcpy(r.ring.host + lo, data, len);
+    HIP_TRY(hipMemcpyAsync(r.ring.dev + lo, r.ring.host + lo, len, hipMemcpyHostToDevice, c->stream));
     hipEvent_t ev = r.free_events.back();
     r.free_events.pop_back();
     HIP_TRY(hipEventRecord(ev, c->stream));
     r.live.push_back({lo, len, hash, ev});
     r.head = hi;
-    *dev = r.dev + lo;
+    *dev = r.ring.dev + lo;
     return FLUID_OK;
 }
 
@@ -1851,40 +1882,10 @@ int fluid_destroy(fluid_ctx* c)
     if (c->tiles) (void)hipFree(c->tiles);
     for (auto& b : c->consts.live) (void)hipEventDestroy(b.copied);
     for (hipEvent_t ev : c->consts.free_events) (void)hipEventDestroy(ev);
-    if (c->consts.dev) (void)hipFree(c->consts.dev);
-    if (c->consts.host) (void)hipHostFree(c->consts.host);
-    if (c->red.d_max) (void)hipFree(c->red.d_max);
-    if (c->red.d_moments) (void)hipFree(c->red.d_moments);
-    if (c->red.d_partials) (void)hipFree(c->red.d_partials);
-    if (c->red.host) (void)hipHostFree(c->red.host);
-    if (c->red.d_mean) (void)hipFree(c->red.d_mean);
-    if (c->red.d_var) (void)hipFree(c->red.d_var);
-    if (c->red.d_gram_partials) (void)hipFree(c->red.d_gram_partials);
-    if (c->red.d_gram) (void)hipFree(c->red.d_gram);
-    if (c->red.gram_host) (void)hipHostFree(c->red.gram_host);
-    if (c->stage.dev) (void)hipFree(c->stage.dev);
     if (c->observe.table) (void)hipFree(c->observe.table);
-    if (c->observe.d_partials) (void)hipFree(c->observe.d_partials);
-    if (c->observe.d_out) (void)hipFree(c->observe.d_out);
-    if (c->observe.host) (void)hipHostFree(c->observe.host);
-    if (c->lgram.d_lists) (void)hipFree(c->lgram.d_lists);
-    if (c->lgram.h_lists) (void)hipHostFree(c->lgram.h_lists);
-    if (c->lgram.d_operands) (void)hipFree(c->lgram.d_operands);
-    if (c->lgram.d_out) (void)hipFree(c->lgram.d_out);
-    if (c->lgram.h_out) (void)hipHostFree(c->lgram.h_out);
-    if (c->etkf.d_in) (void)hipFree(c->etkf.d_in);
-    if (c->etkf.h_in) (void)hipHostFree(c->etkf.h_in);
-    if (c->etkf.d_out) (void)hipFree(c->etkf.d_out);
-    if (c->etkf.h_out) (void)hipHostFree(c->etkf.h_out);
-    if (c->etkf.d_status) (void)hipFree(c->etkf.d_status);
-    if (c->etkf.h_status) (void)hipHostFree(c->etkf.h_status);
     for (hipEvent_t ev : c->xform.copied)
         if (ev) (void)hipEventDestroy(ev);
-    if (c->xform.dev) (void)hipFree(c->xform.dev);
-    if (c->xform.host) (void)hipHostFree(c->xform.host);
     if (c->lattice.copied) (void)hipEventDestroy(c->lattice.copied);
-    if (c->lattice.dev) (void)hipFree(c->lattice.dev);
-    if (c->lattice.host) (void)hipHostFree(c->lattice.host);
     if (c->d_partials) (void)hipFree(c->d_partials);
     if (c->scalar_ready) (void)hipEventDestroy(c->scalar_ready);
     if (c->own_arena && c->arena) (void)hipFree(c->arena);
@@ -1896,7 +1897,7 @@ int fluid_destroy(fluid_ctx* c)
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     if (g_cached == c) g_cached = nullptr;
-    delete c;
+    delete c;                                    // (frees every Scratch: nothing runs any more, see the waits above)
     return FLUID_OK;
 }
 
@@ -2431,56 +2432,30 @@ int fluid_absmax_velocity(fluid_ctx* c, int u, int v, float* out)
 }
 
 // ---- ensemble diagnostics -----------------------------------------------------
-// Results and scratch are library-owned and outside the arena (fluid_ctx.h: EnsembleReduce), allocated by the first call
-// that needs them.  An allocation that fails leaves the context as it was: what it had begun is freed again.
+// Results and scratch are Scratch buffers (fluid_ctx.h: EnsembleReduce), reserved by the first call that needs them.
 static int ensure_member_results(fluid_ctx* c)
 {
     EnsembleReduce& r = c->red;
-    if (r.d_max) return FLUID_OK;
     const size_t m = (size_t)c->members;
-    const size_t parts = m * (size_t)fluid::moment_blocks(c->n, c->members);
-    unsigned int* d_max = nullptr;
-    double2 *d_mom = nullptr, *d_part = nullptr;
-    char* host = nullptr;
-    hipError_t e = hipMalloc((void**)&d_max, m * sizeof(unsigned));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_mom, m * sizeof(double2));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_part, parts * sizeof(double2));
-    if (e == hipSuccess) e = hipHostMalloc((void**)&host, m * sizeof(double2), hipHostMallocDefault);
-    if (e != hipSuccess) {
-        if (d_max) (void)hipFree(d_max);
-        if (d_mom) (void)hipFree(d_mom);
-        if (d_part) (void)hipFree(d_part);
-        (void)hipGetLastError();
-        return fail(e == hipErrorOutOfMemory ? FLUID_E_NOMEM : FLUID_E_HIP, "ensemble diagnostics: allocating the results of %d members: %s",
-                    c->members, hipGetErrorString(e));
-    }
-    r.d_max = d_max;
-    r.d_moments = d_mom;
-    r.d_partials = d_part;
-    r.host = host;
-    return FLUID_OK;
+    const char* call = "ensemble diagnostics";
+    TRY(reserve(c, r.max, m * sizeof(unsigned), false, call, "result words"));
+    TRY(reserve(c, r.moments, m * sizeof(double2), true, call, "moments"));
+    return reserve(c, r.partials, m * (size_t)fluid::moment_blocks(c->n, c->members) * sizeof(double2), false, call, "partial moments");
 }
 
 // the two statistics fields: zeroed once, so their pad columns (which no kernel writes) stay zero
 static int ensure_stats(fluid_ctx* c)
 {
-    EnsembleReduce& r = c->red;
-    if (r.d_mean) return FLUID_OK;
     const size_t bytes = c->field_floats * sizeof(float);
-    float *mean = nullptr, *var = nullptr;
-    hipError_t e = hipMalloc((void**)&mean, bytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&var, bytes);
-    if (e == hipSuccess) e = hipMemsetAsync(mean, 0, bytes, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(var, 0, bytes, c->stream);
-    if (e != hipSuccess) {
-        if (mean) (void)hipFree(mean);
-        if (var) (void)hipFree(var);
-        (void)hipGetLastError();
-        return fail(e == hipErrorOutOfMemory ? FLUID_E_NOMEM : FLUID_E_HIP, "fluid_ensemble_stats: allocating two fields of %zu bytes: %s", bytes,
-                    hipGetErrorString(e));
+    for (Scratch* s : {&c->red.mean, &c->red.var}) {
+        bool grew = false;
+        TRY(reserve(c, *s, bytes, false, "fluid_ensemble_stats", "a statistics field", &grew));
+        if (!grew) continue;
+        if (const hipError_t e = hipMemsetAsync(s->dev, 0, bytes, c->stream); e != hipSuccess) {
+            s->release();                          // nothing was enqueued on it; never kept with pads that are not zero
+            return fail(FLUID_E_HIP, "fluid_ensemble_stats: hipMemsetAsync: %s", hipGetErrorString(e));
+        }
     }
-    r.d_mean = mean;
-    r.d_var = var;
     return FLUID_OK;
 }
 
@@ -2488,9 +2463,9 @@ static int ensure_stats(fluid_ctx* c)
 static int member_words_to_host(fluid_ctx* c, float* out)
 {
     const size_t bytes = (size_t)c->members * sizeof(unsigned);
-    HIP_TRY(hipMemcpyAsync(c->red.host, c->red.d_max, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->red.moments.host, c->red.max.dev, bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    std::memcpy(out, c->red.host, bytes);
+    std::memcpy(out, c->red.moments.host, bytes);
     return FLUID_OK;
 }
 
@@ -2505,8 +2480,8 @@ int fluid_residual_members(fluid_ctx* c, int x, int x0, const float* alpha, cons
     TRY(materialize(c, {x, x0}));
     const float2* mab = nullptr;
     TRY(member_pairs(c, {alpha, c->members}, {beta, c->members}, &mab));
-    HIP_TRY(hipMemsetAsync(c->red.d_max, 0, (size_t)c->members * sizeof(unsigned), c->stream));
-    fluid::launch_residual(c->stream, c->st, c->ptr(x), c->ptr(x0), c->pitch, c->n, c->own0, c->own1, alpha[0], beta[0], c->red.d_max,
+    HIP_TRY(hipMemsetAsync(c->red.max.d<unsigned>(), 0, (size_t)c->members * sizeof(unsigned), c->stream));
+    fluid::launch_residual(c->stream, c->st, c->ptr(x), c->ptr(x0), c->pitch, c->n, c->own0, c->own1, alpha[0], beta[0], c->red.max.d<unsigned>(),
                            c->mb(), /*rstride=*/1, mab);
     HIP_TRY(hipGetLastError());
     return member_words_to_host(c, out);
@@ -2520,8 +2495,8 @@ int fluid_absmax_velocity_members(fluid_ctx* c, int u, int v, float* out)
     if (c->members == 1) return fluid_absmax_velocity(c, u, v, out);
     TRY(ensure_member_results(c));
     TRY(materialize(c, {u, v}));
-    HIP_TRY(hipMemsetAsync(c->red.d_max, 0, (size_t)c->members * sizeof(unsigned), c->stream));
-    fluid::launch_absmax2(c->stream, c->st, c->ptr(u), c->ptr(v), c->pitch, c->n, c->own0, c->own1, c->red.d_max, c->mb(), /*rstride=*/1);
+    HIP_TRY(hipMemsetAsync(c->red.max.d<unsigned>(), 0, (size_t)c->members * sizeof(unsigned), c->stream));
+    fluid::launch_absmax2(c->stream, c->st, c->ptr(u), c->ptr(v), c->pitch, c->n, c->own0, c->own1, c->red.max.d<unsigned>(), c->mb(), /*rstride=*/1);
     HIP_TRY(hipGetLastError());
     return member_words_to_host(c, out);
 }
@@ -2541,39 +2516,16 @@ int fluid_member_moments(fluid_ctx* c, int field, double* sum, double* sumsq)
     TRY(refuse_slabs(c, "fluid_member_moments"));
     TRY(ensure_member_results(c));
     TRY(materialize(c, field));
-    fluid::launch_member_moments(c->stream, c->st, c->ptr(field), c->pitch, c->n, c->mb(), c->red.d_partials, c->red.d_moments);
+    fluid::launch_member_moments(c->stream, c->st, c->ptr(field), c->pitch, c->n, c->mb(), c->red.partials.d<double2>(),
+                                 c->red.moments.d<double2>());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(c->red.host, c->red.d_moments, (size_t)c->members * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->red.moments.host, c->red.moments.dev, (size_t)c->members * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    const double2* h = reinterpret_cast<const double2*>(c->red.host);
+    const double2* h = c->red.moments.h<double2>();
     for (int m = 0; m < c->members; ++m) {
         if (sum) sum[m] = h[m].x;
         if (sumsq) sumsq[m] = h[m].y;
     }
-    return FLUID_OK;
-}
-
-// the scratch and the result of fluid_member_gram, sized for this context's N and M once
-static int ensure_gram(fluid_ctx* c)
-{
-    EnsembleReduce& r = c->red;
-    if (r.d_gram) return FLUID_OK;
-    const int mp = fluid::gram_padded(c->members);
-    const size_t matrix = (size_t)mp * mp * sizeof(double), parts = matrix * (size_t)fluid::gram_blocks(c->n, c->members);
-    double *d_part = nullptr, *d_out = nullptr, *host = nullptr;
-    hipError_t e = hipMalloc((void**)&d_part, parts);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_out, matrix);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&host, matrix, hipHostMallocDefault);
-    if (e != hipSuccess) {
-        if (d_part) (void)hipFree(d_part);
-        if (d_out) (void)hipFree(d_out);
-        (void)hipGetLastError();
-        return fail(e == hipErrorOutOfMemory ? FLUID_E_NOMEM : FLUID_E_HIP, "fluid_member_gram: allocating %zu bytes of partial matrices: %s",
-                    parts + matrix, hipGetErrorString(e));
-    }
-    r.d_gram_partials = d_part;
-    r.d_gram = d_out;
-    r.gram_host = host;
     return FLUID_OK;
 }
 
@@ -2586,16 +2538,20 @@ int fluid_member_gram(fluid_ctx* c, int field, int centre, double* gram)
         return fail(FLUID_E_INVALID, "fluid_member_gram: this context has %d members, above FLUID_TRANSFORM_MAX_MEMBERS = %d", c->members,
                     FLUID_TRANSFORM_MAX_MEMBERS);
     TRY(refuse_slabs(c, "fluid_member_gram"));
-    TRY(ensure_gram(c));
+    const int M = c->members, mp = fluid::gram_padded(M);
+    const size_t matrix = (size_t)mp * mp * sizeof(double);
+    EnsembleReduce& r = c->red;                    // sized for this context's N and M: reserved once
+    TRY(reserve(c, r.gram_partials, matrix * (size_t)fluid::gram_blocks(c->n, M), false, "fluid_member_gram", "partial matrices"));
+    TRY(reserve(c, r.gram, matrix, true, "fluid_member_gram", "the result"));
     const float inv = c->st != fluid::STORAGE_F32 ? 1.0f / c->field[field].fscale : 1.0f;      // as pack_range sees the field
     TRY(materialize(c, field, /*keep_scale=*/inv != 1.0f));
-    fluid::launch_member_gram(c->stream, c->st, c->ptr(field), c->pitch, c->n, c->mb(), inv, centre != 0, c->red.d_gram_partials, c->red.d_gram);
+    fluid::launch_member_gram(c->stream, c->st, c->ptr(field), c->pitch, c->n, c->mb(), inv, centre != 0, r.gram_partials.d<double>(),
+                              r.gram.d<double>());
     HIP_TRY(hipGetLastError());
-    const int M = c->members, mp = fluid::gram_padded(M);
-    HIP_TRY(hipMemcpyAsync(c->red.gram_host, c->red.d_gram, (size_t)mp * mp * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(r.gram.host, r.gram.dev, matrix, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     for (int k = 0; k < M; ++k)                    // the upper triangle was computed; the lower one is its mirror
-        for (int m = k; m < M; ++m) gram[(size_t)k * M + m] = gram[(size_t)m * M + k] = c->red.gram_host[(size_t)k * mp + m];
+        for (int m = k; m < M; ++m) gram[(size_t)k * M + m] = gram[(size_t)m * M + k] = r.gram.h<double>()[(size_t)k * mp + m];
     return FLUID_OK;
 }
 
@@ -2606,13 +2562,14 @@ int fluid_ensemble_stats(fluid_ctx* c, int field, float* mean, float* variance)
     TRY(refuse_slabs(c, "fluid_ensemble_stats"));
     TRY(ensure_stats(c));
     TRY(materialize(c, field));
-    fluid::launch_ensemble_stats(c->stream, c->st, c->ptr(field), c->pitch, c->n, c->mb(), c->red.d_mean, c->red.d_var);
+    fluid::launch_ensemble_stats(c->stream, c->st, c->ptr(field), c->pitch, c->n, c->mb(), c->red.mean.d<float>(),
+                                 c->red.var.d<float>());
     HIP_TRY(hipGetLastError());
     c->red.have_stats = true;
     if (!mean && !variance) return FLUID_OK;       // computed only: the results stay on the device (fluid_ensemble_stats_ptr)
     const size_t hp = (size_t)c->w * sizeof(float), dp = (size_t)c->pitch * sizeof(float);
-    if (mean) HIP_TRY(hipMemcpy2DAsync(mean, hp, c->red.d_mean + XOFF, dp, hp, (size_t)c->w, hipMemcpyDeviceToHost, c->stream));
-    if (variance) HIP_TRY(hipMemcpy2DAsync(variance, hp, c->red.d_var + XOFF, dp, hp, (size_t)c->w, hipMemcpyDeviceToHost, c->stream));
+    if (mean) HIP_TRY(hipMemcpy2DAsync(mean, hp, c->red.mean.d<float>() + XOFF, dp, hp, (size_t)c->w, hipMemcpyDeviceToHost, c->stream));
+    if (variance) HIP_TRY(hipMemcpy2DAsync(variance, hp, c->red.var.d<float>() + XOFF, dp, hp, (size_t)c->w, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return FLUID_OK;
 }
@@ -2622,8 +2579,8 @@ int fluid_ensemble_stats_ptr(fluid_ctx* c, void** mean_dev, void** variance_dev)
     if (!c) return fail(FLUID_E_INVALID, "fluid_ensemble_stats_ptr: null context");
     TRY(refuse_slabs(c, "fluid_ensemble_stats_ptr"));
     if (!c->red.have_stats) return fail(FLUID_E_INVALID, "fluid_ensemble_stats_ptr: no fluid_ensemble_stats has run on this context yet");
-    if (mean_dev) *mean_dev = c->red.d_mean;
-    if (variance_dev) *variance_dev = c->red.d_var;
+    if (mean_dev) *mean_dev = c->red.mean.dev;
+    if (variance_dev) *variance_dev = c->red.var.dev;
     return FLUID_OK;
 }
 
@@ -2805,29 +2762,6 @@ static size_t transform_table_bytes(int members)
     return (size_t)members * (size_t)fluid::transform_padded(members) * sizeof(double) + (size_t)members * sizeof(unsigned long long);
 }
 
-static int ensure_transform(fluid_ctx* c, const char* call)
-{
-    TransformTables& t = c->xform;
-    if (t.dev) return FLUID_OK;
-    const size_t slot = const_pad(transform_table_bytes(c->members)), bytes = slot * TransformTables::kSlots;
-    char *dev = nullptr, *host = nullptr;
-    hipError_t e = hipMalloc((void**)&dev, bytes);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&host, bytes, hipHostMallocDefault);
-    for (int k = 0; e == hipSuccess && k < TransformTables::kSlots; ++k)
-        if (!t.copied[k]) e = hipEventCreateWithFlags(&t.copied[k], hipEventDisableTiming);
-    if (e != hipSuccess) {          // (events already made stay with the context: the next call takes them, fluid_destroy frees them)
-        (void)hipGetLastError();
-        if (dev) (void)hipFree(dev);
-        if (host) (void)hipHostFree(host);
-        return fail(e == hipErrorOutOfMemory ? FLUID_E_NOMEM : FLUID_E_HIP, "%s: allocating weight tables of %zu bytes: %s", call, bytes,
-                    hipGetErrorString(e));
-    }
-    t.dev = dev;
-    t.host = host;
-    t.slot = slot;
-    return FLUID_OK;
-}
-
 // One call's table on its way to the device: `weights` -- M * M floats, weights[k * M + m] the weight of OLD member k in
 // (the increment of) NEW member m, all finite (the entry points check) -- widened into the next slot of the ring and
 // copied on the context's stream.  What the kernels take of it: the device addresses, `used` (a bit for every column with
@@ -2842,11 +2776,13 @@ struct StagedTable {
 static int stage_transform_table(fluid_ctx* c, const char* call, const float* weights, StagedTable* out)
 {
     const int M = c->members, MP = fluid::transform_padded(M);
-    TRY(ensure_transform(c, call));
     TransformTables& t = c->xform;
+    const size_t slot = const_pad(transform_table_bytes(M));
+    TRY(reserve(c, t.tables, slot * TransformTables::kSlots, true, call, "weight tables"));
+    for (hipEvent_t& ev : t.copied) TRY(ensure_event(&ev));
     const int s = t.next;
     if (t.in_use[s]) HIP_TRY(hipEventSynchronize(t.copied[s]));      // a formality unless kSlots calls are still queued
-    double* table = reinterpret_cast<double*>(t.host + (size_t)s * t.slot);
+    double* table = t.tables.h<double>((size_t)s * slot);
     unsigned long long* bits = reinterpret_cast<unsigned long long*>(table + (size_t)M * MP);
     StagedTable st;
     for (int k = 0; k < M; ++k) {
@@ -2860,12 +2796,11 @@ static int stage_transform_table(fluid_ctx* c, const char* call, const float* we
         bits[k] = row;
         st.used |= row;
     }
-    char* dev = t.dev + (size_t)s * t.slot;
-    HIP_TRY(hipMemcpyAsync(dev, table, transform_table_bytes(M), hipMemcpyHostToDevice, c->stream));
+    st.table = t.tables.d<double>((size_t)s * slot);
+    HIP_TRY(hipMemcpyAsync(t.tables.d<char>((size_t)s * slot), table, transform_table_bytes(M), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipEventRecord(t.copied[s], c->stream));
     t.in_use[s] = true;
     t.next = (s + 1) % TransformTables::kSlots;
-    st.table = reinterpret_cast<const double*>(dev);
     st.bits = reinterpret_cast<const unsigned long long*>(st.table + (size_t)M * MP);
     *out = st;
     return FLUID_OK;
@@ -3040,28 +2975,10 @@ int fluid_taper_gaspari_cohn(fluid_ctx* c, float col, float row, float hw, void*
 static int ensure_lattice(fluid_ctx* c, const char* call, size_t bytes)
 {
     LatticeNodeTables& t = c->lattice;
-    if (t.bytes >= bytes) return FLUID_OK;
-    char *dev = nullptr, *host = nullptr;
-    hipError_t e = hipMalloc((void**)&dev, bytes);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&host, bytes, hipHostMallocDefault);
-    if (e == hipSuccess && !t.copied) e = hipEventCreateWithFlags(&t.copied, hipEventDisableTiming);
-    if (e != hipSuccess) {          // (the old, smaller buffers stay: the context is as it was)
-        (void)hipGetLastError();
-        if (dev) (void)hipFree(dev);
-        if (host) (void)hipHostFree(host);
-        return fail(e == hipErrorOutOfMemory ? FLUID_E_NOMEM : FLUID_E_HIP, "%s: allocating node tables of %zu bytes: %s", call, bytes,
-                    hipGetErrorString(e));
-    }
-    if (t.dev) {                    // growing: earlier lattice launches may still read the old tables
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        (void)hipFree(t.dev);
-        (void)hipHostFree(t.host);
-        t.in_use = false;
-    }
-    t.dev = dev;
-    t.host = host;
-    t.bytes = bytes;
-    return FLUID_OK;
+    bool grew = false;
+    TRY(reserve(c, t.tables, bytes, true, call, "node tables", &grew));
+    if (grew) t.in_use = false;     // (the stream has been waited for: nothing copies out of a twin any more)
+    return ensure_event(&t.copied);
 }
 
 int fluid_transform_members_lattice(fluid_ctx* c, const int* fields, int nfields, const float* increments, int nodes_row, int nodes_col,
@@ -3097,8 +3014,8 @@ int fluid_transform_members_lattice(fluid_ctx* c, const int* fields, int nfields
         TRY(ensure_lattice(c, call, bytes));
         LatticeNodeTables& t = c->lattice;
         if (t.in_use) HIP_TRY(hipEventSynchronize(t.copied));       // the call before may still be copying out of the twin
-        double* table = reinterpret_cast<double*>(t.host);
-        unsigned long long* bits = reinterpret_cast<unsigned long long*>(t.host + table_bytes);
+        double* table = t.tables.h<double>();
+        unsigned long long* bits = t.tables.h<unsigned long long>(table_bytes);
         unsigned long long* cols = bits + (size_t)nodes * M;
         for (int node = 0; node < nodes; ++node) {
             unsigned long long all = 0;
@@ -3115,11 +3032,11 @@ int fluid_transform_members_lattice(fluid_ctx* c, const int* fields, int nfields
             }
             cols[node] = all;
         }
-        HIP_TRY(hipMemcpyAsync(t.dev, t.host, bytes, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(t.tables.dev, t.tables.host, bytes, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipEventRecord(t.copied, c->stream));
         t.in_use = true;
-        dev.table = reinterpret_cast<const double*>(t.dev);
-        dev.bits = reinterpret_cast<const unsigned long long*>(t.dev + table_bytes);
+        dev.table = t.tables.d<double>();
+        dev.bits = t.tables.d<unsigned long long>(table_bytes);
         dev.cols = dev.bits + (size_t)nodes * M;
     }
     const fluid::Lattice lat = {nodes_row, nodes_col, row0, col0, step};
@@ -3203,19 +3120,9 @@ int fluid_relax_spread(fluid_ctx* c, const int* fields, int nfields, const void*
 // tools/ensemble_io_timing.py records what the bulk copies cost with it.
 static int ensure_stage(fluid_ctx* c, const char* call)
 {
-    if (c->stage.dev) return FLUID_OK;
     const size_t member_bytes = member_cells(c) * sizeof(float);
-    const int g = (int)std::max<size_t>(1, std::min<size_t>((size_t)c->members, ((size_t)64 << 20) / member_bytes));
-    float* dev = nullptr;
-    const hipError_t e = hipMalloc((void**)&dev, (size_t)g * member_bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(e == hipErrorOutOfMemory ? FLUID_E_NOMEM : FLUID_E_HIP, "%s: allocating a staging buffer of %zu bytes: %s", call,
-                    (size_t)g * member_bytes, hipGetErrorString(e));
-    }
-    c->stage.dev = dev;
-    c->stage.members = g;
-    return FLUID_OK;
+    c->stage.members = (int)std::max<size_t>(1, std::min<size_t>((size_t)c->members, ((size_t)64 << 20) / member_bytes));
+    return reserve(c, c->stage.buf, (size_t)c->stage.members * member_bytes, false, call, "staging buffer");
 }
 
 // fluid_download_members (factor 0) / fluid_download_members_coarse: the same staging buffer, in groups of as many (coarse)
@@ -3232,8 +3139,8 @@ static int download_body(fluid_ctx* c, const char* call, int field, int factor, 
     const int group = (int)std::min<size_t>((size_t)c->members, (size_t)c->stage.members * (member_cells(c) / cells));
     for (int first = 0; first < c->members; first += group) {      // groups in stream order: the buffer is reused
         const int count = std::min(group, c->members - first);
-        TRY(pack_range(c, field, first, count, c->stage.dev, cells, factor));
-        HIP_TRY(hipMemcpyAsync(host + (size_t)first * cells, c->stage.dev, (size_t)count * cells * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        TRY(pack_range(c, field, first, count, c->stage.dev(), cells, factor));
+        HIP_TRY(hipMemcpyAsync(host + (size_t)first * cells, c->stage.dev(), (size_t)count * cells * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     return FLUID_OK;
@@ -3257,8 +3164,8 @@ int fluid_upload_members(fluid_ctx* c, int field, const float* host)
     const size_t cells = member_cells(c);
     for (int first = 0; first < c->members; first += c->stage.members) {
         const int count = std::min(c->stage.members, c->members - first);
-        HIP_TRY(hipMemcpyAsync(c->stage.dev, host + (size_t)first * cells, (size_t)count * cells * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        TRY(unpack_launch(c, field, first, count, c->stage.dev, cells));
+        HIP_TRY(hipMemcpyAsync(c->stage.dev(), host + (size_t)first * cells, (size_t)count * cells * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        TRY(unpack_launch(c, field, first, count, c->stage.dev(), cells));
     }
     wrote(c, field, kEverywhere);              // every member was replaced: an unpack of all members, in groups
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -3462,45 +3369,15 @@ int fluid_observe_members_host(fluid_ctx* c, int field, float* host)
         for (size_t p0 = 0; p0 < P; p0 += piece) {                       // (one piece unless the network outgrows the buffer: count is 1 then)
             const size_t np = std::min(piece, P - p0);
             fluid::launch_observe_members(c->stream, c->st, x, c->pitch, {count, c->field_floats}, from.inv, from.sources(), first, pts, (int)p0,
-                                          (int)np, c->stage.dev, np);
+                                          (int)np, c->stage.dev(), np);
             HIP_TRY(hipGetLastError());
             if (np == P)
-                HIP_TRY(hipMemcpyAsync(host + (size_t)first * P, c->stage.dev, (size_t)count * P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+                HIP_TRY(hipMemcpyAsync(host + (size_t)first * P, c->stage.dev(), (size_t)count * P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
             else
-                HIP_TRY(hipMemcpyAsync(host + (size_t)first * P + p0, c->stage.dev, np * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+                HIP_TRY(hipMemcpyAsync(host + (size_t)first * P + p0, c->stage.dev(), np * sizeof(float), hipMemcpyDeviceToHost, c->stream));
         }
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
-    return FLUID_OK;
-}
-
-// the scratch and the result of fluid_observation_gram: partials for the blocks of this network (a larger network later:
-// allocated anew, the old ones freed after it), the folded result and its pinned twin
-static int ensure_observation_gram(fluid_ctx* c)
-{
-    Observation& o = c->observe;
-    const int blocks = fluid::observation_gram_blocks(o.points, c->members);
-    const size_t entries = fluid::observation_gram_entries(c->members) * sizeof(double), parts = entries * (size_t)blocks;
-    if (o.d_out && blocks <= o.partial_blocks) return FLUID_OK;
-    double *d_part = nullptr, *d_out = o.d_out, *host = o.host;
-    hipError_t e = hipMalloc((void**)&d_part, parts);
-    if (e == hipSuccess && !d_out) e = hipMalloc((void**)&d_out, entries);
-    if (e == hipSuccess && !host) e = hipHostMalloc((void**)&host, entries, hipHostMallocDefault);
-    if (e != hipSuccess) {
-        if (d_part) (void)hipFree(d_part);
-        if (d_out && d_out != o.d_out) (void)hipFree(d_out);
-        (void)hipGetLastError();
-        return fail(e == hipErrorOutOfMemory ? FLUID_E_NOMEM : FLUID_E_HIP, "fluid_observation_gram: allocating %zu bytes of partial results: %s",
-                    parts + entries, hipGetErrorString(e));
-    }
-    if (o.d_partials) {                                                  // (every earlier call ended in a wait: nothing reads them)
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        (void)hipFree(o.d_partials);
-    }
-    o.d_partials = d_part;
-    o.partial_blocks = blocks;
-    o.d_out = d_out;
-    o.host = host;
     return FLUID_OK;
 }
 
@@ -3520,22 +3397,26 @@ int fluid_observation_gram(fluid_ctx* c, int field, int centre, const float* obs
         for (size_t p = 0; p < P; ++p)
             if (!std::isfinite(inv_sigma[p]))
                 return fail(FLUID_E_INVALID, "fluid_observation_gram: inv_sigma[%zu] (point %zu) is not finite", p, p);
-    TRY(ensure_observation_gram(c));
+    const int M = c->members, mp = fluid::gram_padded(M);
+    const size_t entries = fluid::observation_gram_entries(M) * sizeof(double);
+    // partials for the blocks of this network (a larger network later: they grow), the folded result and its twin
+    TRY(reserve(c, o.partials, entries * (size_t)fluid::observation_gram_blocks(o.points, M), false, "fluid_observation_gram", "partial results"));
+    TRY(reserve(c, o.result, entries, true, "fluid_observation_gram", "the result"));
     if (obs) HIP_TRY(hipMemcpyAsync(o.obs(), obs, P * sizeof(float), hipMemcpyHostToDevice, c->stream));
     if (inv_sigma) HIP_TRY(hipMemcpyAsync(o.sigma(), inv_sigma, P * sizeof(float), hipMemcpyHostToDevice, c->stream));
     ObservedFrom from;
     TRY(settle_for_observing(c, field, &from));
     fluid::launch_observation_gram(c->stream, c->st, from.x, c->pitch, c->mb(), from.inv, from.sources(), observation_points(c), centre != 0,
-                                   obs ? o.obs() : nullptr, inv_sigma ? o.sigma() : nullptr, o.d_partials, o.d_out);
+                                   obs ? o.obs() : nullptr, inv_sigma ? o.sigma() : nullptr, o.partials.d<double>(), o.result.d<double>());
     HIP_TRY(hipGetLastError());
-    const int M = c->members, mp = fluid::gram_padded(M);
-    HIP_TRY(hipMemcpyAsync(o.host, o.d_out, fluid::observation_gram_entries(M) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(o.result.host, o.result.dev, entries, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    const double* host = o.result.h<double>();
     for (int k = 0; k < M; ++k)                    // the upper triangle was computed; the lower one is its mirror
-        for (int m = k; m < M; ++m) gram[(size_t)k * M + m] = gram[(size_t)m * M + k] = o.host[(size_t)k * mp + m];
+        for (int m = k; m < M; ++m) gram[(size_t)k * M + m] = gram[(size_t)m * M + k] = host[(size_t)k * mp + m];
     if (rhs)
-        for (int k = 0; k < M; ++k) rhs[k] = o.host[(size_t)mp * mp + k];
-    if (dd) *dd = o.host[(size_t)mp * mp + mp];
+        for (int k = 0; k < M; ++k) rhs[k] = host[(size_t)mp * mp + k];
+    if (dd) *dd = host[(size_t)mp * mp + mp];
     return FLUID_OK;
 }
 
@@ -3572,34 +3453,10 @@ static void lattice_pairs(const fluid_ctx* c, int nodes_row, int nodes_col, int 
 }
 }  // extern "C++"
 
-// one of the call's buffers, grown to `bytes`: the new ones are allocated before the old ones are freed, so a failure leaves
-// everything as it was (every earlier call ended in a wait: nothing reads the old ones)
-static int grow_lattice_gram(const char* call, const char* what, char** dev, char** host, size_t* room, size_t bytes)
-{
-    if (*room >= bytes) return FLUID_OK;
-    char *d = nullptr, *h = nullptr;
-    hipError_t e = hipMalloc((void**)&d, bytes);
-    if (e == hipSuccess && host) e = hipHostMalloc((void**)&h, bytes, hipHostMallocDefault);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        if (d) (void)hipFree(d);
-        return fail(e == hipErrorOutOfMemory ? FLUID_E_NOMEM : FLUID_E_HIP, "%s: allocating %zu bytes of %s: %s", call, bytes, what,
-                    hipGetErrorString(e));
-    }
-    if (*dev) (void)hipFree(*dev);
-    *dev = d;
-    if (host) {
-        if (*host) (void)hipHostFree(*host);
-        *host = h;
-    }
-    *room = bytes;
-    return FLUID_OK;
-}
-
 // What fluid_observation_gram_lattice and fluid_analyse_lattice share, under the caller's name: the refusals beyond the
 // call's own pointers, the point lists (built, cached and uploaded here and nowhere else), and the two launches that leave
-// every node's result in LatticeGram::d_out.  Nothing is waited for, except where a buffer an analysis in flight may still
-// read is about to be rewritten or freed.
+// every node's result in LatticeGram::out.  Nothing is waited for, except where the lists an analysis in flight may still
+// read are about to be rewritten, or a buffer grows (reserve).
 static int enqueue_lattice_gram(fluid_ctx* c, const char* call, int field, int centre, const float* obs, const float* inv_sigma, int nodes_row,
                                 int nodes_col, int row0, int col0, int step, float hw)
 {
@@ -3645,14 +3502,13 @@ static int enqueue_lattice_gram(fluid_ctx* c, const char* call, int field, int c
     const int M = c->members, mp = fluid::gram_padded(M);
     const size_t E = fluid::observation_gram_entries(M), start_bytes = ((B + 1) * sizeof(int) + 7) & ~(size_t)7;
     const size_t list_bytes = start_bytes + (size_t)pairs * sizeof(int2);
-    if (g.list_bytes < list_bytes) g.valid = false;                      // (not cached, then: new lists are about to replace the old)
-    TRY(grow_lattice_gram(call, "point lists", &g.d_lists, &g.h_lists, &g.list_bytes, list_bytes));
-    TRY(grow_lattice_gram(call, "point operands", reinterpret_cast<char**>(&g.d_operands), nullptr, &g.operand_bytes,
-                          P * (size_t)(mp + 2) * sizeof(double)));
-    TRY(grow_lattice_gram(call, "node results", reinterpret_cast<char**>(&g.d_out), reinterpret_cast<char**>(&g.h_out), &g.out_bytes,
-                          B * E * sizeof(double)));
-    int* h_start = reinterpret_cast<int*>(g.h_lists);
-    int2* h_entry = reinterpret_cast<int2*>(g.h_lists + start_bytes);
+    bool grew = false;
+    TRY(reserve(c, g.lists, list_bytes, true, call, "point lists", &grew));
+    if (grew) g.valid = false;                                           // (not cached, then) the old lists went with the old buffer
+    TRY(reserve(c, g.operands, P * (size_t)(mp + 2) * sizeof(double), false, call, "point operands"));
+    TRY(reserve(c, g.out, B * E * sizeof(double), true, call, "node results"));
+    int* h_start = g.lists.h<int>();
+    int2* h_entry = g.lists.h<int2>(start_bytes);
     if (!cached) {
         g.valid = false;
         std::vector<int> at(start.begin(), start.end() - 1);             // where the next entry of a node goes
@@ -3667,7 +3523,7 @@ static int enqueue_lattice_gram(fluid_ctx* c, const char* call, int field, int c
         for (size_t b = 0; b < B; ++b) inside = inside && at[b] == start[b + 1];
         if (!inside) return fail(FLUID_E_INVALID, "%s: the point lists do not match their count (internal error)", call);
         std::memcpy(h_start, start.data(), (B + 1) * sizeof(int));
-        HIP_TRY(hipMemcpyAsync(g.d_lists, g.h_lists, list_bytes, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(g.lists.dev, g.lists.host, list_bytes, hipMemcpyHostToDevice, c->stream));
         g.nodes_row = nodes_row; g.nodes_col = nodes_col; g.row0 = row0; g.col0 = col0; g.step = step; g.c = hw;
         g.pairs = pairs;
         g.valid = true;
@@ -3676,9 +3532,10 @@ static int enqueue_lattice_gram(fluid_ctx* c, const char* call, int field, int c
     if (inv_sigma) HIP_TRY(hipMemcpyAsync(o.sigma(), inv_sigma, P * sizeof(float), hipMemcpyHostToDevice, c->stream));
     ObservedFrom from;
     TRY(settle_for_observing(c, field, &from));
-    const fluid::LatticeLists lists = {reinterpret_cast<const int*>(g.d_lists), reinterpret_cast<const int2*>(g.d_lists + start_bytes), (int)B};
+    const fluid::LatticeLists lists = {g.lists.d<int>(), g.lists.d<int2>(start_bytes), (int)B};
     fluid::launch_observation_gram_lattice(c->stream, c->st, from.x, c->pitch, c->mb(), from.inv, from.sources(), observation_points(c), centre != 0,
-                                           obs ? o.obs() : nullptr, inv_sigma ? o.sigma() : nullptr, g.d_operands, lists, g.d_out);
+                                           obs ? o.obs() : nullptr, inv_sigma ? o.sigma() : nullptr, g.operands.d<double>(), lists,
+                                           g.out.d<double>());
     HIP_TRY(hipGetLastError());
     return FLUID_OK;
 }
@@ -3695,13 +3552,13 @@ int fluid_observation_gram_lattice(fluid_ctx* c, int field, int centre, const fl
     const size_t B = (size_t)nodes_row * (size_t)nodes_col;
     const int M = c->members, mp = fluid::gram_padded(M);
     const size_t E = fluid::observation_gram_entries(M);
-    const int* h_start = reinterpret_cast<const int*>(g.h_lists);
-    HIP_TRY(hipMemcpyAsync(g.h_out, g.d_out, B * E * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    const int* h_start = g.lists.h<int>();
+    HIP_TRY(hipMemcpyAsync(g.out.host, g.out.dev, B * E * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->etkf.in_flight = false;
     for (size_t b = 0; b < B; ++b) {
         const int count = h_start[b + 1] - h_start[b];
-        const double* r = g.h_out + b * E;
+        const double* r = g.out.h<double>() + b * E;
         double* gm = gram + b * (size_t)M * M;
         if (counts) counts[b] = count;
         for (int k = 0; k < M; ++k)                // k <= m was computed (an empty node: nothing was); the rest is its mirror
@@ -3755,49 +3612,29 @@ int fluid_etkf_increments(fluid_ctx* c, int nodes, const double* gram, const dou
     EtkfBuffers& e = c->etkf;
     const size_t gram_bytes = B * MM * sizeof(double), rhs_bytes = B * M * sizeof(double), word_bytes = B * sizeof(int);
     const size_t inc_bytes = B * MM * sizeof(float);
-    TRY(grow_lattice_gram(call, "operands", &e.d_in, &e.h_in, &e.in_bytes, gram_bytes + rhs_bytes + word_bytes));
-    TRY(grow_lattice_gram(call, "results", &e.d_out, &e.h_out, &e.out_bytes, inc_bytes + word_bytes));
-    std::memcpy(e.h_in, gram, gram_bytes);
-    std::memcpy(e.h_in + gram_bytes, rhs, rhs_bytes);
-    if (counts) std::memcpy(e.h_in + gram_bytes + rhs_bytes, counts, word_bytes);
-    HIP_TRY(hipMemcpyAsync(e.d_in, e.h_in, gram_bytes + rhs_bytes + (counts ? word_bytes : 0), hipMemcpyHostToDevice, c->stream));
+    TRY(reserve(c, e.in, gram_bytes + rhs_bytes + word_bytes, true, call, "operands"));
+    TRY(reserve(c, e.out, inc_bytes + word_bytes, true, call, "results"));
+    std::memcpy(e.in.host, gram, gram_bytes);
+    std::memcpy(e.in.host + gram_bytes, rhs, rhs_bytes);
+    if (counts) std::memcpy(e.in.host + gram_bytes + rhs_bytes, counts, word_bytes);
+    HIP_TRY(hipMemcpyAsync(e.in.dev, e.in.host, gram_bytes + rhs_bytes + (counts ? word_bytes : 0), hipMemcpyHostToDevice, c->stream));
     fluid::EtkfOperands in;
-    in.gram = reinterpret_cast<const double*>(e.d_in);
+    in.gram = e.in.d<double>();
     in.gram_node = MM;
     in.gram_row = (size_t)M;
-    in.rhs = reinterpret_cast<const double*>(e.d_in + gram_bytes);
+    in.rhs = e.in.d<double>(gram_bytes);
     in.rhs_node = (size_t)M;
-    in.counts = counts ? reinterpret_cast<const int*>(e.d_in + gram_bytes + rhs_bytes) : nullptr;
+    in.counts = counts ? e.in.d<int>(gram_bytes + rhs_bytes) : nullptr;
     fluid::EtkfResults out;
-    out.increments = reinterpret_cast<float*>(e.d_out);
-    out.status = reinterpret_cast<int*>(e.d_out + inc_bytes);
+    out.increments = e.out.d<float>();
+    out.status = e.out.d<int>(inc_bytes);
     fluid::launch_etkf_solve(c->stream, M, (double)(M - 1) / (double)rho, in, out, nodes);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(e.h_out, e.d_out, inc_bytes + word_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(e.out.host, e.out.dev, inc_bytes + word_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     e.in_flight = false;
-    std::memcpy(increments, e.h_out, inc_bytes);
-    if (status) std::memcpy(status, e.h_out + inc_bytes, word_bytes);
-    return FLUID_OK;
-}
-
-// the status words of the fused route: one int per node of the largest lattice, and their pinned twin
-static int ensure_etkf_status(fluid_ctx* c, const char* call)
-{
-    EtkfBuffers& e = c->etkf;
-    if (e.d_status) return FLUID_OK;
-    const size_t bytes = (size_t)FLUID_LATTICE_MAX_NODES * sizeof(int);
-    int *dev = nullptr, *host = nullptr;
-    hipError_t err = hipMalloc((void**)&dev, bytes);
-    if (err == hipSuccess) err = hipHostMalloc((void**)&host, bytes, hipHostMallocDefault);
-    if (err != hipSuccess) {
-        (void)hipGetLastError();
-        if (dev) (void)hipFree(dev);
-        return fail(err == hipErrorOutOfMemory ? FLUID_E_NOMEM : FLUID_E_HIP, "%s: allocating %zu bytes of status words: %s", call, bytes,
-                    hipGetErrorString(err));
-    }
-    e.d_status = dev;
-    e.h_status = host;
+    std::memcpy(increments, e.out.host, inc_bytes);
+    if (status) std::memcpy(status, e.out.host + inc_bytes, word_bytes);
     return FLUID_OK;
 }
 
@@ -3810,8 +3647,9 @@ int fluid_analyse_lattice(fluid_ctx* c, int field, const float* obs, const float
     if (!c) return fail(FLUID_E_INVALID, "%s: null context", call);
     TRY(check_transform(c, call, fields, nfields));
     TRY(check_etkf(c, call, rho));
-    TRY(ensure_etkf_status(c, call));
-    // the two Gram launches: every node's C, rhs and dd in LatticeGram::d_out, its point count in the start offsets of d_lists
+    // the status words: one int per node of the largest lattice, and their twin
+    TRY(reserve(c, c->etkf.status, (size_t)FLUID_LATTICE_MAX_NODES * sizeof(int), true, call, "status words"));
+    // the two Gram launches: every node's C, rhs and dd in LatticeGram::out, its point count in the start offsets of the lists
     TRY(enqueue_lattice_gram(c, call, field, /*centre=*/1, obs, inv_sigma, nodes_row, nodes_col, row0, col0, step, hw));
     const int M = c->members, MP = fluid::transform_padded(M), mp = fluid::gram_padded(M), nodes = nodes_row * nodes_col;
     const size_t E = fluid::observation_gram_entries(M);
@@ -3820,18 +3658,18 @@ int fluid_analyse_lattice(fluid_ctx* c, int field, const float* obs, const float
     LatticeNodeTables& t = c->lattice;          // written on the device, in stream order: the pinned twin and its event stay out of it
     LatticeGram& g = c->lgram;
     fluid::EtkfOperands in;
-    in.gram = g.d_out;
+    in.gram = g.out.d<double>();
     in.gram_node = E;
     in.gram_row = (size_t)mp;
-    in.rhs = g.d_out + (size_t)mp * mp;
+    in.rhs = g.out.d<double>() + (size_t)mp * mp;
     in.rhs_node = E;
-    in.counts = reinterpret_cast<const int*>(g.d_lists);
+    in.counts = g.lists.d<int>();
     in.starts = true;
     fluid::EtkfResults out;
-    out.table = reinterpret_cast<double*>(t.dev);
-    out.bits = reinterpret_cast<unsigned long long*>(t.dev + table_bytes);
+    out.table = t.tables.d<double>();
+    out.bits = t.tables.d<unsigned long long>(table_bytes);
     out.cols = out.bits + (size_t)nodes * M;
-    out.status = c->etkf.d_status;
+    out.status = c->etkf.status.d<int>();
     fluid::launch_etkf_solve(c->stream, M, (double)(M - 1) / (double)rho, in, out, nodes);
     HIP_TRY(hipGetLastError());
     c->etkf.analysed = nodes;
@@ -3860,11 +3698,12 @@ int fluid_analyse_lattice_status(fluid_ctx* c, int* solved, int* empty, int* fai
     if (!c) return fail(FLUID_E_INVALID, "%s: null context", call);
     EtkfBuffers& e = c->etkf;
     if (e.analysed == 0) return fail(FLUID_E_INVALID, "%s: no fluid_analyse_lattice has run in this context", call);
-    HIP_TRY(hipMemcpyAsync(e.h_status, e.d_status, (size_t)e.analysed * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(e.status.host, e.status.dev, (size_t)e.analysed * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     e.in_flight = false;
+    const int* status = e.status.h<int>();
     int n[3] = {0, 0, 0};
-    for (int b = 0; b < e.analysed; ++b) n[e.h_status[b] == 0 ? 0 : e.h_status[b] == 1 ? 1 : 2] += 1;
+    for (int b = 0; b < e.analysed; ++b) n[status[b] == 0 ? 0 : status[b] == 1 ? 1 : 2] += 1;
     if (solved) *solved = n[0];
     if (empty) *empty = n[1];
     if (failed) *failed = n[2];
