@@ -148,6 +148,9 @@ SIGNATURES = {
     "fluid_analyse_lattice_status": [_ctx, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
     "fluid_member_spread": [_ctx, C.POINTER(_i), _i, C.c_void_p, C.c_size_t],
     "fluid_relax_spread": [_ctx, C.POINTER(_i), _i, C.c_void_p, C.c_size_t, _f],
+    "fluid_noise_members": [_ctx, C.POINTER(_i), _i, _i, _MF, C.c_ulonglong, C.c_uint, _i],
+    "fluid_noise_dense": [_ctx, C.c_void_p, C.c_size_t, _f, C.c_ulonglong, C.c_uint, _i],
+    "fluid_noise_value": [C.c_ulonglong, C.c_uint, _i, _i, C.c_uint, C.c_uint, C.POINTER(C.c_double)],
     "fluid_set_jacobi_variant": [_ctx, _i],
     "fluid_division_mode": [_ctx, _f, _f, C.POINTER(_i)],
     "fluid_autotune_pending": [_ctx, C.POINTER(_i)],
@@ -180,6 +183,9 @@ LATTICE_MAX_NODES = 4096
 LATTICE_GRAM_MAX_ENTRIES = 1 << 24
 ETKF_MAX_SWEEPS = 28
 ETKF_SOLVED, ETKF_EMPTY, ETKF_FAILED = 0, 1, 2
+NOISE_SET, NOISE_ADD = 0, 1
+NOISE_DENSE_TAG = 15                 # the counter tag of fluid_noise_dense: no field id
+NOISE_IDS = 65536                    # member ids and stream ids lie below it
 
 _lib = None
 

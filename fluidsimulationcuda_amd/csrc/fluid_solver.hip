@@ -19,6 +19,7 @@
 
 #include "fluid_ctx.h"
 #include "fluid_etkf.h"
+#include "fluid_noise.h"
 
 namespace fluid_detail {
 
@@ -3112,6 +3113,85 @@ int fluid_relax_spread(fluid_ctx* c, const int* fields, int nfields, const void*
         wrote(c, f, kEverywhere);                                    // nothing owed ...
         c->field[f].fscale = scale;                                  // ... and the scale it had: the launch stored at it
     }
+    return FLUID_OK;
+}
+
+// ---- ensemble noise: fluid_noise_members / fluid_noise_dense / fluid_noise_value -------------------------------------------
+// (include/fluid_amd.h "ensemble noise".)  The list is checked as a spread's is, without its M >= 2 rule.  SET replaces the
+// field in all members, as an unpack of all members does: nothing is settled, what the field owed itself is dropped, the
+// scale becomes 1.  ADD settles the field as fluid_relax_spread does, a scale KEPT, and stores at it.  The amplitudes go
+// through the ring of per-member constants (one member: by value).  One launch per field, no wait; the launches belong to
+// none of the timing categories.
+int fluid_noise_members(fluid_ctx* c, const int* fields, int nfields, int mode, const float* amplitude, unsigned long long seed,
+                        unsigned int sequence, int member_offset)
+{
+    const char* call = "fluid_noise_members";
+    if (!fields) return fail(FLUID_E_INVALID, "%s: null array `fields`", call);
+    if (!amplitude) return fail(FLUID_E_INVALID, "%s: null array `amplitude`", call);
+    if (!c) return fail(FLUID_E_INVALID, "%s: null context", call);
+    if (nfields < 1 || nfields > FLUID_NFIELDS) return fail(FLUID_E_INVALID, "%s: nfields %d outside [1, %d]", call, nfields, FLUID_NFIELDS);
+    for (int k = 0; k < nfields; ++k) {
+        if (!c->valid_field(fields[k])) return fail(FLUID_E_INVALID, "%s: bad field id %d (fields[%d])", call, fields[k], k);
+        for (int j = 0; j < k; ++j)
+            if (fields[j] == fields[k]) return fail(FLUID_E_INVALID, "%s: field %d is listed twice (fields[%d] and fields[%d])", call, fields[k], j, k);
+    }
+    if (mode != FLUID_NOISE_SET && mode != FLUID_NOISE_ADD)
+        return fail(FLUID_E_INVALID, "%s: mode %d is neither FLUID_NOISE_SET nor FLUID_NOISE_ADD", call, mode);
+    for (int m = 0; m < c->members; ++m)
+        if (!std::isfinite(amplitude[m])) return fail(FLUID_E_INVALID, "%s: member %d: amplitude is not finite (%g)", call, m, (double)amplitude[m]);
+    if (member_offset < 0 || member_offset > fluid::kNoiseIds - c->members)
+        return fail(FLUID_E_INVALID, "%s: member_offset %d with %d member(s): member ids must lie in [0, %d]", call, member_offset, c->members,
+                    fluid::kNoiseIds - 1);
+    TRY(refuse_slabs(c, call));
+    const bool add = mode == FLUID_NOISE_ADD;
+    const fluid::NoiseKey key = {(unsigned)seed, (unsigned)(seed >> 32), sequence};
+    const float* per_member = nullptr;
+    if (c->members > 1) {
+        TRY(ensure_consts(c));
+        TRY(member_floats(c, MemberVal(amplitude, c->members), &per_member));
+    }
+    for (int k = 0; k < nfields; ++k) {
+        const int f = fields[k];
+        float scale = 1.0f;
+        if (add) {
+            scale = c->st != fluid::STORAGE_F32 ? c->field[f].fscale : 1.0f;                  // as pack_range sees the field
+            TRY(materialize(c, f, /*keep_scale=*/scale != 1.0f));
+        }
+        fluid::launch_noise_members(c->stream, c->st, c->ptr(f), c->pitch, c->n, c->mb(), add, 1.0f / scale, scale, amplitude[0], per_member,
+                                    key, f, member_offset);
+        HIP_TRY(hipGetLastError());
+        wrote(c, f, kEverywhere);                                    // nothing owed, plain values ...
+        c->field[f].fscale = scale;                                  // ... or, ADD, the scale it had: the launch stored at it
+    }
+    return FLUID_OK;
+}
+
+int fluid_noise_dense(fluid_ctx* c, void* out_dev, size_t count, float amplitude, unsigned long long seed, unsigned int sequence, int stream_id)
+{
+    const char* call = "fluid_noise_dense";
+    if (!out_dev) return fail(FLUID_E_INVALID, "%s: null device pointer `out_dev`", call);
+    if (!c) return fail(FLUID_E_INVALID, "%s: null context", call);
+    if (!std::isfinite(amplitude)) return fail(FLUID_E_INVALID, "%s: amplitude is not finite (%g)", call, (double)amplitude);
+    if (stream_id < 0 || stream_id >= fluid::kNoiseIds)
+        return fail(FLUID_E_INVALID, "%s: stream_id %d outside [0, %d]", call, stream_id, fluid::kNoiseIds - 1);
+    TRY(refuse_slabs(c, call));
+    size_t bytes = 0;
+    if (__builtin_mul_overflow(count, sizeof(float), &bytes)) return fail(FLUID_E_INVALID, "%s: count %zu is too large", call, count);
+    TRY(check_device_span(c, call, "out_dev", out_dev, bytes));
+    if (count == 0) return FLUID_OK;
+    fluid::launch_noise_dense(c->stream, static_cast<float*>(out_dev), count, amplitude, {(unsigned)seed, (unsigned)(seed >> 32), sequence}, stream_id);
+    HIP_TRY(hipGetLastError());
+    return FLUID_OK;
+}
+
+int fluid_noise_value(unsigned long long seed, unsigned int sequence, int tag, int member_id, unsigned int c0, unsigned int c1, double* z)
+{
+    const char* call = "fluid_noise_value";
+    if (!z) return fail(FLUID_E_INVALID, "%s: null pointer `z`", call);
+    if (tag < 0 || tag > fluid::kNoiseDenseTag) return fail(FLUID_E_INVALID, "%s: tag %d outside [0, %d]", call, tag, fluid::kNoiseDenseTag);
+    if (member_id < 0 || member_id >= fluid::kNoiseIds)
+        return fail(FLUID_E_INVALID, "%s: member_id %d outside [0, %d]", call, member_id, fluid::kNoiseIds - 1);
+    *z = fluid::noise_z((unsigned)seed, (unsigned)(seed >> 32), c0, c1, fluid::noise_word2(tag, member_id), sequence);
     return FLUID_OK;
 }
 

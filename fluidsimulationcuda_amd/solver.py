@@ -680,6 +680,61 @@ class FluidSolver:
         if wait:
             self.synchronize()
 
+    # -- ensemble noise: reproducible randomness on the device, the same bits for every members, launch shape and process
+    def _amplitudes(self, amplitude):
+        a = np.asarray(amplitude, dtype=np.float32)
+        if a.ndim == 0:
+            a = np.full(self.members, a, dtype=np.float32)
+        elif a.ndim != 1 or a.shape[0] != self.members:
+            raise ValueError("amplitude: expected a scalar or %d values (one per member), got shape %s" % (self.members, a.shape))
+        return np.ascontiguousarray(a, dtype=np.float32)
+
+    def noise(self, fields, amplitude, seed, sequence=0, mode=capi.NOISE_SET, member_offset=0):
+        """Approximately normal noise (mean 0, variance 1, |z| <= 4.899; Philox4x32-10, eight 16-bit halves summed) times
+        `amplitude` -- a scalar or one value per member -- set into (mode capi.NOISE_SET or "set") or added to (capi.NOISE_ADD
+        or "add") every cell of every member of the listed fields, ghost ring included, in one launch per field, no wait.
+        The noise of (seed, sequence, field, member_offset + member, cell) is the same bits whatever `members` is: contexts
+        that hold parts of one big ensemble pass the index of their first member as `member_offset`.  A new `sequence` per
+        cycle gives new noise under one `seed` (include/fluid_amd.h, "ensemble noise")."""
+        ids = [_fid(f) for f in ((fields,) if isinstance(fields, (str, int)) else fields)]
+        mode = {"set": capi.NOISE_SET, "add": capi.NOISE_ADD}.get(mode, mode)
+        a = self._amplitudes(amplitude)
+        capi.check(capi.lib().fluid_noise_members(self._h, (C.c_int * len(ids))(*ids), len(ids), int(mode), _mf(a), int(seed), int(sequence),
+                                                  int(member_offset)))
+
+    def noise_dense(self, out, amplitude, seed, sequence=0, stream_id=0, count=None, wait=True):
+        """out[q] = amplitude * z for the first `count` floats of a dense device buffer (None: all of it; a plain address
+        needs a count), z of the stream `stream_id` in [0, 65535] of (seed, sequence): the observation noise of a twin
+        experiment, or the perturbed observations of a stochastic filter.  One launch; `wait`: as for pack.  Returns `out`."""
+        if count is None:
+            count = device_floats(out, -1)
+            if count < 0:
+                raise ValueError("noise_dense: a plain address needs a count")
+        elif device_floats(out, count) < count:
+            raise ValueError("noise_dense: the buffer holds %d floats, count is %d" % (device_floats(out, count), count))
+        self._handover(wait)
+        capi.check(capi.lib().fluid_noise_dense(self._h, device_address(out), int(count), float(amplitude), int(seed), int(sequence),
+                                                int(stream_id)))
+        if wait:
+            self.synchronize()
+        return out
+
+    def perturb(self, field, scratch, amplitude, seed, sequence, alpha, beta, iters, b=0):
+        """Spatially correlated noise added to `field`: white noise of amplitude 1 set into scratch[0], smoothed by the
+        implicit diffusion solve (Weaver & Courtier 2001) diffuse(b, scratch[1], scratch[0], alpha, beta, iters), and the
+        result added as add_source(field, scratch[1], dt=amplitude) -- those three calls and nothing else, so the solve
+        starts from what scratch[1] holds.  `scratch`: two of the six fields (the solve's right-hand side and its result),
+        distinct from each other and from `field`; alpha, beta, amplitude: a scalar or one value per member.  Smoothing
+        shrinks the variance: measure what one call leaves in scratch[1] once, with member_moments, and rescale `amplitude`
+        by 1 / its standard deviation."""
+        white, smooth = scratch
+        mv = member_values(self.members, alpha=alpha, beta=beta)
+        if mv is None:
+            mv = {"alpha": np.full(self.members, alpha, np.float32), "beta": np.full(self.members, beta, np.float32)}
+        self.noise((white,), 1.0, seed, sequence, capi.NOISE_SET)
+        capi.check(capi.lib().fluid_op_diffuse_members(self._h, int(b), _fid(smooth), _fid(white), _mf(mv["alpha"]), _mf(mv["beta"]), int(iters)))
+        capi.check(capi.lib().fluid_op_add_source_members(self._h, _fid(field), _fid(smooth), _mf(self._amplitudes(amplitude))))
+
     def set_jacobi_variant(self, variant):
         capi.check(capi.lib().fluid_set_jacobi_variant(self._h, variant))
 
@@ -763,6 +818,14 @@ def coarse_size(n, factor):
     side = C.c_int()
     capi.check(capi.lib().fluid_coarse_size(int(n), int(factor), C.byref(side)))
     return side.value
+
+
+def noise_value(seed, sequence, tag, member_id, c0, c1):
+    """The z of one counter of the ensemble noise: (c0, c1, (tag << 16) | member_id, sequence) under `seed` -- for a field
+    cell tag = the field id, c0 = the column, c1 = the row (fluid_noise_value: host logic, no device)."""
+    z = C.c_double()
+    capi.check(capi.lib().fluid_noise_value(int(seed), int(sequence), int(tag), int(member_id), int(c0), int(c1), C.byref(z)))
+    return z.value
 
 
 def coefficients(n, dt, coef):

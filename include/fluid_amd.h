@@ -908,6 +908,67 @@ int fluid_analyse_lattice_status(fluid_ctx *ctx, int *solved, int *empty, int *f
 int fluid_member_spread(fluid_ctx *ctx, const int *fields, int nfields, void *out_dev, size_t field_stride);
 int fluid_relax_spread(fluid_ctx *ctx, const int *fields, int nfields, const void *prior_dev, size_t field_stride, float alpha);
 
+/* ---- ensemble noise: reproducible randomness on the device, set or added in place -----------------------------------------
+ * M = fluid_members(ctx), M >= 1, W = N + 2.  What makes one member differ from the next -- initial perturbations, additive
+ * inflation or model error between cycles (`rho` and RTPS only rescale the spread that is left), the stochastic forcing the
+ * *_PREV sources carry, the observation noise of a twin experiment or of a perturbed-observation filter -- is drawn here,
+ * on the device, by a counter-based generator with a contract exact to the bit: the noise of (seed, sequence, field,
+ * member, cell) is the same bits for every M, every launch shape and every process.  A cycle is fluid_noise_members ->
+ * fluid_member_spread -> fluid_analyse_lattice -> fluid_relax_spread -> fluid_run_members, nothing crossing to the host.
+ *
+ * Random word.  Philox4x32-10 (Salmon, Moraes, Dror & Shaw 2011): multipliers 0xD2511F53 and 0xCD9E8D57, key increments
+ * 0x9E3779B9 and 0xBB67AE85, ten rounds.  Known answers (counter; key -> output, hexadecimal words):
+ *     0 0 0 0; 0 0                                                  -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8
+ *     ffffffff ffffffff ffffffff ffffffff; ffffffff ffffffff        -> 408f276d 41c83b0e a20bc7c6 6d5451fd
+ *     243f6a88 85a308d3 13198a2e 03707344; a4093822 299f31d0        -> d16cfe09 94fdcceb 5001e420 24126ea1
+ * Addressing.  key = (low, high 32 bits of the 64-bit `seed`).  For the cell in row i, column j of a member of a field,
+ * counter = (j, i, (field id << 16) | member id, `sequence`), member id = member_offset + m for member m of the context:
+ * `member_offset` lets an ensemble split over several contexts draw the noise of one big ensemble.  The ghost ring is a
+ * cell like any other; the pitch and the pad columns take no part.
+ * Value.  From the four output words: S = the sum of their eight 16-bit halves, an integer in [0, 524280]; z = (double)(S -
+ * 262140) * C, C = 0x1.3988e1412ed76p-16 = 1 / sqrt(8 * (2^32 - 1) / 12), one rounding.  z is Irwin-Hall with n = 8: mean 0,
+ * variance 1, excess kurtosis -0.15, |z| <= 4.899 -- APPROXIMATELY normal, not normal: the tails end.  No transcendental
+ * function appears, on purpose: the device and a numpy model agree to the bit.
+ *
+ * - fluid_noise_members: `fields`: nfields distinct field ids, host memory, nfields in [1, FLUID_NFIELDS]; `amplitude`: M
+ *   finite host floats, a_m for member m.  One kernel launch per listed field whatever M is, enqueued on the context's
+ *   stream, no wait; the host arrays belong to the caller again when the call returns.  All arithmetic is IEEE double, every
+ *   operation rounded once, none contracted.  Per listed field, per cell of the W x W array (pad columns are neither read
+ *   nor written), per member m:
+ *    FLUID_NOISE_SET: y = (float)((double)a_m * z); the store is narrow(y).  The field is REPLACED in all members: nothing is
+ *       settled first, what the field owed itself is dropped, and afterwards it holds plain values (scale 1), as after a
+ *       fluid_unpack_members of all members.
+ *    FLUID_NOISE_ADD: x is read as rule 1 of fluid_transform_members_local reads it -- the field is settled first, and an
+ *       fp16 field held at a pressure scale KEEPS the scale --; p = (double)a_m * z; y = (float)((double)x + p), product and
+ *       sum each rounded once and NOT contracted into one fused operation; the store follows that call's rule 6: narrow(y)
+ *       times the scale, +-inf beyond 65504 / scale.  A member with a_m == 0, of either sign, is not stored and keeps every
+ *       bit.  A non-finite x stays non-finite in that cell only.
+ *   Any M >= 1 works, one-member contexts included: there is NO cap at FLUID_TRANSFORM_MAX_MEMBERS.
+ * - fluid_noise_dense writes `count` floats to a dense DEVICE array, aligned to 4 bytes: out[q] = (float)((double)amplitude *
+ *   z), z of the counter (low 32 bits of q, high 32 bits of q, (15 << 16) | stream_id, sequence) -- tag 15 is no field id,
+ *   so no field cell shares a counter with it.  stream_id in [0, 65535].  One launch, no wait; count = 0 launches nothing.
+ *   This is the observation noise for `obs`, or the perturbed observations of a stochastic EnKF.
+ * - fluid_noise_value: host logic only, no context and no device, like fluid_coefficients: *z = the z of the counter (c0, c1,
+ *   (tag << 16) | member_id, sequence) under `seed`; tag in [0, 15], member_id in [0, 65535].  The kernels and this function
+ *   share one body.
+ * Correlated noise needs nothing new: an implicit diffusion solve applied to white noise is the standard correlation model
+ * (Weaver & Courtier 2001), and fluid_op_diffuse_members is that solve.  The recipe: FLUID_NOISE_SET into a scratch field,
+ * fluid_op_diffuse_members from it into a second one, fluid_op_add_source_members with the amplitudes as `dt`.  Smoothing
+ * shrinks the variance: measure it once with fluid_member_moments and rescale the amplitudes.
+ * Refusals, all FLUID_E_INVALID with a message that names the call and, where it applies, the list position or the member,
+ * found before anything is launched or any state changes, null pointers before the context is looked at: a null `fields`,
+ * `amplitude`, `out_dev` or `z`, a null context; nfields outside [1, FLUID_NFIELDS]; a bad field id; a field listed twice; a
+ * mode that is neither of the two; a non-finite amplitude; member_offset < 0 or member_offset + M > 65536; a stream_id,
+ * member_id or tag out of range; an `out_dev` that is not device memory of the context's device, or whose `count` floats
+ * do not lie inside one allocation (asked of the runtime on the host, as for a pack); row slabs.
+ * The launches belong to none of the fluid_timing categories. */
+enum { FLUID_NOISE_SET = 0, FLUID_NOISE_ADD = 1 };
+int fluid_noise_members(fluid_ctx *ctx, const int *fields, int nfields, int mode, const float *amplitude, unsigned long long seed,
+                        unsigned int sequence, int member_offset);
+int fluid_noise_dense(fluid_ctx *ctx, void *out_dev, size_t count, float amplitude, unsigned long long seed, unsigned int sequence,
+                      int stream_id);
+int fluid_noise_value(unsigned long long seed, unsigned int sequence, int tag, int member_id, unsigned int c0, unsigned int c1, double *z);
+
 int fluid_set_jacobi_variant(fluid_ctx *ctx, int variant);
 /* How FLUID_JACOBI_TB divides by `beta` in a solve with these coefficients (diagnostic; runs the on-device proof
  * if this beta has not been seen): 0 true division, 2 double-precision reciprocal, 3 two-term float reciprocal
