@@ -61,6 +61,12 @@ class RunPlan(C.Structure):
                 ("snapshots", C.c_void_p), ("capacity", C.c_size_t)]
 
 
+class ObsWindow(C.Structure):
+    """fluid_obs_window: which points of the resident network a windowed run observes after which step, and into what record"""
+    _fields_ = [("field", C.c_int), ("nslots", C.c_int), ("slot_first", C.POINTER(C.c_int)), ("slot_step", C.POINTER(C.c_int)),
+                ("record_dev", C.c_void_p), ("member_stride", C.c_size_t)]
+
+
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int,
                           C.POINTER(C.c_float))
 
@@ -151,6 +157,13 @@ SIGNATURES = {
     "fluid_noise_members": [_ctx, C.POINTER(_i), _i, _i, _MF, C.c_ulonglong, C.c_uint, _i],
     "fluid_noise_dense": [_ctx, C.c_void_p, C.c_size_t, _f, C.c_ulonglong, C.c_uint, _i],
     "fluid_noise_value": [C.c_ulonglong, C.c_uint, _i, _i, C.c_uint, C.c_uint, C.POINTER(C.c_double)],
+    "fluid_observe_members_range": [_ctx, _i, _i, _i, C.c_void_p, C.c_size_t],
+    "fluid_run_window": [_ctx, _MF, _MF, _MF, C.POINTER(RunPlan), _i, C.POINTER(ObsWindow), C.POINTER(_i)],
+    "fluid_observation_gram_recorded": [_ctx, C.c_void_p, C.c_size_t, _i, _MF, _MF, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                        C.POINTER(C.c_double)],
+    "fluid_observation_gram_lattice_recorded": [_ctx, C.c_void_p, C.c_size_t, _i, _MF, _MF, _i, _i, _i, _i, _i, _f,
+                                                C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i)],
+    "fluid_analyse_lattice_recorded": [_ctx, C.c_void_p, C.c_size_t, _MF, _MF, _i, _i, _i, _i, _i, _f, _f, C.POINTER(_i), _i],
     "fluid_set_jacobi_variant": [_ctx, _i],
     "fluid_division_mode": [_ctx, _f, _f, C.POINTER(_i)],
     "fluid_autotune_pending": [_ctx, C.POINTER(_i)],
@@ -186,6 +199,7 @@ ETKF_SOLVED, ETKF_EMPTY, ETKF_FAILED = 0, 1, 2
 NOISE_SET, NOISE_ADD = 0, 1
 NOISE_DENSE_TAG = 15                 # the counter tag of fluid_noise_dense: no field id
 NOISE_IDS = 65536                    # member ids and stream ids lie below it
+WINDOW_MAX_SLOTS = 65536             # FLUID_WINDOW_MAX_SLOTS: slots of one fluid_run_window
 
 _lib = None
 

@@ -222,6 +222,13 @@ struct FieldSource {                      // (no initialisers: it lives in LDS)
 struct FieldSources {
     FieldSource of[kObservedFields];
 };
+// The two Gram launches take a third source, `recorded` non-null (include/fluid_amd.h "asynchronous observations"): h_k[p] =
+// h[k * stride + p], floats an earlier launch on the stream left; st, x, inv, typed and the taps of `pts` are then not read
+// (pts.count still is).  One instantiation serves every storage type.
+struct RecordedValues {
+    const float* h = nullptr;
+    size_t stride = 0;
+};
 // The three observing launches below take (`x`, `inv`) -- every point observes that field -- or, `typed` non-null, the table
 // pts.field indexes (`x` and `inv` are then not read).  These are different kernels: the one-field instantiations have no
 // per-point lookup.
@@ -242,7 +249,8 @@ inline size_t observation_gram_entries(int members)
 }
 int observation_gram_blocks(int points, int members);
 void launch_observation_gram(hipStream_t s, int st, const void* x, int pitch, Members mb, float inv, const FieldSources* typed,
-                             const ObservationPoints& pts, bool centre, const float* obs, const float* sigma, double* partials, double* out);
+                             const ObservationPoints& pts, bool centre, const float* obs, const float* sigma, double* partials, double* out,
+                             const RecordedValues* recorded = nullptr);
 
 // Localised updates (include/fluid_amd.h "localised updates").
 // The box of a launch, half-open, in cells of the (n + 2)^2 array: rows [row_lo, row_hi), columns [col_lo, col_hi).
@@ -325,6 +333,6 @@ struct LatticeLists {
 // + 2) doubles of scratch.  Two launches whatever the counts: every point is observed once, then one block per node.
 void launch_observation_gram_lattice(hipStream_t s, int st, const void* x, int pitch, Members mb, float inv, const FieldSources* typed,
                                      const ObservationPoints& pts, bool centre, const float* obs, const float* sigma, double* operands, const LatticeLists& lists,
-                                     double* out);
+                                     double* out, const RecordedValues* recorded = nullptr);
 
 }  // namespace fluid

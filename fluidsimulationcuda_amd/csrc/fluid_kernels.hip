@@ -1900,15 +1900,24 @@ __device__ __forceinline__ float observe_point(const S* __restrict__ x, int pitc
 // addresses in one broadcast read.  observe_point is the same for both: it gets a base and an inv.
 template <typename S>
 struct OneField {
-    static constexpr bool typed = false;
+    static constexpr bool typed = false, recorded = false;
     const S* x;                            // member 0 of the launch
     float inv;
 };
 struct FieldOfPoint {
-    static constexpr bool typed = true;
+    static constexpr bool typed = true, recorded = false;
     const unsigned char* index;            // [points] field ids < kObservedFields
     FieldSources table;
     unsigned first;                        // member 0 of the launch is member `first` of every field
+};
+
+// Recorded (include/fluid_amd.h "asynchronous observations"): nothing is observed, h_k[p] is the float an earlier launch left
+// in a record.  The two Gram kernels' gather is then one load per member: lane = point, so a wave reads 64 consecutive floats;
+// no taps, no weights, no table and no barrier for it.  It does not depend on the storage type: instantiated with S = float.
+struct Recorded {
+    static constexpr bool typed = false, recorded = true;
+    const float* h;                        // h[member * stride + point]
+    size_t stride;
 };
 
 template <typename SRC>
@@ -1994,16 +2003,24 @@ __global__ __launch_bounds__(256) void k_observation_gram(SRC src, int pitch, si
     auto load = [&](unsigned c) {
         const int pt = (int)c * CH + lane;
         const bool live = pt < points;
-        const unsigned long long o = live ? tap[pt] : 0ull;
-        const float4 w = live ? weight[pt] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        float inv = 0.0f;
-        const S* x = live ? source_of<S>(src, sources, ms, (unsigned)pt, &inv) : nullptr;
+        if constexpr (SRC::recorded) {
 #pragma unroll
-        for (int r = 0; r < L; ++r) {
-            const int k = wave + 4 * r;
-            float a = 0.0f;
-            if (live && k < members) a = observe_point<S>(x + (size_t)k * ms, pitch, o, w, inv);
-            f[r] = a;
+            for (int r = 0; r < L; ++r) {
+                const int k = wave + 4 * r;
+                f[r] = live && k < members ? src.h[(size_t)k * src.stride + (size_t)pt] : 0.0f;
+            }
+        } else {
+            const unsigned long long o = live ? tap[pt] : 0ull;
+            const float4 w = live ? weight[pt] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            float inv = 0.0f;
+            const S* x = live ? source_of<S>(src, sources, ms, (unsigned)pt, &inv) : nullptr;
+#pragma unroll
+            for (int r = 0; r < L; ++r) {
+                const int k = wave + 4 * r;
+                float a = 0.0f;
+                if (live && k < members) a = observe_point<S>(x + (size_t)k * ms, pitch, o, w, inv);
+                f[r] = a;
+            }
         }
     };
 
@@ -2129,16 +2146,24 @@ __global__ __launch_bounds__(256) void k_observation_operands(SRC src, int pitch
     {
         const int pt = first + lane;
         const bool live = pt < points;
-        const unsigned long long o = live ? tap[pt] : 0ull;
-        const float4 w = live ? weight[pt] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        float inv = 0.0f;
-        const S* x = live ? source_of<S>(src, sources, ms, (unsigned)pt, &inv) : nullptr;
+        if constexpr (SRC::recorded) {
 #pragma unroll
-        for (int r = 0; r < L; ++r) {
-            const int k = wave + 4 * r;
-            float a = 0.0f;
-            if (live && k < members) a = observe_point<S>(x + (size_t)k * ms, pitch, o, w, inv);
-            stage[lane * R + k] = (double)a;
+            for (int r = 0; r < L; ++r) {
+                const int k = wave + 4 * r;
+                stage[lane * R + k] = (double)(live && k < members ? src.h[(size_t)k * src.stride + (size_t)pt] : 0.0f);
+            }
+        } else {
+            const unsigned long long o = live ? tap[pt] : 0ull;
+            const float4 w = live ? weight[pt] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            float inv = 0.0f;
+            const S* x = live ? source_of<S>(src, sources, ms, (unsigned)pt, &inv) : nullptr;
+#pragma unroll
+            for (int r = 0; r < L; ++r) {
+                const int k = wave + 4 * r;
+                float a = 0.0f;
+                if (live && k < members) a = observe_point<S>(x + (size_t)k * ms, pitch, o, w, inv);
+                stage[lane * R + k] = (double)a;
+            }
         }
     }
     __syncthreads();
@@ -3430,6 +3455,18 @@ void launch_member_gram(hipStream_t s, int st, const void* x, int pitch, int n, 
             __VA_ARGS__;                                                          \
         }                                                                         \
     } while (0)
+// ... and of the two Gram launches, which also read a record (`recorded` non-null: st, x, inv and typed are not looked at)
+#define FLUID_BY_OBSERVED(st, typed, recorded, ...)                               \
+    do {                                                                          \
+        if (recorded) {                                                           \
+            using S = float;                                                      \
+            using SRC = Recorded;                                                 \
+            const SRC src = {(recorded)->h, (recorded)->stride};                  \
+            __VA_ARGS__;                                                          \
+        } else {                                                                  \
+            FLUID_BY_STORAGE(st, FLUID_BY_SOURCE(typed, 0, __VA_ARGS__));         \
+        }                                                                         \
+    } while (0)
 
 void launch_observe_members(hipStream_t s, int st, const void* x, int pitch, Members mb, float inv, const FieldSources* typed, int first_member,
                             const ObservationPoints& pts, int first_point, int npoints, float* out, size_t ostride)
@@ -3447,15 +3484,15 @@ int observation_gram_blocks(int points, int members)
 }
 
 void launch_observation_gram(hipStream_t s, int st, const void* x, int pitch, Members mb, float inv, const FieldSources* typed,
-                             const ObservationPoints& pts, bool centre, const float* obs, const float* sigma, double* partials, double* out)
+                             const ObservationPoints& pts, bool centre, const float* obs, const float* sigma, double* partials, double* out,
+                             const RecordedValues* recorded)
 {
     const int mp = gram_padded(mb.count), blocks = observation_gram_blocks(pts.count, mb.count);
     const unsigned chunks = cdiv((unsigned)pts.count, kObsChunk);
 #define FLUID_OBS_GRAM_LAUNCH(MP, CENTRE, OBS)                                                                                             \
-    FLUID_BY_STORAGE(st, FLUID_BY_SOURCE(typed, 0,                                                                                         \
-                                         hipLaunchKernelGGL((k_observation_gram<S, MP, CENTRE, OBS, SRC>), dim3(blocks), dim3(256), 0, s, src,     \
-                                                            pitch, mb.stride, mb.count, pts.tap, (const float4*)pts.weight, obs, sigma, pts.count, \
-                                                            chunks, partials)))
+    FLUID_BY_OBSERVED(st, typed, recorded,                                                                                                 \
+                      hipLaunchKernelGGL((k_observation_gram<S, MP, CENTRE, OBS, SRC>), dim3(blocks), dim3(256), 0, s, src, pitch, mb.stride,      \
+                                         mb.count, pts.tap, (const float4*)pts.weight, obs, sigma, pts.count, chunks, partials))
 #define FLUID_OBS_GRAM_CASE(MP)                                     \
     case MP:                                                        \
         if (centre && obs) FLUID_OBS_GRAM_LAUNCH(MP, true, true);   \
@@ -3477,15 +3514,14 @@ void launch_observation_gram(hipStream_t s, int st, const void* x, int pitch, Me
 
 void launch_observation_gram_lattice(hipStream_t s, int st, const void* x, int pitch, Members mb, float inv, const FieldSources* typed,
                                      const ObservationPoints& pts, bool centre, const float* obs, const float* sigma, double* operands, const LatticeLists& lists,
-                                     double* out)
+                                     double* out, const RecordedValues* recorded)
 {
     const int mp = gram_padded(mb.count);
     const unsigned chunks = cdiv((unsigned)pts.count, kObsChunk);
 #define FLUID_OBS_OPERANDS_LAUNCH(MP, CENTRE, OBS)                                                                                         \
-    FLUID_BY_STORAGE(st, FLUID_BY_SOURCE(typed, 0,                                                                                         \
-                                         hipLaunchKernelGGL((k_observation_operands<S, MP, CENTRE, OBS, SRC>), dim3(chunks), dim3(256), 0, s, src, \
-                                                            pitch, mb.stride, mb.count, pts.tap, (const float4*)pts.weight, obs, sigma, pts.count, \
-                                                            operands)))
+    FLUID_BY_OBSERVED(st, typed, recorded,                                                                                                 \
+                      hipLaunchKernelGGL((k_observation_operands<S, MP, CENTRE, OBS, SRC>), dim3(chunks), dim3(256), 0, s, src, pitch, mb.stride,  \
+                                         mb.count, pts.tap, (const float4*)pts.weight, obs, sigma, pts.count, operands))
 #define FLUID_LATTICE_GRAM_CASE(MP)                                                                                                        \
     case MP:                                                                                                                               \
         if (centre && obs) FLUID_OBS_OPERANDS_LAUNCH(MP, true, true);                                                                      \

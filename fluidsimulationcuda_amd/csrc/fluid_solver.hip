@@ -3378,20 +3378,59 @@ static fluid::ObservationPoints observation_points(const fluid_ctx* c)
     return {c->observe.tap(), c->observe.weight(), c->observe.points, c->observe.field_of_point()};
 }
 
+// A record (include/fluid_amd.h "asynchronous observations") under the caller's name: member_stride 0 is P, anything else at
+// least P, and the (M - 1) * stride + P floats lie inside one device allocation.  The network is set (check_observe).
+static int check_record(const fluid_ctx* c, const char* call, const void* record_dev, size_t* member_stride)
+{
+    const size_t P = (size_t)c->observe.points;
+    if (*member_stride == 0) *member_stride = P;
+    if (*member_stride < P) return fail(FLUID_E_INVALID, "%s: member_stride %zu is below the %zu points of the network", call, *member_stride, P);
+    size_t bytes = 0;
+    if (!dense_span(P, c->members, *member_stride, &bytes)) return fail(FLUID_E_INVALID, "%s: member_stride %zu is too large", call, *member_stride);
+    return check_device_span(c, call, "record_dev", record_dev, bytes);
+}
+
+// Where the h_k[p] of a Gram call come from: a field (or FLUID_FIELD_OF_POINT) sampled now, or -- `record` non-null, `field`
+// is then not looked at -- the floats of a record.  One body per direct / recorded pair takes it.
+struct GramSource {
+    int field = 0;
+    const void* record = nullptr;
+    size_t stride = 0;
+    explicit GramSource(int f) : field(f) {}
+    GramSource(const void* r, size_t s) : record(r), stride(s) {}
+};
+
+// check_observe for either source; a record's stride comes back resolved
+static int check_gram_source(const fluid_ctx* c, const char* call, GramSource* src)
+{
+    if (!src->record) return check_observe(c, call, src->field);
+    TRY(refuse_slabs(c, call));
+    if (c->observe.points == 0) return fail(FLUID_E_INVALID, "%s: no observation network is set (fluid_set_observation_points)", call);
+    return check_record(c, call, src->record, &src->stride);
+}
+
 // What an observing launch reads: one field and its 1 / scale, or -- FLUID_FIELD_OF_POINT -- the table the points' field ids
 // index.  As pack_range sees a field: the lazy state settled, a scale kept and divided back in the kernel.  The table is
 // built after EVERY field of the network is settled, because settling one field may hand another one's buffer on.
+// A record is read as it lies: no field is settled or looked at.
 struct ObservedFrom {
     const void* x = nullptr;
     float inv = 1.0f;
     fluid::FieldSources table = {};
     bool typed = false;
+    fluid::RecordedValues record = {};
     const fluid::FieldSources* sources() const { return typed ? &table : nullptr; }
+    const fluid::RecordedValues* recorded() const { return record.h ? &record : nullptr; }
 };
 
-static int settle_for_observing(fluid_ctx* c, int field, ObservedFrom* from)
+static int settle_for_observing(fluid_ctx* c, const GramSource& src, ObservedFrom* from)
 {
     auto inv_of = [&](int f) { return c->st != fluid::STORAGE_F32 ? 1.0f / c->field[f].fscale : 1.0f; };
+    const int field = src.field;
+    if (src.record) {
+        from->record = {static_cast<const float*>(src.record), src.stride};
+        return FLUID_OK;
+    }
     if (field != FLUID_FIELD_OF_POINT) {
         from->inv = inv_of(field);
         TRY(materialize(c, field, /*keep_scale=*/from->inv != 1.0f));
@@ -3421,11 +3460,38 @@ int fluid_observe_members(fluid_ctx* c, int field, void* out_dev, size_t member_
     if (!dense_span(P, c->members, member_stride, &bytes)) return fail(FLUID_E_INVALID, "fluid_observe_members: member_stride %zu is too large", member_stride);
     TRY(check_device_span(c, "fluid_observe_members", "out_dev", out_dev, bytes));
     ObservedFrom from;
-    TRY(settle_for_observing(c, field, &from));
+    TRY(settle_for_observing(c, GramSource(field), &from));
     fluid::launch_observe_members(c->stream, c->st, from.x, c->pitch, c->mb(), from.inv, from.sources(), 0, observation_points(c), 0, (int)P,
                                   static_cast<float*>(out_dev), member_stride);
     HIP_TRY(hipGetLastError());
     return FLUID_OK;
+}
+
+// fluid_observe_members_range behind its checks, and every observation of fluid_run_window: the launch of
+// fluid_observe_members with p0, np and the output pointer advanced by `first`.  An empty range launches and settles nothing.
+static int observe_range(fluid_ctx* c, int field, int first, int count, void* record_dev, size_t member_stride)
+{
+    if (count == 0) return FLUID_OK;
+    ObservedFrom from;
+    TRY(settle_for_observing(c, GramSource(field), &from));
+    fluid::launch_observe_members(c->stream, c->st, from.x, c->pitch, c->mb(), from.inv, from.sources(), 0, observation_points(c), first, count,
+                                  static_cast<float*>(record_dev) + first, member_stride);
+    HIP_TRY(hipGetLastError());
+    return FLUID_OK;
+}
+
+int fluid_observe_members_range(fluid_ctx* c, int field, int first, int count, void* record_dev, size_t member_stride)
+{
+    const char* call = "fluid_observe_members_range";
+    if (!record_dev) return fail(FLUID_E_INVALID, "%s: null device pointer `record_dev`", call);
+    if (!c) return fail(FLUID_E_INVALID, "%s: null context", call);
+    TRY(check_observe(c, call, field));
+    const int P = c->observe.points;
+    if (first < 0 || first > P || count < 0 || count > P - first)
+        return fail(FLUID_E_INVALID, "%s: first = %d, count = %d: the points [%d, %lld) do not lie inside the [0, %d) of the network", call, first,
+                    count, first, (long long)first + (long long)count, P);
+    TRY(check_record(c, call, record_dev, &member_stride));
+    return observe_range(c, field, first, count, record_dev, member_stride);
 }
 
 // Through the staging buffer of fluid_download_members, whatever its size: as many whole members per group as fit in it,
@@ -3437,7 +3503,7 @@ int fluid_observe_members_host(fluid_ctx* c, int field, float* host)
     TRY(check_observe(c, "fluid_observe_members_host", field));
     TRY(ensure_stage(c, "fluid_observe_members_host"));
     ObservedFrom from;
-    TRY(settle_for_observing(c, field, &from));
+    TRY(settle_for_observing(c, GramSource(field), &from));
     const size_t P = (size_t)c->observe.points, room = (size_t)c->stage.members * member_cells(c);
     const int group = (int)std::max<size_t>(1, std::min<size_t>((size_t)c->members, room / P));
     const size_t piece = std::min(P, room);
@@ -3461,33 +3527,36 @@ int fluid_observe_members_host(fluid_ctx* c, int field, float* host)
     return FLUID_OK;
 }
 
-int fluid_observation_gram(fluid_ctx* c, int field, int centre, const float* obs, const float* inv_sigma, double* gram, double* rhs, double* dd)
+// fluid_observation_gram / fluid_observation_gram_recorded: one body, under the caller's name
+static int observation_gram_body(fluid_ctx* c, const char* call, GramSource src, int centre, const float* obs, const float* inv_sigma,
+                                 double* gram, double* rhs, double* dd)
 {
-    if (!gram) return fail(FLUID_E_INVALID, "fluid_observation_gram: null array `gram`");
-    if (!obs && (rhs || dd)) return fail(FLUID_E_INVALID, "fluid_observation_gram: `%s` is given but `obs` is null", rhs ? "rhs" : "dd");
-    if (!c) return fail(FLUID_E_INVALID, "fluid_observation_gram: null context");
-    if (field != FLUID_FIELD_OF_POINT && !c->valid_field(field)) return fail(FLUID_E_INVALID, "fluid_observation_gram: bad field id %d", field);
+    if (!gram) return fail(FLUID_E_INVALID, "%s: null array `gram`", call);
+    if (!obs && (rhs || dd)) return fail(FLUID_E_INVALID, "%s: `%s` is given but `obs` is null", call, rhs ? "rhs" : "dd");
+    if (!c) return fail(FLUID_E_INVALID, "%s: null context", call);
+    if (!src.record && src.field != FLUID_FIELD_OF_POINT && !c->valid_field(src.field))
+        return fail(FLUID_E_INVALID, "%s: bad field id %d", call, src.field);
     if (c->members > FLUID_TRANSFORM_MAX_MEMBERS)
-        return fail(FLUID_E_INVALID, "fluid_observation_gram: this context has %d members, above FLUID_TRANSFORM_MAX_MEMBERS = %d", c->members,
+        return fail(FLUID_E_INVALID, "%s: this context has %d members, above FLUID_TRANSFORM_MAX_MEMBERS = %d", call, c->members,
                     FLUID_TRANSFORM_MAX_MEMBERS);
-    TRY(check_observe(c, "fluid_observation_gram", field));
+    TRY(check_gram_source(c, call, &src));
     Observation& o = c->observe;
     const size_t P = (size_t)o.points;
     if (inv_sigma)
         for (size_t p = 0; p < P; ++p)
-            if (!std::isfinite(inv_sigma[p]))
-                return fail(FLUID_E_INVALID, "fluid_observation_gram: inv_sigma[%zu] (point %zu) is not finite", p, p);
+            if (!std::isfinite(inv_sigma[p])) return fail(FLUID_E_INVALID, "%s: inv_sigma[%zu] (point %zu) is not finite", call, p, p);
     const int M = c->members, mp = fluid::gram_padded(M);
     const size_t entries = fluid::observation_gram_entries(M) * sizeof(double);
     // partials for the blocks of this network (a larger network later: they grow), the folded result and its twin
-    TRY(reserve(c, o.partials, entries * (size_t)fluid::observation_gram_blocks(o.points, M), false, "fluid_observation_gram", "partial results"));
-    TRY(reserve(c, o.result, entries, true, "fluid_observation_gram", "the result"));
+    TRY(reserve(c, o.partials, entries * (size_t)fluid::observation_gram_blocks(o.points, M), false, call, "partial results"));
+    TRY(reserve(c, o.result, entries, true, call, "the result"));
     if (obs) HIP_TRY(hipMemcpyAsync(o.obs(), obs, P * sizeof(float), hipMemcpyHostToDevice, c->stream));
     if (inv_sigma) HIP_TRY(hipMemcpyAsync(o.sigma(), inv_sigma, P * sizeof(float), hipMemcpyHostToDevice, c->stream));
     ObservedFrom from;
-    TRY(settle_for_observing(c, field, &from));
+    TRY(settle_for_observing(c, src, &from));
     fluid::launch_observation_gram(c->stream, c->st, from.x, c->pitch, c->mb(), from.inv, from.sources(), observation_points(c), centre != 0,
-                                   obs ? o.obs() : nullptr, inv_sigma ? o.sigma() : nullptr, o.partials.d<double>(), o.result.d<double>());
+                                   obs ? o.obs() : nullptr, inv_sigma ? o.sigma() : nullptr, o.partials.d<double>(), o.result.d<double>(),
+                                   from.recorded());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(o.result.host, o.result.dev, entries, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -3498,6 +3567,19 @@ int fluid_observation_gram(fluid_ctx* c, int field, int centre, const float* obs
         for (int k = 0; k < M; ++k) rhs[k] = host[(size_t)mp * mp + k];
     if (dd) *dd = host[(size_t)mp * mp + mp];
     return FLUID_OK;
+}
+
+int fluid_observation_gram(fluid_ctx* c, int field, int centre, const float* obs, const float* inv_sigma, double* gram, double* rhs, double* dd)
+{
+    return observation_gram_body(c, "fluid_observation_gram", GramSource(field), centre, obs, inv_sigma, gram, rhs, dd);
+}
+
+int fluid_observation_gram_recorded(fluid_ctx* c, const void* record_dev, size_t member_stride, int centre, const float* obs,
+                                    const float* inv_sigma, double* gram, double* rhs, double* dd)
+{
+    const char* call = "fluid_observation_gram_recorded";
+    if (!record_dev) return fail(FLUID_E_INVALID, "%s: null device pointer `record_dev`", call);
+    return observation_gram_body(c, call, {record_dev, member_stride}, centre, obs, inv_sigma, gram, rhs, dd);
 }
 
 // ---- lattice observations: fluid_observation_gram_lattice ------------------------------------------------------------------
@@ -3537,10 +3619,10 @@ static void lattice_pairs(const fluid_ctx* c, int nodes_row, int nodes_col, int 
 // call's own pointers, the point lists (built, cached and uploaded here and nowhere else), and the two launches that leave
 // every node's result in LatticeGram::out.  Nothing is waited for, except where the lists an analysis in flight may still
 // read are about to be rewritten, or a buffer grows (reserve).
-static int enqueue_lattice_gram(fluid_ctx* c, const char* call, int field, int centre, const float* obs, const float* inv_sigma, int nodes_row,
-                                int nodes_col, int row0, int col0, int step, float hw)
+static int enqueue_lattice_gram(fluid_ctx* c, const char* call, GramSource src, int centre, const float* obs, const float* inv_sigma,
+                                int nodes_row, int nodes_col, int row0, int col0, int step, float hw)
 {
-    TRY(check_observe(c, call, field));
+    TRY(check_gram_source(c, call, &src));
     if (c->members > FLUID_TRANSFORM_MAX_MEMBERS)
         return fail(FLUID_E_INVALID, "%s: this context has %d members, above FLUID_TRANSFORM_MAX_MEMBERS = %d", call, c->members,
                     FLUID_TRANSFORM_MAX_MEMBERS);
@@ -3611,23 +3693,24 @@ static int enqueue_lattice_gram(fluid_ctx* c, const char* call, int field, int c
     if (obs) HIP_TRY(hipMemcpyAsync(o.obs(), obs, P * sizeof(float), hipMemcpyHostToDevice, c->stream));
     if (inv_sigma) HIP_TRY(hipMemcpyAsync(o.sigma(), inv_sigma, P * sizeof(float), hipMemcpyHostToDevice, c->stream));
     ObservedFrom from;
-    TRY(settle_for_observing(c, field, &from));
+    TRY(settle_for_observing(c, src, &from));
     const fluid::LatticeLists lists = {g.lists.d<int>(), g.lists.d<int2>(start_bytes), (int)B};
     fluid::launch_observation_gram_lattice(c->stream, c->st, from.x, c->pitch, c->mb(), from.inv, from.sources(), observation_points(c), centre != 0,
                                            obs ? o.obs() : nullptr, inv_sigma ? o.sigma() : nullptr, g.operands.d<double>(), lists,
-                                           g.out.d<double>());
+                                           g.out.d<double>(), from.recorded());
     HIP_TRY(hipGetLastError());
     return FLUID_OK;
 }
 
-int fluid_observation_gram_lattice(fluid_ctx* c, int field, int centre, const float* obs, const float* inv_sigma, int nodes_row, int nodes_col,
-                                   int row0, int col0, int step, float hw, double* gram, double* rhs, double* dd, int* counts)
+// fluid_observation_gram_lattice / fluid_observation_gram_lattice_recorded: one body, under the caller's name
+static int lattice_gram_body(fluid_ctx* c, const char* call, const GramSource& src, int centre, const float* obs, const float* inv_sigma,
+                             int nodes_row, int nodes_col, int row0, int col0, int step, float hw, double* gram, double* rhs, double* dd,
+                             int* counts)
 {
-    const char* call = "fluid_observation_gram_lattice";
     if (!gram) return fail(FLUID_E_INVALID, "%s: null array `gram`", call);
     if (!obs && (rhs || dd)) return fail(FLUID_E_INVALID, "%s: `%s` is given but `obs` is null", call, rhs ? "rhs" : "dd");
     if (!c) return fail(FLUID_E_INVALID, "%s: null context", call);
-    TRY(enqueue_lattice_gram(c, call, field, centre, obs, inv_sigma, nodes_row, nodes_col, row0, col0, step, hw));
+    TRY(enqueue_lattice_gram(c, call, src, centre, obs, inv_sigma, nodes_row, nodes_col, row0, col0, step, hw));
     LatticeGram& g = c->lgram;
     const size_t B = (size_t)nodes_row * (size_t)nodes_col;
     const int M = c->members, mp = fluid::gram_padded(M);
@@ -3648,6 +3731,23 @@ int fluid_observation_gram_lattice(fluid_ctx* c, int field, int centre, const fl
         if (dd) dd[b] = count ? r[(size_t)mp * mp + mp] : 0.0;
     }
     return FLUID_OK;
+}
+
+int fluid_observation_gram_lattice(fluid_ctx* c, int field, int centre, const float* obs, const float* inv_sigma, int nodes_row, int nodes_col,
+                                   int row0, int col0, int step, float hw, double* gram, double* rhs, double* dd, int* counts)
+{
+    return lattice_gram_body(c, "fluid_observation_gram_lattice", GramSource(field), centre, obs, inv_sigma, nodes_row, nodes_col, row0, col0, step, hw,
+                             gram, rhs, dd, counts);
+}
+
+int fluid_observation_gram_lattice_recorded(fluid_ctx* c, const void* record_dev, size_t member_stride, int centre, const float* obs,
+                                            const float* inv_sigma, int nodes_row, int nodes_col, int row0, int col0, int step, float hw,
+                                            double* gram, double* rhs, double* dd, int* counts)
+{
+    const char* call = "fluid_observation_gram_lattice_recorded";
+    if (!record_dev) return fail(FLUID_E_INVALID, "%s: null device pointer `record_dev`", call);
+    return lattice_gram_body(c, call, {record_dev, member_stride}, centre, obs, inv_sigma, nodes_row, nodes_col, row0, col0, step, hw, gram, rhs,
+                             dd, counts);
 }
 
 // ---- one-call analysis: fluid_etkf_increments, fluid_analyse_lattice, fluid_analyse_lattice_status -------------------------
@@ -3718,10 +3818,10 @@ int fluid_etkf_increments(fluid_ctx* c, int nodes, const double* gram, const dou
     return FLUID_OK;
 }
 
-int fluid_analyse_lattice(fluid_ctx* c, int field, const float* obs, const float* inv_sigma, int nodes_row, int nodes_col, int row0, int col0,
-                          int step, float hw, float rho, const int* fields, int nfields)
+// fluid_analyse_lattice / fluid_analyse_lattice_recorded: one body, under the caller's name
+static int analyse_lattice_body(fluid_ctx* c, const char* call, const GramSource& src, const float* obs, const float* inv_sigma, int nodes_row,
+                                int nodes_col, int row0, int col0, int step, float hw, float rho, const int* fields, int nfields)
 {
-    const char* call = "fluid_analyse_lattice";
     if (!obs) return fail(FLUID_E_INVALID, "%s: null array `obs`", call);
     if (!fields) return fail(FLUID_E_INVALID, "%s: null array `fields`", call);
     if (!c) return fail(FLUID_E_INVALID, "%s: null context", call);
@@ -3730,7 +3830,7 @@ int fluid_analyse_lattice(fluid_ctx* c, int field, const float* obs, const float
     // the status words: one int per node of the largest lattice, and their twin
     TRY(reserve(c, c->etkf.status, (size_t)FLUID_LATTICE_MAX_NODES * sizeof(int), true, call, "status words"));
     // the two Gram launches: every node's C, rhs and dd in LatticeGram::out, its point count in the start offsets of the lists
-    TRY(enqueue_lattice_gram(c, call, field, /*centre=*/1, obs, inv_sigma, nodes_row, nodes_col, row0, col0, step, hw));
+    TRY(enqueue_lattice_gram(c, call, src, /*centre=*/1, obs, inv_sigma, nodes_row, nodes_col, row0, col0, step, hw));
     const int M = c->members, MP = fluid::transform_padded(M), mp = fluid::gram_padded(M), nodes = nodes_row * nodes_col;
     const size_t E = fluid::observation_gram_entries(M);
     const size_t table_bytes = (size_t)nodes * M * MP * sizeof(double), bits_bytes = (size_t)nodes * M * sizeof(unsigned long long);
@@ -3772,6 +3872,23 @@ int fluid_analyse_lattice(fluid_ctx* c, int field, const float* obs, const float
     return FLUID_OK;
 }
 
+int fluid_analyse_lattice(fluid_ctx* c, int field, const float* obs, const float* inv_sigma, int nodes_row, int nodes_col, int row0, int col0,
+                          int step, float hw, float rho, const int* fields, int nfields)
+{
+    return analyse_lattice_body(c, "fluid_analyse_lattice", GramSource(field), obs, inv_sigma, nodes_row, nodes_col, row0, col0, step, hw, rho, fields,
+                                nfields);
+}
+
+int fluid_analyse_lattice_recorded(fluid_ctx* c, const void* record_dev, size_t member_stride, const float* obs, const float* inv_sigma,
+                                   int nodes_row, int nodes_col, int row0, int col0, int step, float hw, float rho, const int* fields,
+                                   int nfields)
+{
+    const char* call = "fluid_analyse_lattice_recorded";
+    if (!record_dev) return fail(FLUID_E_INVALID, "%s: null device pointer `record_dev`", call);
+    return analyse_lattice_body(c, call, {record_dev, member_stride}, obs, inv_sigma, nodes_row, nodes_col, row0, col0, step, hw, rho, fields,
+                                nfields);
+}
+
 int fluid_analyse_lattice_status(fluid_ctx* c, int* solved, int* empty, int* failed)
 {
     const char* call = "fluid_analyse_lattice_status";
@@ -3795,8 +3912,51 @@ int fluid_analyse_lattice_status(fluid_ctx* c, int* solved, int* empty, int* fai
 // consumes them, or fluid_step's rule; after every `every`-th step each listed field packed into its snapshot slot.
 // factor 0: the dense snapshots of fluid_run / fluid_run_members; a coarse factor: every snapshot pack is the block-averaged one
 // and `snapshots` / `capacity` count coarse floats (the sources stay full resolution).
+// A window (fluid_run_window; null for every other run): the slots in the order they are observed -- by step, slots of one
+// step in slot order -- and where the next one is.  Before the first step and behind every step's snapshot packs run_body
+// observes the slots due, each one a fluid_observe_members_range.
+struct WindowSchedule {
+    const fluid_obs_window* w = nullptr;
+    size_t stride = 0;                    // w->member_stride, resolved
+    std::vector<int> order;
+    size_t next = 0;
+};
+
+static int observe_due(fluid_ctx* c, WindowSchedule* ws, int steps_done)
+{
+    const fluid_obs_window* w = ws->w;
+    for (; ws->next < ws->order.size() && w->slot_step[ws->order[ws->next]] == steps_done; ++ws->next) {
+        const int s = ws->order[ws->next], first = w->slot_first[s];
+        TRY(observe_range(c, w->field, first, w->slot_first[s + 1] - first, w->record_dev, ws->stride));
+    }
+    return FLUID_OK;
+}
+
+// what fluid_run_window refuses of its window, and the schedule
+static int check_window(const fluid_ctx* c, const char* call, const fluid_run_plan* p, const fluid_obs_window* w, WindowSchedule* ws)
+{
+    TRY(check_observe(c, call, w->field));
+    const int P = c->observe.points;
+    if (p->nsteps < 0) return fail(FLUID_E_INVALID, "%s: nsteps < 0", call);
+    for (int s = 0; s < w->nslots; ++s) {
+        const int lo = w->slot_first[s], hi = w->slot_first[s + 1];
+        if (lo < 0 || lo > hi || hi > P)
+            return fail(FLUID_E_INVALID, "%s: slot %d holds points [%d, %d): the slots' points must not decrease and lie inside [0, %d points]",
+                        call, s, lo, hi, P);
+        if (w->slot_step[s] < 0 || w->slot_step[s] > p->nsteps)
+            return fail(FLUID_E_INVALID, "%s: slot %d is observed after %d steps, outside [0, nsteps = %d]", call, s, w->slot_step[s], p->nsteps);
+    }
+    ws->w = w;
+    ws->stride = w->member_stride;
+    TRY(check_record(c, call, w->record_dev, &ws->stride));
+    ws->order.resize((size_t)w->nslots);
+    for (int s = 0; s < w->nslots; ++s) ws->order[(size_t)s] = s;
+    std::stable_sort(ws->order.begin(), ws->order.end(), [w](int a, int b) { return w->slot_step[a] < w->slot_step[b]; });
+    return FLUID_OK;
+}
+
 static int run_body(fluid_ctx* c, const char* call, const MemberVal& dt, const MemberVal& diff, const MemberVal& visc, const fluid_run_plan* p,
-                    int factor, int* snapshots_written)
+                    int factor, int* snapshots_written, WindowSchedule* window = nullptr)
 {
     TRY(refuse_slabs(c, call));
     if (factor) TRY(check_factor(call, c->n, factor));
@@ -3821,6 +3981,7 @@ static int run_body(fluid_ctx* c, const char* call, const MemberVal& dt, const M
     if (p->sources) TRY(check_device_span(c, call, "sources", p->sources, 3 * block * sizeof(float)));
     const float* src = static_cast<const float*>(p->sources);
     float* snap = static_cast<float*>(p->snapshots);
+    if (window) TRY(observe_due(c, window, 0));
     for (int z = 0; z < p->nsteps; ++z) {
         if (src) {
             for (int k = 0; k < 3; ++k) TRY(unpack_range(c, FLUID_U_PREV + k, 0, c->members, src + (size_t)k * block, cells));
@@ -3833,6 +3994,7 @@ static int run_body(fluid_ctx* c, const char* call, const MemberVal& dt, const M
                 TRY(pack_range(c, p->fields[k], 0, c->members, snap, snap_cells, factor));
                 snap += snap_block;
             }
+        if (window) TRY(observe_due(c, window, z + 1));
     }
     HIP_TRY(hipGetLastError());
     if (snapshots_written) *snapshots_written = snapshots;
@@ -3855,15 +4017,18 @@ int fluid_run_coarse(fluid_ctx* c, float dt, float diff, float visc, const fluid
 }
 
 // fluid_run_members (factor 0) / fluid_run_members_coarse
+// ... / fluid_run_window (either factor; `window` non-null)
 static int run_members_body(fluid_ctx* c, const char* call, const float* dt, const float* diff, const float* visc, const fluid_run_plan* plan,
-                            int factor, int* snapshots_written)
+                            int factor, int* snapshots_written, const fluid_obs_window* window = nullptr)
 {
     if (!plan) return fail(FLUID_E_INVALID, "%s: null plan", call);
     TRY(check_member_args(c, call, {{"dt", dt}, {"diff", diff}, {"visc", visc}}));
-    if (c->members == 1) return run_body(c, call, dt[0], diff[0], visc[0], plan, factor, snapshots_written);
+    WindowSchedule schedule, *ws = window ? &schedule : nullptr;
+    if (window) TRY(check_window(c, call, plan, window, ws));
+    if (c->members == 1) return run_body(c, call, dt[0], diff[0], visc[0], plan, factor, snapshots_written, ws);
     if (factor) TRY(check_factor(call, c->n, factor));      // before ensure_consts: a refusal changes nothing
     TRY(ensure_consts(c));
-    return run_body(c, call, {dt, c->members}, {diff, c->members}, {visc, c->members}, plan, factor, snapshots_written);
+    return run_body(c, call, {dt, c->members}, {diff, c->members}, {visc, c->members}, plan, factor, snapshots_written, ws);
 }
 
 int fluid_run_members(fluid_ctx* c, const float* dt, const float* diff, const float* visc, const fluid_run_plan* plan, int* snapshots_written)
@@ -3876,6 +4041,20 @@ int fluid_run_members_coarse(fluid_ctx* c, const float* dt, const float* diff, c
 {
     TRY(refuse_factor_zero("fluid_run_members_coarse", factor));
     return run_members_body(c, "fluid_run_members_coarse", dt, diff, visc, plan, factor, snapshots_written);
+}
+
+// fluid_run_window (include/fluid_amd.h "asynchronous observations"): the members' run of either kind with a window
+int fluid_run_window(fluid_ctx* c, const float* dt, const float* diff, const float* visc, const fluid_run_plan* plan, int factor,
+                     const fluid_obs_window* window, int* snapshots_written)
+{
+    const char* call = "fluid_run_window";
+    if (!window) return fail(FLUID_E_INVALID, "%s: null window", call);
+    if (!window->record_dev) return fail(FLUID_E_INVALID, "%s: null device pointer `record_dev`", call);
+    if (window->nslots < 0 || window->nslots > FLUID_WINDOW_MAX_SLOTS)
+        return fail(FLUID_E_INVALID, "%s: nslots = %d outside [0, FLUID_WINDOW_MAX_SLOTS = %d]", call, window->nslots, FLUID_WINDOW_MAX_SLOTS);
+    if (window->nslots > 0 && !window->slot_first) return fail(FLUID_E_INVALID, "%s: null array `slot_first`", call);
+    if (window->nslots > 0 && !window->slot_step) return fail(FLUID_E_INVALID, "%s: null array `slot_step`", call);
+    return run_members_body(c, call, dt, diff, visc, plan, factor, snapshots_written, window);
 }
 
 // ---- timing -------------------------------------------------------------------

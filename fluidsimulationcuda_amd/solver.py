@@ -314,15 +314,9 @@ class FluidSolver:
                                                      None if y is None else rhs.ctypes.data_as(dp), None if y is None else C.byref(dd)))
         return g if y is None else (g, rhs, dd.value)
 
-    def run(self, nsteps, every=0, fields=(), sources=None, out=None, dt=DT, diff=DIFF, visc=VIS, iters=ITERS, use_sources=False,
-            wait=True, coarse=None):
-        """nsteps steps without the host in the loop.  `sources`: a dense device array (3, members, N+2, N+2) -- u_prev,
-        v_prev, dens_prev -- put back before EVERY step (a forced run); None: step()'s rule.  every > 0: after every
-        `every`-th step the listed fields are recorded into `out`, a dense device array (snapshots, len(fields), members,
-        N+2, N+2) (None: a torch tensor of that shape is allocated).  Returns (out, snapshots written); out is None when
-        nothing is recorded.  dt / diff / visc: a scalar or one value per member, like step.  `wait`: as for pack.
-        coarse=r: the snapshots are block-averaged like pack(coarse=r), `out` is (snapshots, len(fields), members, C, C);
-        the sources stay full resolution."""
+    def _run_plan(self, nsteps, every, fields, sources, out, iters, use_sources, coarse):
+        """The capi.RunPlan of run() and run_window(), and the snapshot array it records into: `out`, a new tensor when it
+        is None and something is recorded, None when nothing is."""
         w = self.n + 2 if coarse is None else coarse_size(self.n, coarse)
         ids = [_fid(f) for f in fields]
         every, nsteps = int(every), int(nsteps)
@@ -337,6 +331,18 @@ class FluidSolver:
                             sources=device_address(sources) if sources is not None else None, every=every,
                             fields=(C.c_int * len(ids))(*ids) if ids else None, nfields=len(ids),
                             snapshots=device_address(out) if every > 0 else None, capacity=capacity)
+        return plan, (out if every > 0 else None)
+
+    def run(self, nsteps, every=0, fields=(), sources=None, out=None, dt=DT, diff=DIFF, visc=VIS, iters=ITERS, use_sources=False,
+            wait=True, coarse=None):
+        """nsteps steps without the host in the loop.  `sources`: a dense device array (3, members, N+2, N+2) -- u_prev,
+        v_prev, dens_prev -- put back before EVERY step (a forced run); None: step()'s rule.  every > 0: after every
+        `every`-th step the listed fields are recorded into `out`, a dense device array (snapshots, len(fields), members,
+        N+2, N+2) (None: a torch tensor of that shape is allocated).  Returns (out, snapshots written); out is None when
+        nothing is recorded.  dt / diff / visc: a scalar or one value per member, like step.  `wait`: as for pack.
+        coarse=r: the snapshots are block-averaged like pack(coarse=r), `out` is (snapshots, len(fields), members, C, C);
+        the sources stay full resolution."""
+        plan, out = self._run_plan(nsteps, every, fields, sources, out, iters, use_sources, coarse)
         written = C.c_int()
         mv = member_values(self.members, dt=dt, diff=diff, visc=visc)
         self._handover(wait)
@@ -346,7 +352,7 @@ class FluidSolver:
         capi.check(fn(self._h, *((dt, diff, visc) if mv is None else [_mf(a) for a in mv.values()]), *tail))
         if wait:
             self.synchronize()
-        return (out if every > 0 else None), written.value
+        return out, written.value
 
     def member_count(self):
         m = C.c_int()
@@ -734,6 +740,111 @@ class FluidSolver:
         self.noise((white,), 1.0, seed, sequence, capi.NOISE_SET)
         capi.check(capi.lib().fluid_op_diffuse_members(self._h, int(b), _fid(smooth), _fid(white), _mf(mv["alpha"]), _mf(mv["beta"]), int(iters)))
         capi.check(capi.lib().fluid_op_add_source_members(self._h, _fid(field), _fid(smooth), _mf(self._amplitudes(amplitude))))
+
+    # -- asynchronous observations: H x recorded during a run, the analysis formed from the record
+    def _per_point(self, a, name):
+        if a is None:
+            return None
+        points = self.observation_points()
+        a = np.ascontiguousarray(np.asarray(a, np.float32).ravel())
+        if a.size != points:
+            raise ValueError("%s must hold one value per point (%d), got %d" % (name, points, a.size))
+        return a
+
+    def _record(self, record, member_stride):
+        """A record to write: `record`, or -- None -- a new (members, points) float32 torch tensor of zeros."""
+        if record is None:
+            points = self.observation_points()
+            if member_stride not in (0, points):
+                raise ValueError("record=None allocates a dense tensor: member_stride must be 0")
+            import torch
+            record = torch.zeros((self.members, points), dtype=torch.float32, device="cuda")
+        return record
+
+    def observe_range(self, first, count, out, field=None, member_stride=0, wait=True):
+        """observe_device for the points [first, first + count) only: out[m * member_stride + p] for those p, every other
+        float of `out` keeps its bits; one launch, count = 0 launches nothing.  `out` is a RECORD: the layout of
+        observe_device's array, whole network wide (include/fluid_amd.h, "asynchronous observations").  `wait`: as for
+        pack.  Returns `out`."""
+        self._handover(wait)
+        capi.check(capi.lib().fluid_observe_members_range(self._h, _ofid(field), int(first), int(count), device_address(out),
+                                                          int(member_stride)))
+        if wait:
+            self.synchronize()
+        return out
+
+    def run_window(self, nsteps, slot_first, slot_step, record=None, field=None, member_stride=0, every=0, fields=(), sources=None,
+                   out=None, dt=DT, diff=DIFF, visc=VIS, iters=ITERS, use_sources=False, wait=True, coarse=None):
+        """run() that observes on the way: slot s, the points [slot_first[s], slot_first[s + 1]) of the network, is observed
+        into `record` after slot_step[s] steps (0: before the first), behind that step's snapshots -- each an
+        observe_range(slot_first[s], slot_first[s + 1] - slot_first[s], record, field, member_stride).  len(slot_first) =
+        len(slot_step) + 1 (both empty: the plain run).  record=None: a (members, points) tensor of zeros is allocated, so
+        that points in no slot read 0.  The other keywords are run()'s.  Returns (record, out, snapshots written)."""
+        first, step = [int(v) for v in slot_first], [int(v) for v in slot_step]
+        if (first or step) and len(first) != len(step) + 1:
+            raise ValueError("slot_first must hold one more entry than slot_step (%d), got %d" % (len(step), len(first)))
+        record = self._record(record, member_stride)
+        plan, out = self._run_plan(nsteps, every, fields, sources, out, iters, use_sources, coarse)
+        window = capi.ObsWindow(field=_ofid(field), nslots=len(step), slot_first=(C.c_int * len(first))(*first) if step else None,
+                                slot_step=(C.c_int * len(step))(*step) if step else None, record_dev=device_address(record),
+                                member_stride=int(member_stride))
+        written = C.c_int()
+        mv = [np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float32), (self.members,))) for v in (dt, diff, visc)]
+        self._handover(wait)
+        capi.check(capi.lib().fluid_run_window(self._h, *[_mf(a) for a in mv], C.byref(plan), 0 if coarse is None else int(coarse),
+                                               C.byref(window), C.byref(written)))
+        if wait:
+            self.synchronize()
+        return record, out, written.value
+
+    def observation_gram_recorded(self, record, obs=None, inv_sigma=None, centre=True, member_stride=0):
+        """observation_gram with h_k[p] read from a record, record[k * member_stride + p], instead of sampled: no field is
+        settled or read (include/fluid_amd.h, "asynchronous observations").  A record observe_device just wrote gives
+        observation_gram's bits.  What torch's current stream still owes the record is waited for first."""
+        y, s = self._per_point(obs, "obs"), self._per_point(inv_sigma, "inv_sigma")
+        dp = C.POINTER(C.c_double)
+        g = np.empty((self.members, self.members), np.float64)
+        rhs, dd = np.empty(self.members, np.float64), C.c_double()
+        self._handover(True)
+        capi.check(capi.lib().fluid_observation_gram_recorded(
+            self._h, device_address(record), int(member_stride), 1 if centre else 0, None if y is None else _mf(y),
+            None if s is None else _mf(s), g.ctypes.data_as(dp), None if y is None else rhs.ctypes.data_as(dp),
+            None if y is None else C.byref(dd)))
+        return g if y is None else (g, rhs, dd.value)
+
+    def observation_gram_lattice_recorded(self, record, shape, origin, step, c, obs=None, inv_sigma=None, centre=True, member_stride=0):
+        """observation_gram_lattice from a record: the same returns, the same point lists and their cache."""
+        y, s = self._per_point(obs, "obs"), self._per_point(inv_sigma, "inv_sigma")
+        nr, nc = (int(v) for v in shape)
+        row0, col0 = (int(v) for v in origin)
+        m, dp = self.members, C.POINTER(C.c_double)
+        room = (max(nr, 0), max(nc, 0))                  # (a refused shape still needs arrays to hand over)
+        g = np.empty(room + (m, m), np.float64)
+        rhs, dd = np.empty(room + (m,), np.float64), np.empty(room, np.float64)
+        counts = np.empty(room, np.int32)
+        self._handover(True)
+        capi.check(capi.lib().fluid_observation_gram_lattice_recorded(
+            self._h, device_address(record), int(member_stride), 1 if centre else 0, None if y is None else _mf(y),
+            None if s is None else _mf(s), nr, nc, row0, col0, int(step), float(c), g.ctypes.data_as(dp),
+            None if y is None else rhs.ctypes.data_as(dp), None if y is None else dd.ctypes.data_as(dp),
+            counts.ctypes.data_as(C.POINTER(C.c_int))))
+        return (g, counts) if y is None else (g, rhs, dd, counts)
+
+    def analyse_lattice_recorded(self, record, shape, origin, step, c, obs, inv_sigma=None, rho=1.0, fields=("dens", "u", "v"), wait=True,
+                                 member_stride=0):
+        """analyse_lattice from a record: the weights come from what the members showed when each observation was taken,
+        and are applied to `fields` as they are now -- the 4D-LETKF of a window recorded by run_window.  Only `fields` are
+        settled and updated; analyse_status() serves this call too."""
+        y, s = self._per_point(obs, "obs"), self._per_point(inv_sigma, "inv_sigma")
+        nr, nc = (int(v) for v in shape)
+        row0, col0 = (int(v) for v in origin)
+        ids = [_fid(f) for f in fields]
+        self._handover(wait)
+        capi.check(capi.lib().fluid_analyse_lattice_recorded(
+            self._h, device_address(record), int(member_stride), None if y is None else _mf(y), None if s is None else _mf(s), nr, nc,
+            row0, col0, int(step), float(c), float(rho), (C.c_int * len(ids))(*ids), len(ids)))
+        if wait:
+            self.synchronize()
 
     def set_jacobi_variant(self, variant):
         capi.check(capi.lib().fluid_set_jacobi_variant(self._h, variant))

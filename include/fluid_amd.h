@@ -969,6 +969,78 @@ int fluid_noise_dense(fluid_ctx *ctx, void *out_dev, size_t count, float amplitu
                       int stream_id);
 int fluid_noise_value(unsigned long long seed, unsigned int sequence, int tag, int member_id, unsigned int c0, unsigned int c1, double *z);
 
+/* ---- asynchronous observations: record H x during a run, analyse from the record -------------------------------------------
+ * M = fluid_members(ctx), P = the points of the resident network.  Everything above takes every observation at the analysis
+ * time: the observing calls sample the fields as they are now.  Real networks report all through the forecast window; the
+ * standard answer is 4D-LETKF (Hunt et al. 2004, 2007): apply the observation operator to every member at the time each
+ * observation was taken, during the forecast, keep those values H x, and at the end of the window form the same M x M
+ * problem from the kept values and apply its weights to the state at the end of the window.  Nothing in the algebra
+ * changes, only where h_k[p] comes from.  A 4D cycle is fluid_noise_members -> fluid_member_spread -> fluid_run_window ->
+ * fluid_analyse_lattice_recorded -> fluid_relax_spread, nothing crossing to the host.
+ *
+ * A RECORD is a dense DEVICE float array: record[m * member_stride + p] = h_m[p].  member_stride = 0: P; any other value
+ * must be at least P (the floats in between are not touched).  Alignment: 4 bytes.  Its extent is (M - 1) * member_stride +
+ * P floats inside one allocation.  This is exactly the out_dev of fluid_observe_members.
+ *
+ * - fluid_observe_members_range is fluid_observe_members for the points [first, first + count) only: for those p and every
+ *   member, record[m * member_stride + p] gets the bits fluid_observe_members would write there -- the same definition of h,
+ *   the same settling, the same fp16 scale; FLUID_FIELD_OF_POINT on a typed network is allowed.  Every other float of the
+ *   record keeps its bits.  One kernel launch whatever M and count are, on the context's stream, no wait; count = 0
+ *   launches nothing.
+ * - fluid_run_window: the caller orders the network by report time; a SLOT is a contiguous range of points, slot s the points
+ *   [slot_first[s], slot_first[s + 1]), observed after slot_step[s] steps of the run.  The call is defined as a sequence of
+ *   existing calls, bit for bit in every field of every member, every snapshot and the record: it is fluid_run_members when
+ *   factor == 0 and fluid_run_members_coarse with that factor otherwise; before the first step it observes the slots with
+ *   slot_step[s] == 0, in slot order; after step t, behind that step's snapshot packs if any, the slots with slot_step[s] ==
+ *   t, in slot order.  Each observation is fluid_observe_members_range(ctx, window->field, slot_first[s], slot_first[s + 1] -
+ *   slot_first[s], record_dev, member_stride).  Empty slots launch nothing; points in no slot are never written; several
+ *   slots may share a step; slots need not be in time order.  No wait anywhere.  nslots == 0 is the plain run, bit for bit, but not
+ *   the plain call: the window is checked whatever nslots is, so a network must be set and record_dev must be a record of
+ *   full extent even when nothing will be written to it.  The host
+ *   arrays and the struct belong to the caller again when the call returns.
+ * - fluid_observation_gram_recorded, fluid_observation_gram_lattice_recorded and fluid_analyse_lattice_recorded are their
+ *   namesakes with rule 1 replaced by h_k[p] = record[k * member_stride + p].  The float is read in stream order: a record
+ *   written earlier on the context's stream needs no wait.  Everything after rule 1 is untouched, operation for operation:
+ *   the mean chain, 1 / sigma and the innovation, the chunks of 64 points and the wave order, the folds, the point lists and
+ *   their cache (the same cache, shared with the direct calls), the weights, the solve, the lattice update and the status
+ *   words (fluid_analyse_lattice_status serves both).  So:
+ *    1. A record that fluid_observe_members just wrote gives the direct call's bits.
+ *    2. No field is settled or read by the two Gram calls; fluid_analyse_lattice_recorded settles and updates only the listed
+ *       `fields` -- the state at the END of the window, which is the point of the method.
+ *    3. The network must be set: it supplies the positions and P.  Whether it is typed does not matter.
+ *    4. Poisoning follows the namesakes, "a non-finite h_k" meaning a non-finite float in the record.
+ *   The library does not know which points were recorded.  For points that were left out: zero-fill the record first and
+ *   give such points inv_sigma 0.
+ * Refusals, all FLUID_E_INVALID with a message that names the call and, where it applies, the slot or the point, found
+ * before anything is launched or any state changes, null pointers before the context is looked at: whatever the namesake
+ * refuses, under the new name; a null record_dev, window, plan, dt, diff or visc; a null slot_first or slot_step with
+ * nslots > 0; nslots outside [0, FLUID_WINDOW_MAX_SLOTS] (the message gives both numbers); first, count or first + count
+ * outside [0, P]; a slot_first that decreases, starts below 0 or ends above P (the slot is named); a slot_step[s] outside
+ * [0, nsteps] (the slot is named); a stride below P; a record that is not device memory of the context's device or whose
+ * extent does not lie inside one allocation (asked of the runtime on the host, as for a pack); no network set;
+ * FLUID_FIELD_OF_POINT on an untyped network; M > FLUID_TRANSFORM_MAX_MEMBERS for the three recorded calls; row slabs.
+ * The launches belong to none of the fluid_timing categories. */
+#define FLUID_WINDOW_MAX_SLOTS 65536
+typedef struct fluid_obs_window {
+    int field;              /* field id or FLUID_FIELD_OF_POINT */
+    int nslots;             /* 0 .. FLUID_WINDOW_MAX_SLOTS */
+    const int *slot_first;  /* host, nslots + 1 ints: slot s holds points [slot_first[s], slot_first[s+1]) */
+    const int *slot_step;   /* host, nslots ints in [0, plan->nsteps]: slot s is observed after that many steps */
+    void *record_dev;
+    size_t member_stride;
+} fluid_obs_window;
+int fluid_observe_members_range(fluid_ctx *ctx, int field, int first, int count, void *record_dev, size_t member_stride);
+int fluid_run_window(fluid_ctx *ctx, const float *dt, const float *diff, const float *visc, const fluid_run_plan *plan, int factor,
+                     const fluid_obs_window *window, int *snapshots_written);
+int fluid_observation_gram_recorded(fluid_ctx *ctx, const void *record_dev, size_t member_stride, int centre, const float *obs,
+                                    const float *inv_sigma, double *gram, double *rhs, double *dd);
+int fluid_observation_gram_lattice_recorded(fluid_ctx *ctx, const void *record_dev, size_t member_stride, int centre, const float *obs,
+                                            const float *inv_sigma, int nodes_row, int nodes_col, int row0, int col0, int step, float c,
+                                            double *gram, double *rhs, double *dd, int *counts);
+int fluid_analyse_lattice_recorded(fluid_ctx *ctx, const void *record_dev, size_t member_stride, const float *obs, const float *inv_sigma,
+                                   int nodes_row, int nodes_col, int row0, int col0, int step, float c, float rho, const int *fields,
+                                   int nfields);
+
 int fluid_set_jacobi_variant(fluid_ctx *ctx, int variant);
 /* How FLUID_JACOBI_TB divides by `beta` in a solve with these coefficients (diagnostic; runs the on-device proof
  * if this beta has not been seen): 0 true division, 2 double-precision reciprocal, 3 two-term float reciprocal
