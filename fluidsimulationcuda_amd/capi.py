@@ -164,6 +164,13 @@ SIGNATURES = {
     "fluid_observation_gram_lattice_recorded": [_ctx, C.c_void_p, C.c_size_t, _i, _MF, _MF, _i, _i, _i, _i, _i, _f,
                                                 C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i)],
     "fluid_analyse_lattice_recorded": [_ctx, C.c_void_p, C.c_size_t, _MF, _MF, _i, _i, _i, _i, _i, _f, _f, C.POINTER(_i), _i],
+    "fluid_observation_departures": [_ctx, _i, _MF, _MF, _f, _MF, _MF, _MF, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte),
+                                     C.POINTER(C.c_double)],
+    "fluid_observation_departures_recorded": [_ctx, C.c_void_p, C.c_size_t, _MF, _MF, _f, _MF, _MF, _MF, C.POINTER(C.c_ubyte),
+                                              C.POINTER(C.c_ubyte), C.POINTER(C.c_double)],
+    "fluid_set_observation_qc": [_ctx, _f],
+    "fluid_observation_qc": [_ctx, _MF],
+    "fluid_observation_qc_result": [_ctx, C.POINTER(C.c_ubyte), C.POINTER(_i), C.POINTER(_i)],
     "fluid_set_jacobi_variant": [_ctx, _i],
     "fluid_division_mode": [_ctx, _f, _f, C.POINTER(_i)],
     "fluid_autotune_pending": [_ctx, C.POINTER(_i)],

@@ -186,6 +186,15 @@ struct Observation {
     const unsigned long long* tap() const { return reinterpret_cast<const unsigned long long*>(table + (size_t)points * 16); }
     float* obs() const { return reinterpret_cast<float*>(table + (size_t)points * 24); }
     float* sigma() const { return reinterpret_cast<float*>(table + (size_t)points * 28); }
+    // Screening observations (fluid_set_observation_qc, fluid_observation_departures).  The gate: `qc` > 0 makes the six Gram
+    // and analysis calls screen their points first; the launch writes sigma() and `flags`, one byte per point and its twin,
+    // which fluid_observation_qc_result copies back.  `qc` outlives the network, `qc_checked` does not.
+    float qc = 0.0f;                      // the resident threshold, 0: off
+    bool qc_checked = false;              // a gated call has filled `flags` for the network in place
+    Scratch flags;
+    // fluid_observation_departures: ONE buffer with a twin, copied back whole -- three sums (32 bytes), then [points] floats
+    // of mean, spread and departure, then [points] bytes of rank and flag; and the sums' per-chunk partials, three doubles each
+    Scratch screen, chunk_sums;
 };
 
 // Lattice observations (fluid_observation_gram_lattice): the point lists of the nodes, the operands of every point and the

@@ -252,6 +252,25 @@ void launch_observation_gram(hipStream_t s, int st, const void* x, int pitch, Me
                              const ObservationPoints& pts, bool centre, const float* obs, const float* sigma, double* partials, double* out,
                              const RecordedValues* recorded = nullptr);
 
+// Screening observations (include/fluid_amd.h "screening observations"): per point of the network the ensemble mean and
+// spread of h, the departure of `obs` from the mean, its rank among the members and the decision of the background check
+// at `threshold` (0: nothing is rejected), rules 2 - 5 of the header.  `obs`, `sigma`: as for launch_observation_gram; `obs`
+// null leaves only mean and spread defined.  Every pointer of ScreenOutputs is device memory and may be null: pts.count
+// entries each; `sigma`, the 1 / sigma the Gram launches behind this one read -- +0 at a rejected point, the input's float
+// (1 for a null input) elsewhere; it may be the input buffer; `sums`, three doubles over the points not rejected (count, sum
+// of d * d, sum of var / sigma^2) through `chunk_sums`, three doubles per chunk of 64 points, in a fixed order.  mb.count in
+// [2, kTransformMaxMembers].  One launch, and a second small one for `sums`.
+struct ScreenOutputs {
+    float* sigma = nullptr;
+    float *mean = nullptr, *spread = nullptr, *departure = nullptr;
+    unsigned char *rank = nullptr, *flag = nullptr;
+    double *chunk_sums = nullptr, *sums = nullptr;
+};
+inline size_t observation_screen_chunks(int points) { return ((size_t)points + 63) / 64; }
+void launch_observation_screen(hipStream_t s, int st, const void* x, int pitch, Members mb, float inv, const FieldSources* typed,
+                               const ObservationPoints& pts, const float* obs, const float* sigma, float threshold, const ScreenOutputs& out,
+                               const RecordedValues* recorded = nullptr);
+
 // Localised updates (include/fluid_amd.h "localised updates").
 // The box of a launch, half-open, in cells of the (n + 2)^2 array: rows [row_lo, row_hi), columns [col_lo, col_hi).
 struct CellBox {

@@ -2198,6 +2198,128 @@ __global__ __launch_bounds__(256) void k_observation_operands(SRC src, int pitch
     for (int v = t; v < nc * R; v += 256) rows[v] = stage[v];
 }
 
+// ---- screening observations (include/fluid_amd.h "screening observations") ------------------------------------------------
+// fluid_observation_departures and the gate of the six Gram and analysis calls: one body.  The first half of
+// k_observation_operands with the members walked at run time -- a block takes the CH = 64 points of its chunk, wave w gathers
+// and interpolates members w, w + 4, .., staged as doubles [point][member], kScreenRow = 65 doubles per point (an odd row:
+// the lanes of the second half, one per point, walk their rows on different banks).  One lane per point then runs rules 2 - 5
+// of the header, every operation rounded once: the mean chain and the chain of squared anomalies of k_ensemble_stats, the
+// departure of k_observation_gram with CENTRE, the decision, the rank.  Every output pointer may be null:
+//   mean, spread, departure [points] floats, rank, flag [points] bytes: the per-point results;
+//   sigma_out [points] floats: +0 at a rejected point, what the point came with elsewhere (sigma_in, or 1 for a null one) --
+//     the buffer the Gram launch behind this one reads; it may be sigma_in itself: a lane reads its own float, then writes it;
+//   chunk_sums [chunks][3] doubles: the count, the sum of d * d and the sum of vs over the chunk's points that are not
+//     rejected, each added in increasing point index from -0.0 (which is "from the first term": -0.0 + x has the bits of x).
+// `obs` null: nothing beyond mean and spread is defined, and the host passes none of the other outputs.
+constexpr int kScreenRow = 65;
+
+template <typename S, typename SRC>
+__global__ __launch_bounds__(256) void k_observation_screen(SRC src, int pitch, size_t ms, int members,
+                                                            const unsigned long long* __restrict__ tap, const float4* __restrict__ weight,
+                                                            const float* __restrict__ obs, const float* sigma_in, float threshold, int points,
+                                                            float* sigma_out, float* __restrict__ mean, float* __restrict__ spread,
+                                                            float* __restrict__ departure, unsigned char* __restrict__ rank,
+                                                            unsigned char* __restrict__ flag, double* __restrict__ chunk_sums)
+{
+#pragma clang fp contract(off)
+    constexpr int CH = kObsChunk, R = kScreenRow;
+    __shared__ double stage[CH * R];
+    __shared__ double term[3][CH];
+    __shared__ FieldSource sources[kObservedFields];
+    stage_sources(src, sources);
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int first = (int)blockIdx.x * CH, nc = min(CH, points - first);
+    {
+        const int pt = first + lane;
+        const bool live = pt < points;
+        if constexpr (SRC::recorded) {
+            if (live)
+                for (int k = wave; k < members; k += 4) stage[lane * R + k] = (double)src.h[(size_t)k * src.stride + (size_t)pt];
+        } else {
+            if (live) {
+                const unsigned long long o = tap[pt];
+                const float4 w = weight[pt];
+                float inv = 0.0f;
+                const S* x = source_of<S>(src, sources, ms, (unsigned)pt, &inv);
+                for (int k = wave; k < members; k += 4) stage[lane * R + k] = (double)observe_point<S>(x + (size_t)k * ms, pitch, o, w, inv);
+            }
+        }
+    }
+    __syncthreads();
+    if (t < nc) {
+        const int pt = first + t;
+        const double* p = stage + t * R;
+        double s = p[0];
+        for (int m = 1; m < members; ++m) s = s + p[m];
+        const double mu = s / (double)members;
+        double e = p[0] - mu;
+        double q = e * e;
+        for (int m = 1; m < members; ++m) {
+            e = p[m] - mu;
+            const double ee = e * e;
+            q = q + ee;
+        }
+        const double var = q / (double)(members - 1);
+        if (mean) mean[pt] = (float)mu;
+        if (spread) spread[pt] = (float)sqrt(var);
+        const float sf = sigma_in ? sigma_in[pt] : 1.0f;
+        bool rejected = false;
+        double lhs = 0.0, vs = 0.0;
+        if (obs) {
+            const double y = (double)obs[pt], sg = (double)sf;
+            const double dep = y - mu;
+            const double d = dep * sg;
+            lhs = d * d;
+            vs = var * sg;
+            vs = vs * sg;
+            const double bound = 1.0 + vs;
+            const double t2 = (double)threshold * (double)threshold;
+            const double lim = t2 * bound;
+            rejected = threshold != 0.0f && lhs > lim;
+            if (departure) departure[pt] = (float)dep;
+            if (rank) {
+                int below = 0;
+                for (int m = 0; m < members; ++m) below += p[m] < y ? 1 : 0;      // (floats widened exactly: the floats' own order)
+                rank[pt] = (unsigned char)below;
+            }
+            if (flag) flag[pt] = rejected ? 1 : 0;
+        }
+        if (sigma_out) sigma_out[pt] = rejected ? 0.0f : sf;
+        if (chunk_sums) {
+            term[0][t] = rejected ? -0.0 : 1.0;                                   // (-0.0: adding it changes no bit of any sum)
+            term[1][t] = rejected ? -0.0 : lhs;
+            term[2][t] = rejected ? -0.0 : vs;
+        }
+    }
+    if (chunk_sums) {
+        __syncthreads();
+        if (t < 3) {
+            double a = -0.0;
+            for (int i = 0; i < nc; ++i) a = a + term[t][i];
+            chunk_sums[(size_t)blockIdx.x * 3 + t] = a;
+        }
+    }
+}
+
+// the three sums of k_observation_screen's chunks, folded as k_fold_observation_gram folds partials: 16 lanes per sum, lane j
+// chains the chunks j, j + 16, .. from -0.0, then the 16 sums are added in index order.  One block of 64 lanes.
+__global__ __launch_bounds__(64) void k_fold_screen_sums(const double* __restrict__ chunk_sums, int chunks, double* __restrict__ out)
+{
+    __shared__ double part[16][4];
+    const int e = threadIdx.x & 3, j = threadIdx.x >> 2;
+    double s = -0.0;
+    if (e < 3)
+        for (int c = j; c < chunks; c += 16) s = s + chunk_sums[(size_t)c * 3 + e];
+    part[j][e] = s;
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        s = part[0][threadIdx.x];
+#pragma unroll
+        for (int p = 1; p < 16; ++p) s = s + part[p][threadIdx.x];
+        out[threadIdx.x] = s;
+    }
+}
+
 // fluid_observation_gram_lattice, second launch: the second half of k_observation_gram, one block per node, the node index
 // in the grid.  start[node] .. start[node + 1] are the node's entries {point index, bits of the float weight w}, in
 // increasing point index, built and bounds-checked on the host; a block walks them in chunks of CH = 64: the entries go to
@@ -3539,6 +3661,18 @@ void launch_observation_gram_lattice(hipStream_t s, int st, const void* x, int p
     }
 #undef FLUID_LATTICE_GRAM_CASE
 #undef FLUID_OBS_OPERANDS_LAUNCH
+}
+
+void launch_observation_screen(hipStream_t s, int st, const void* x, int pitch, Members mb, float inv, const FieldSources* typed,
+                               const ObservationPoints& pts, const float* obs, const float* sigma, float threshold, const ScreenOutputs& out,
+                               const RecordedValues* recorded)
+{
+    const unsigned chunks = cdiv((unsigned)pts.count, kObsChunk);
+    FLUID_BY_OBSERVED(st, typed, recorded,
+                      hipLaunchKernelGGL((k_observation_screen<S, SRC>), dim3(chunks), dim3(256), 0, s, src, pitch, mb.stride, mb.count, pts.tap,
+                                         (const float4*)pts.weight, obs, sigma, threshold, pts.count, out.sigma, out.mean, out.spread,
+                                         out.departure, out.rank, out.flag, out.sums ? out.chunk_sums : nullptr));
+    if (out.sums) hipLaunchKernelGGL(k_fold_screen_sums, dim3(1), dim3(64), 0, s, out.chunk_sums, (int)chunks, out.sums);
 }
 
 void launch_ensemble_stats(hipStream_t s, int st, const void* x, int pitch, int n, Members mb, float* mean, float* var)

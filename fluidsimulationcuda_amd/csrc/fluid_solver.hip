@@ -3323,6 +3323,7 @@ static int set_network(fluid_ctx* c, const char* call, const float* col, const f
     o.typed = typed;
     o.mask = mask;
     o.fields.swap(ids);
+    o.qc_checked = false;                                               // (the threshold stays: fluid_set_observation_qc)
     LatticeGram& g = c->lgram;                                          // the positions fluid_observation_gram_lattice builds its lists from
     g.valid = false;
     g.coords.resize((size_t)npoints * 2);
@@ -3527,6 +3528,36 @@ int fluid_observe_members_host(fluid_ctx* c, int field, float* host)
     return FLUID_OK;
 }
 
+// ---- screening observations: the gate of the Gram and analysis calls (include/fluid_amd.h "screening observations") -------
+// With a resident threshold above 0 a call that has `obs` screens the h it is about to use: one launch behind the uploads
+// and the settling, in front of the Gram launch, no wait.  It leaves the flags in Observation::flags and 1 / sigma -- +0 at
+// the rejected points, the caller's float or 1 elsewhere -- in Observation::sigma(), which the Gram launch then reads
+// whether the caller gave an inv_sigma or not.  gate_reserve: with the call's other buffers, before anything is enqueued.
+static bool gated(const fluid_ctx* c, const float* obs) { return c->observe.qc > 0.0f && obs; }
+
+static int gate_reserve(fluid_ctx* c, const char* call, const float* obs)
+{
+    if (!gated(c, obs)) return FLUID_OK;
+    return reserve(c, c->observe.flags, (size_t)c->observe.points, true, call, "screening flags");
+}
+
+// *sigma: the device buffer the Gram launch reads, null for none -- as the call had it without the gate
+static int gate_launch(fluid_ctx* c, const ObservedFrom& from, const float* obs, const float* inv_sigma, const float** sigma)
+{
+    Observation& o = c->observe;
+    *sigma = inv_sigma ? o.sigma() : nullptr;
+    if (!gated(c, obs)) return FLUID_OK;
+    fluid::ScreenOutputs out;
+    out.sigma = o.sigma();
+    out.flag = o.flags.d<unsigned char>();
+    fluid::launch_observation_screen(c->stream, c->st, from.x, c->pitch, c->mb(), from.inv, from.sources(), observation_points(c), o.obs(), *sigma,
+                                     o.qc, out, from.recorded());
+    HIP_TRY(hipGetLastError());
+    o.qc_checked = true;
+    *sigma = o.sigma();
+    return FLUID_OK;
+}
+
 // fluid_observation_gram / fluid_observation_gram_recorded: one body, under the caller's name
 static int observation_gram_body(fluid_ctx* c, const char* call, GramSource src, int centre, const float* obs, const float* inv_sigma,
                                  double* gram, double* rhs, double* dd)
@@ -3550,13 +3581,15 @@ static int observation_gram_body(fluid_ctx* c, const char* call, GramSource src,
     // partials for the blocks of this network (a larger network later: they grow), the folded result and its twin
     TRY(reserve(c, o.partials, entries * (size_t)fluid::observation_gram_blocks(o.points, M), false, call, "partial results"));
     TRY(reserve(c, o.result, entries, true, call, "the result"));
+    TRY(gate_reserve(c, call, obs));
     if (obs) HIP_TRY(hipMemcpyAsync(o.obs(), obs, P * sizeof(float), hipMemcpyHostToDevice, c->stream));
     if (inv_sigma) HIP_TRY(hipMemcpyAsync(o.sigma(), inv_sigma, P * sizeof(float), hipMemcpyHostToDevice, c->stream));
     ObservedFrom from;
     TRY(settle_for_observing(c, src, &from));
+    const float* sigma = nullptr;
+    TRY(gate_launch(c, from, obs, inv_sigma, &sigma));
     fluid::launch_observation_gram(c->stream, c->st, from.x, c->pitch, c->mb(), from.inv, from.sources(), observation_points(c), centre != 0,
-                                   obs ? o.obs() : nullptr, inv_sigma ? o.sigma() : nullptr, o.partials.d<double>(), o.result.d<double>(),
-                                   from.recorded());
+                                   obs ? o.obs() : nullptr, sigma, o.partials.d<double>(), o.result.d<double>(), from.recorded());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(o.result.host, o.result.dev, entries, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -3580,6 +3613,126 @@ int fluid_observation_gram_recorded(fluid_ctx* c, const void* record_dev, size_t
     const char* call = "fluid_observation_gram_recorded";
     if (!record_dev) return fail(FLUID_E_INVALID, "%s: null device pointer `record_dev`", call);
     return observation_gram_body(c, call, {record_dev, member_stride}, centre, obs, inv_sigma, gram, rhs, dd);
+}
+
+// ---- screening observations: fluid_observation_departures, the resident gate and its result --------------------------------
+static int check_threshold(const char* call, float threshold)
+{
+    if (!std::isfinite(threshold) || threshold < 0.0f)
+        return fail(FLUID_E_INVALID, "%s: threshold = %g is not finite or is negative", call, (double)threshold);
+    return FLUID_OK;
+}
+
+// fluid_observation_departures / fluid_observation_departures_recorded: one body, under the caller's name.  The launch of
+// the gate with every output asked for; the results come back through Observation::screen in one copy.
+static int departures_body(fluid_ctx* c, const char* call, GramSource src, const float* obs, const float* inv_sigma, float threshold, float* mean,
+                           float* spread, float* departure, unsigned char* rank, unsigned char* flag, double* sums)
+{
+    if (!obs && (departure || rank || flag || sums))
+        return fail(FLUID_E_INVALID, "%s: `%s` is given but `obs` is null", call, departure ? "departure" : rank ? "rank" : flag ? "flag" : "sums");
+    TRY(check_threshold(call, threshold));
+    if (!obs && threshold != 0.0f) return fail(FLUID_E_INVALID, "%s: threshold = %g needs `obs`, which is null", call, (double)threshold);
+    if (!c) return fail(FLUID_E_INVALID, "%s: null context", call);
+    if (!src.record && src.field != FLUID_FIELD_OF_POINT && !c->valid_field(src.field))
+        return fail(FLUID_E_INVALID, "%s: bad field id %d", call, src.field);
+    TRY(refuse_slabs(c, call));                                          // (a slab context has one member: say what it is first)
+    if (c->members < 2 || c->members > FLUID_TRANSFORM_MAX_MEMBERS)
+        return fail(FLUID_E_INVALID, "%s: this context has %d members, outside [2, FLUID_TRANSFORM_MAX_MEMBERS = %d]", call, c->members,
+                    FLUID_TRANSFORM_MAX_MEMBERS);
+    TRY(check_gram_source(c, call, &src));
+    Observation& o = c->observe;
+    const size_t P = (size_t)o.points;
+    if (inv_sigma)
+        for (size_t p = 0; p < P; ++p)
+            if (!std::isfinite(inv_sigma[p])) return fail(FLUID_E_INVALID, "%s: inv_sigma[%zu] (point %zu) is not finite", call, p, p);
+    constexpr size_t kSums = 32;                                         // three doubles, the floats behind them 16-byte aligned
+    const size_t bytes = kSums + P * (3 * sizeof(float) + 2);
+    TRY(reserve(c, o.screen, bytes, true, call, "the results"));
+    if (sums) TRY(reserve(c, o.chunk_sums, fluid::observation_screen_chunks(o.points) * 3 * sizeof(double), false, call, "partial sums"));
+    if (obs) HIP_TRY(hipMemcpyAsync(o.obs(), obs, P * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (inv_sigma) HIP_TRY(hipMemcpyAsync(o.sigma(), inv_sigma, P * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    ObservedFrom from;
+    TRY(settle_for_observing(c, src, &from));
+    fluid::ScreenOutputs out;
+    out.mean = o.screen.d<float>(kSums);
+    out.spread = out.mean + P;
+    if (obs) {
+        out.departure = out.spread + P;
+        out.rank = o.screen.d<unsigned char>(kSums + P * 3 * sizeof(float));
+        out.flag = out.rank + P;
+    }
+    if (sums) {
+        out.chunk_sums = o.chunk_sums.d<double>();
+        out.sums = o.screen.d<double>();
+    }
+    fluid::launch_observation_screen(c->stream, c->st, from.x, c->pitch, c->mb(), from.inv, from.sources(), observation_points(c),
+                                     obs ? o.obs() : nullptr, inv_sigma ? o.sigma() : nullptr, threshold, out, from.recorded());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(o.screen.host, o.screen.dev, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->etkf.in_flight = false;
+    const float* hf = o.screen.h<float>(kSums);
+    const unsigned char* hb = o.screen.h<unsigned char>(kSums + P * 3 * sizeof(float));
+    if (mean) std::memcpy(mean, hf, P * sizeof(float));
+    if (spread) std::memcpy(spread, hf + P, P * sizeof(float));
+    if (departure) std::memcpy(departure, hf + 2 * P, P * sizeof(float));
+    if (rank) std::memcpy(rank, hb, P);
+    if (flag) std::memcpy(flag, hb + P, P);
+    if (sums) std::memcpy(sums, o.screen.host, 3 * sizeof(double));
+    return FLUID_OK;
+}
+
+int fluid_observation_departures(fluid_ctx* c, int field, const float* obs, const float* inv_sigma, float threshold, float* mean, float* spread,
+                                 float* departure, unsigned char* rank, unsigned char* flag, double* sums)
+{
+    return departures_body(c, "fluid_observation_departures", GramSource(field), obs, inv_sigma, threshold, mean, spread, departure, rank, flag, sums);
+}
+
+int fluid_observation_departures_recorded(fluid_ctx* c, const void* record_dev, size_t member_stride, const float* obs, const float* inv_sigma,
+                                          float threshold, float* mean, float* spread, float* departure, unsigned char* rank,
+                                          unsigned char* flag, double* sums)
+{
+    const char* call = "fluid_observation_departures_recorded";
+    if (!record_dev) return fail(FLUID_E_INVALID, "%s: null device pointer `record_dev`", call);
+    return departures_body(c, call, {record_dev, member_stride}, obs, inv_sigma, threshold, mean, spread, departure, rank, flag, sums);
+}
+
+int fluid_set_observation_qc(fluid_ctx* c, float threshold)
+{
+    const char* call = "fluid_set_observation_qc";
+    TRY(check_threshold(call, threshold));
+    if (!c) return fail(FLUID_E_INVALID, "%s: null context", call);
+    TRY(refuse_slabs(c, call));
+    if (c->members < 2) return fail(FLUID_E_INVALID, "%s: this context has %d members, below 2", call, c->members);
+    c->observe.qc = threshold;
+    return FLUID_OK;
+}
+
+int fluid_observation_qc(fluid_ctx* c, float* threshold)
+{
+    if (!threshold) return fail(FLUID_E_INVALID, "fluid_observation_qc: null pointer `threshold`");
+    if (!c) return fail(FLUID_E_INVALID, "fluid_observation_qc: null context");
+    *threshold = c->observe.qc;
+    return FLUID_OK;
+}
+
+int fluid_observation_qc_result(fluid_ctx* c, unsigned char* flags, int* checked, int* rejected)
+{
+    const char* call = "fluid_observation_qc_result";
+    if (!c) return fail(FLUID_E_INVALID, "%s: null context", call);
+    Observation& o = c->observe;
+    if (!o.qc_checked) return fail(FLUID_E_INVALID, "%s: no gated call has run on this network (fluid_set_observation_qc)", call);
+    const size_t P = (size_t)o.points;
+    HIP_TRY(hipMemcpyAsync(o.flags.host, o.flags.dev, P, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->etkf.in_flight = false;
+    const unsigned char* h = o.flags.h<unsigned char>();
+    int n = 0;
+    for (size_t p = 0; p < P; ++p) n += h[p] != 0;
+    if (flags) std::memcpy(flags, h, P);
+    if (checked) *checked = (int)P;
+    if (rejected) *rejected = n;
+    return FLUID_OK;
 }
 
 // ---- lattice observations: fluid_observation_gram_lattice ------------------------------------------------------------------
@@ -3669,6 +3822,7 @@ static int enqueue_lattice_gram(fluid_ctx* c, const char* call, GramSource src, 
     if (grew) g.valid = false;                                           // (not cached, then) the old lists went with the old buffer
     TRY(reserve(c, g.operands, P * (size_t)(mp + 2) * sizeof(double), false, call, "point operands"));
     TRY(reserve(c, g.out, B * E * sizeof(double), true, call, "node results"));
+    TRY(gate_reserve(c, call, obs));
     int* h_start = g.lists.h<int>();
     int2* h_entry = g.lists.h<int2>(start_bytes);
     if (!cached) {
@@ -3694,10 +3848,11 @@ static int enqueue_lattice_gram(fluid_ctx* c, const char* call, GramSource src, 
     if (inv_sigma) HIP_TRY(hipMemcpyAsync(o.sigma(), inv_sigma, P * sizeof(float), hipMemcpyHostToDevice, c->stream));
     ObservedFrom from;
     TRY(settle_for_observing(c, src, &from));
+    const float* sigma = nullptr;
+    TRY(gate_launch(c, from, obs, inv_sigma, &sigma));
     const fluid::LatticeLists lists = {g.lists.d<int>(), g.lists.d<int2>(start_bytes), (int)B};
     fluid::launch_observation_gram_lattice(c->stream, c->st, from.x, c->pitch, c->mb(), from.inv, from.sources(), observation_points(c), centre != 0,
-                                           obs ? o.obs() : nullptr, inv_sigma ? o.sigma() : nullptr, g.operands.d<double>(), lists,
-                                           g.out.d<double>(), from.recorded());
+                                           obs ? o.obs() : nullptr, sigma, g.operands.d<double>(), lists, g.out.d<double>(), from.recorded());
     HIP_TRY(hipGetLastError());
     return FLUID_OK;
 }

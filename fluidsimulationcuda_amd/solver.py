@@ -846,6 +846,55 @@ class FluidSolver:
         if wait:
             self.synchronize()
 
+    # -- screening observations: departures, ranks and the background check, on the device
+    def set_observation_qc(self, threshold):
+        """The resident background check: while threshold > 0, observation_gram, observation_gram_lattice, analyse_lattice
+        and their _recorded namesakes, given `obs`, first reject every point with d^2 > threshold^2 (1 + var / sigma^2) --
+        d the normalised departure from the ensemble mean, var the ensemble variance of h -- and proceed as with inv_sigma 0
+        there; one more launch, no wait.  0 (the default) is off; the value outlives the network (include/fluid_amd.h,
+        "screening observations")."""
+        capi.check(capi.lib().fluid_set_observation_qc(self._h, float(threshold)))
+
+    def observation_qc(self):
+        """The resident threshold; 0: the gate is off."""
+        t = C.c_float()
+        capi.check(capi.lib().fluid_observation_qc(self._h, C.byref(t)))
+        return t.value
+
+    def observation_qc_result(self):
+        """Waits for the stream; (flags, checked, rejected) of the last gated call: a uint8 array with 1 at the rejected
+        points, the number of points and the number of flags set."""
+        flags = np.empty(self.observation_points(), np.uint8)
+        checked, rejected = C.c_int(), C.c_int()
+        capi.check(capi.lib().fluid_observation_qc_result(self._h, flags.ctypes.data_as(C.POINTER(C.c_ubyte)), C.byref(checked),
+                                                          C.byref(rejected)))
+        return flags, checked.value, rejected.value
+
+    def observation_departures(self, field=None, record=None, obs=None, inv_sigma=None, threshold=0.0, member_stride=0):
+        """What observation-space verification needs, per point of the network, in at most two launches and one wait: a
+        dict with "mean" and "spread" (float32: the ensemble mean and sample standard deviation of h) and, with `obs`,
+        "departure" (float32, y - mean), "rank" (uint8: the members below y, 0 .. M), "flag" (uint8: 1 where the background
+        check at `threshold` rejects the point; 0 rejects nothing) and "sums" (float64[3] over the points not rejected:
+        their count, the sum of d^2, the sum of var / sigma^2 -- (sums[1] - sums[0]) / sums[2] estimates the inflation the
+        ensemble lacks).  `record`: a record to read h from (record[k * member_stride + p]) instead of sampling `field`.
+        The resident gate is not touched (include/fluid_amd.h, "screening observations")."""
+        y, s = self._per_point(obs, "obs"), self._per_point(inv_sigma, "inv_sigma")
+        points = self.observation_points()
+        bp, dp = C.POINTER(C.c_ubyte), C.POINTER(C.c_double)
+        out = {"mean": np.empty(points, np.float32), "spread": np.empty(points, np.float32)}
+        if y is not None:
+            out.update(departure=np.empty(points, np.float32), rank=np.empty(points, np.uint8), flag=np.empty(points, np.uint8),
+                       sums=np.empty(3, np.float64))
+        tail = [None if y is None else _mf(y), None if s is None else _mf(s), float(threshold), _mf(out["mean"]), _mf(out["spread"]),
+                None if y is None else _mf(out["departure"]), None if y is None else out["rank"].ctypes.data_as(bp),
+                None if y is None else out["flag"].ctypes.data_as(bp), None if y is None else out["sums"].ctypes.data_as(dp)]
+        if record is None:
+            capi.check(capi.lib().fluid_observation_departures(self._h, _ofid(field), *tail))
+        else:
+            self._handover(True)
+            capi.check(capi.lib().fluid_observation_departures_recorded(self._h, device_address(record), int(member_stride), *tail))
+        return out
+
     def set_jacobi_variant(self, variant):
         capi.check(capi.lib().fluid_set_jacobi_variant(self._h, variant))
 

@@ -1041,6 +1041,67 @@ int fluid_analyse_lattice_recorded(fluid_ctx *ctx, const void *record_dev, size_
                                    int nodes_row, int nodes_col, int row0, int col0, int step, float c, float rho, const int *fields,
                                    int nfields);
 
+/* ---- screening observations: departures, ranks and a background check, on the device ---------------------------------------
+ * M = fluid_members(ctx), 2 <= M <= FLUID_TRANSFORM_MAX_MEMBERS; P = the points of the resident network.  Between "H x is
+ * known" and "the weights are formed" every operational filter checks its observations against the background: a report
+ * whose departure from the ensemble mean is many times what the spread and its own error explain is dropped, or it wrecks
+ * every node within 2c of it.  The six Gram and analysis calls read 1 / sigma from a device buffer, and a point with
+ * inv_sigma 0 takes no part; a check that runs on the device and writes that buffer needs no host algebra and no wait.
+ *
+ * Definitions, per point p, shared by everything below.  All arithmetic is IEEE double, every operation rounded once, none
+ * contracted.
+ *    1. h_k[p]: rule 1 of fluid_observation_gram, or record[k * member_stride + p] for the _recorded calls: the same
+ *       observation, the same settling, the same fp16 scale per field, FLUID_FIELD_OF_POINT on a typed network.
+ *    2. s = (double)h_0, then s += (double)h_m for m = 1 .. M-1;  mean_d = s / (double)M;  e_m = (double)h_m - mean_d;
+ *       q = e_0 * e_0, then q += e_m * e_m in member order, each product rounded and then added;  var = q / (double)(M - 1).
+ *       These are the chains of fluid_ensemble_stats and fluid_member_spread.
+ *    3. sg = (double)inv_sigma[p], 1.0 for a null inv_sigma;  dep = (double)y_p - mean_d;  d = dep * sg -- bit for bit the
+ *       d[p] of fluid_observation_gram with centre != 0.
+ *    4. lhs = d * d;  vs = var * sg, then vs = vs * sg;  bound = 1.0 + vs;  t2 = (double)threshold * (double)threshold;
+ *       lim = t2 * bound;  the point is REJECTED when threshold != 0 and lhs > lim.  A comparison with a NaN is false: a NaN
+ *       h, y or sigma rejects nothing, and the poisoning rules of the Gram calls hold unchanged.  The gate is NO guard
+ *       against non-finite values: a rejected y = inf still gives inf * 0 = NaN in the Gram call.  A point that arrives
+ *       with inv_sigma 0 has d = 0 and is never rejected.
+ *    5. rank[p] = the number of k with h_k[p] < y_p, compared as floats: 0 .. M, the bin of the Talagrand histogram.  A NaN
+ *       on either side counts as "not below".
+ *
+ * - fluid_observation_departures / fluid_observation_departures_recorded: synchronous like fluid_observation_gram.  Host
+ *   outputs of P entries each, any of them null: mean[p] = (float)mean_d, spread[p] = (float)sqrt(var), departure[p] =
+ *   (float)dep, rank[p], flag[p] (1: rejected).  `obs` may be null: then departure, rank, flag and sums must be null and
+ *   threshold 0.  sums[3], over the points that are NOT rejected: their count as a double, the sum of d * d, the sum of vs.
+ *   A caller estimates the multiplicative inflation its ensemble lacks from them, E[d * d] = 1 + v: (sums[1] - sums[0]) /
+ *   sums[2].  Order of each sum: within a chunk of 64 consecutive points in increasing point index, from the first term
+ *   (-0.0 for a chunk without one); lane j of 16 then chains the chunks j, j + 16, .. from -0.0 and the 16 are added in index
+ *   order, as fluid_observation_gram folds its partials.  No atomics: the same bits call after call, and the exact sum when
+ *   every partial sum is representable.  At most two launches whatever P and M, one copy back, one wait; the results pass
+ *   through library-owned scratch outside the arena.  The resident gate below and its last result are not touched.
+ * - fluid_set_observation_qc / fluid_observation_qc: the resident gate, a threshold kept in the context; 0, the default, is
+ *   off, any finite value >= 0 is accepted, and it survives fluid_set_observation_points / _network.  While it is above 0,
+ *   fluid_observation_gram, fluid_observation_gram_lattice, fluid_analyse_lattice and their _recorded namesakes, whenever
+ *   their `obs` is non-null, first run rule 4 on the h they are about to use -- with the mean of rule 2 whatever the call's
+ *   own `centre` -- and then proceed BIT FOR BIT as the same call with the gate off and inv_sigma[p] replaced by +0.0f at
+ *   the rejected points, a null inv_sigma counting as all ones.  One more launch on the context's stream and no wait; the
+ *   lists, their cache, the counts, the solve and the status words are as before.  A node whose points are all rejected
+ *   has a zero Gram, not an empty list: its status is "solved" and D = 0 at rho = 1.  A call with `obs` null checks
+ *   nothing and leaves the last result in place.  With the gate off no call changes its bits or its launches.
+ * - fluid_observation_qc_result: waits for the stream; flags[p] of the last gated call (P bytes), *checked = P, *rejected =
+ *   the number of flags set; any pointer may be null.
+ * Refusals, all FLUID_E_INVALID with a message that names the call, found before anything is launched or any state changes,
+ * null pointers before the context is looked at: whatever fluid_observation_gram[_recorded] refuses, under the new names;
+ * M < 2 or M > FLUID_TRANSFORM_MAX_MEMBERS (the message gives both numbers); a threshold that is not finite or is
+ * negative; departure, rank, flag or sums given with obs null; a non-zero threshold with obs null; a null `threshold`
+ * pointer; fluid_set_observation_qc on a one-member context or on row slabs; fluid_observation_qc_result before the first
+ * gated call, and again after the network is replaced.
+ * The launches belong to none of the fluid_timing categories. */
+int fluid_observation_departures(fluid_ctx *ctx, int field, const float *obs, const float *inv_sigma, float threshold, float *mean,
+                                 float *spread, float *departure, unsigned char *rank, unsigned char *flag, double *sums);
+int fluid_observation_departures_recorded(fluid_ctx *ctx, const void *record_dev, size_t member_stride, const float *obs,
+                                          const float *inv_sigma, float threshold, float *mean, float *spread, float *departure,
+                                          unsigned char *rank, unsigned char *flag, double *sums);
+int fluid_set_observation_qc(fluid_ctx *ctx, float threshold);
+int fluid_observation_qc(fluid_ctx *ctx, float *threshold);
+int fluid_observation_qc_result(fluid_ctx *ctx, unsigned char *flags, int *checked, int *rejected);
+
 int fluid_set_jacobi_variant(fluid_ctx *ctx, int variant);
 /* How FLUID_JACOBI_TB divides by `beta` in a solve with these coefficients (diagnostic; runs the on-device proof
  * if this beta has not been seen): 0 true division, 2 double-precision reciprocal, 3 two-term float reciprocal
