@@ -171,6 +171,7 @@ SIGNATURES = {
     "fluid_set_observation_qc": [_ctx, _f],
     "fluid_observation_qc": [_ctx, _MF],
     "fluid_observation_qc_result": [_ctx, C.POINTER(C.c_ubyte), C.POINTER(_i), C.POINTER(_i)],
+    "fluid_verify_members": [_ctx, C.POINTER(_i), _i, C.c_void_p, C.c_size_t, C.POINTER(_i), _i, C.c_void_p, C.c_void_p],
     "fluid_set_jacobi_variant": [_ctx, _i],
     "fluid_division_mode": [_ctx, _f, _f, C.POINTER(_i)],
     "fluid_autotune_pending": [_ctx, C.POINTER(_i)],
@@ -207,6 +208,9 @@ NOISE_SET, NOISE_ADD = 0, 1
 NOISE_DENSE_TAG = 15                 # the counter tag of fluid_noise_dense: no field id
 NOISE_IDS = 65536                    # member ids and stream ids lie below it
 WINDOW_MAX_SLOTS = 65536             # FLUID_WINDOW_MAX_SLOTS: slots of one fluid_run_window
+VERIFY_SUMS = 5                      # FLUID_VERIFY_SUMS: count, then the sums of e, se, var and crps
+VERIFY_ROW = VERIFY_SUMS + TRANSFORM_MAX_MEMBERS + 1      # FLUID_VERIFY_ROW: doubles per field of a score row
+VERIFY_FAIR = 1                      # FLUID_VERIFY_FAIR
 
 _lib = None
 

@@ -136,6 +136,13 @@ struct EnsembleReduce {
     Scratch gram;                         // the folded MP x MP matrix, and its twin
 };
 
+// Verifying ensembles (fluid_verify_members): the per-block partial sums and rank counts of the scoring launch, folded by the
+// launch behind it.  One buffer, reused field after field and call after call in stream order; sized by the call's box
+// (fluid_verify.h: verify_partial_bytes), so a larger box grows it.
+struct EnsembleVerify {
+    Scratch partials;
+};
+
 // The bulk host copies (fluid_download_members / fluid_upload_members) go through a dense float staging buffer on the
 // device.  It holds `members` whole members; a call moves its members group by group in stream order.
 struct MemberStage {
@@ -257,6 +264,7 @@ struct fluid_ctx {
     float* d_partials = nullptr;          // slabs: per-block maxima of the gradient subtraction (launch_subtract_gradient)
     ConstRing consts;                     // tables of per-member constants (fluid_*_members)
     EnsembleReduce red;                   // results and scratch of the ensemble diagnostics
+    EnsembleVerify verify;                // per-block partials of fluid_verify_members
     MemberStage stage;                    // device staging of the bulk host copies
     TransformTables xform;                // weight tables of fluid_transform_members / fluid_select_members
     LatticeNodeTables lattice;            // node tables of fluid_transform_members_lattice

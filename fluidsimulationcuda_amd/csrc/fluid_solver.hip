@@ -20,6 +20,7 @@
 #include "fluid_ctx.h"
 #include "fluid_etkf.h"
 #include "fluid_noise.h"
+#include "fluid_verify.h"
 
 namespace fluid_detail {
 
@@ -3112,6 +3113,60 @@ int fluid_relax_spread(fluid_ctx* c, const int* fields, int nfields, const void*
         HIP_TRY(hipGetLastError());
         wrote(c, f, kEverywhere);                                    // nothing owed ...
         c->field[f].fscale = scale;                                  // ... and the scale it had: the launch stored at it
+    }
+    return FLUID_OK;
+}
+
+// ---- verifying ensembles: fluid_verify_members ------------------------------------------------------------------------------
+// (include/fluid_amd.h "verifying ensembles".)  The list and `truth_dev` are checked as a spread's are, then the member cap,
+// the box as fluid_transform_members_local takes one, the flags and the other two device extents.  Every listed field is
+// settled as pack_range settles it, a scale KEPT: scoring alters nothing.  At most two launches per field, no wait; the
+// launches belong to none of the timing categories.
+static_assert(FLUID_VERIFY_SUMS == fluid::kVerifySums && FLUID_VERIFY_ROW == fluid::kVerifyRow, "the header's row is the kernels' row");
+static_assert((unsigned long long)(kMaxN + 2) * (kMaxN + 2) <= 0xffffffffull, "the cells of the largest box are counted in an unsigned");
+
+int fluid_verify_members(fluid_ctx* c, const int* fields, int nfields, const void* truth_dev, size_t field_stride, const int* box, int flags,
+                         void* crps_dev, void* scores_dev)
+{
+    const char* call = "fluid_verify_members";
+    if (!fields) return fail(FLUID_E_INVALID, "%s: null array `fields`", call);
+    if (!truth_dev) return fail(FLUID_E_INVALID, "%s: null device pointer `truth_dev`", call);
+    if (!scores_dev) return fail(FLUID_E_INVALID, "%s: null device pointer `scores_dev`", call);
+    if (!c) return fail(FLUID_E_INVALID, "%s: null context", call);
+    TRY(check_spread(c, call, fields, nfields, "truth_dev", truth_dev, &field_stride));
+    if (c->members > FLUID_TRANSFORM_MAX_MEMBERS)
+        return fail(FLUID_E_INVALID, "%s: this context has %d members, above FLUID_TRANSFORM_MAX_MEMBERS = %d", call, c->members,
+                    FLUID_TRANSFORM_MAX_MEMBERS);
+    fluid::CellBox b = {1, c->n + 1, 1, c->n + 1};
+    if (box) {
+        for (int e = 0; e < 4; ++e)
+            if (box[e] < 0 || box[e] > c->w)
+                return fail(FLUID_E_INVALID, "%s: box[%d] = %d (%s) outside [0, %d]", call, e, box[e], kBoxEntry[e], c->w);
+        for (int e = 0; e < 4; e += 2)
+            if (box[e] > box[e + 1])
+                return fail(FLUID_E_INVALID, "%s: box[%d] = %d (%s) is above box[%d] = %d (%s)", call, e, box[e], kBoxEntry[e], e + 1, box[e + 1],
+                            kBoxEntry[e + 1]);
+        b = {box[0], box[1], box[2], box[3]};
+    }
+    if (flags & ~FLUID_VERIFY_FAIR) return fail(FLUID_E_INVALID, "%s: unknown flag bits 0x%x (FLUID_VERIFY_FAIR is the only flag)", call, (unsigned)flags);
+    if (((uintptr_t)scores_dev & 7u) != 0) return fail(FLUID_E_INVALID, "%s: `scores_dev` (%p) is not aligned to 8 bytes", call, scores_dev);
+    TRY(check_device_span(c, call, "scores_dev", scores_dev, (size_t)nfields * FLUID_VERIFY_ROW * sizeof(double)));
+    if (crps_dev) {
+        size_t bytes = 0;
+        (void)dense_span(member_cells(c), nfields, field_stride, &bytes);      // (check_spread has found it representable)
+        TRY(check_device_span(c, call, "crps_dev", crps_dev, bytes));
+    }
+    const int blocks = fluid::verify_blocks(b);
+    if (blocks > 0) TRY(reserve(c, c->verify.partials, fluid::verify_partial_bytes(blocks), false, call, "partial scores"));
+    for (int k = 0; k < nfields; ++k) {
+        const int f = fields[k];
+        const float inv = c->st != fluid::STORAGE_F32 ? 1.0f / c->field[f].fscale : 1.0f;      // as pack_range sees the field
+        TRY(materialize(c, f, /*keep_scale=*/inv != 1.0f));
+        fluid::launch_verify_members(c->stream, c->st, c->ptr(f), c->pitch, c->n, c->mb(), inv,
+                                     static_cast<const float*>(truth_dev) + (size_t)k * field_stride, b, (flags & FLUID_VERIFY_FAIR) != 0,
+                                     crps_dev ? static_cast<float*>(crps_dev) + (size_t)k * field_stride : nullptr, c->verify.partials.dev,
+                                     static_cast<double*>(scores_dev) + (size_t)k * FLUID_VERIFY_ROW);
+        HIP_TRY(hipGetLastError());
     }
     return FLUID_OK;
 }

@@ -686,6 +686,56 @@ class FluidSolver:
         if wait:
             self.synchronize()
 
+    # -- verifying ensembles: CRPS, RMSE against spread and the rank histogram against a truth field
+    def verify(self, truth, fields=("dens",), box=None, fair=False, crps_map=None, out=None, wait=True):
+        """Scores the ensemble against `truth`, per listed field over the cells of `box`, in at most two launches per field:
+        one row of capi.VERIFY_ROW float64 per field -- the cell count, the sums of e = mean - truth, e * e, the sample
+        variance and the CRPS, then the rank histogram (members + 1 bins) -- which verify_scores turns into numbers.
+        `truth`: an (nfields, N+2, N+2) float32 device tensor, contiguous; for a twin experiment truth_ctx.pack("dens").
+        `box`: (row_lo, row_hi, col_lo, col_hi), half-open, None for the interior.  `fair`: the CRPS's pair term over
+        M (M - 1).  `crps_map`: a tensor like `truth` that receives the per-cell CRPS inside the box, None for no map.
+        `out`: an (nfields, capi.VERIFY_ROW) float64 device tensor, contiguous -- a row-slice of a larger one will do --, None
+        allocates it.  Returns `out`; `wait`: as for pack.  2 <= members <= capi.TRANSFORM_MAX_MEMBERS (include/fluid_amd.h,
+        "verifying ensembles")."""
+        import torch
+        ids = [_fid(f) for f in ((fields,) if isinstance(fields, (str, int)) else fields)]
+        address = self._spread_tensor(truth, len(ids), "truth")
+        map_address = None if crps_map is None else self._spread_tensor(crps_map, len(ids), "crps_map")
+        if out is None:
+            out = torch.empty((len(ids), capi.VERIFY_ROW), dtype=torch.float64, device="cuda")
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or not out.is_cuda:
+            raise ValueError("out must be a float64 tensor on the device")
+        if tuple(out.shape) != (len(ids), capi.VERIFY_ROW) or not out.is_contiguous():
+            raise ValueError("out must be contiguous with shape (%d, %d), got %s" % (len(ids), capi.VERIFY_ROW, tuple(out.shape)))
+        if box is not None:
+            b = [int(v) for v in box]
+            if len(b) != 4:
+                raise ValueError("box must be (row_lo, row_hi, col_lo, col_hi), got %d values" % len(b))
+            box = (C.c_int * 4)(*b)
+        self._handover(wait)
+        capi.check(capi.lib().fluid_verify_members(self._h, (C.c_int * len(ids))(*ids), len(ids), address, 0, box,
+                                                   capi.VERIFY_FAIR if fair else 0, map_address, int(out.data_ptr())))
+        if wait:
+            self.synchronize()
+        return out
+
+    def verify_scores(self, out):
+        """What verify left in `out`, after a wait for the context's stream: one dict per field (for a tensor of more
+        dimensions, nested lists of them) with `count`, `bias`, `rmse`, `spread`, `crps` and `rank_hist` (int64, members + 1
+        entries).  An empty box gives NaN scores."""
+        self.synchronize()
+        rows = out.cpu().numpy() if hasattr(out, "cpu") else np.asarray(out)
+        if rows.ndim > 2:
+            return [self.verify_scores(r) for r in rows]
+        s = capi.VERIFY_SUMS
+        res = []
+        with np.errstate(divide="ignore", invalid="ignore"):
+            for r in np.atleast_2d(rows):
+                n = r[0]
+                res.append({"count": int(n), "bias": float(r[1] / n), "rmse": float(np.sqrt(r[2] / n)), "spread": float(np.sqrt(r[3] / n)),
+                            "crps": float(r[4] / n), "rank_hist": r[s:s + self.members + 1].astype(np.int64)})
+        return res
+
     # -- ensemble noise: reproducible randomness on the device, the same bits for every members, launch shape and process
     def _amplitudes(self, amplitude):
         a = np.asarray(amplitude, dtype=np.float32)

@@ -1102,6 +1102,67 @@ int fluid_set_observation_qc(fluid_ctx *ctx, float threshold);
 int fluid_observation_qc(fluid_ctx *ctx, float *threshold);
 int fluid_observation_qc_result(fluid_ctx *ctx, unsigned char *flags, int *checked, int *rejected);
 
+/* ---- verifying ensembles: CRPS, RMSE against spread and the rank histogram against a truth field, on the device -------------
+ * M = fluid_members(ctx), 2 <= M <= FLUID_TRANSFORM_MAX_MEMBERS, W = N + 2.  The cycle perturbs, forecasts, observes, screens,
+ * analyses and re-inflates in stream order; whether it WORKS is judged in field space, against a truth a twin experiment has
+ * as one more context's pack: the error of the ensemble mean beside the ensemble variance, the continuous ranked probability
+ * score, the rank histogram over the cells.  fluid_verify_members reads the members once, enqueues on the context's stream
+ * and does not wait; nothing crosses to the host.
+ *
+ * `fields`: nfields distinct field ids, host memory, nfields in [1, FLUID_NFIELDS].  `truth_dev`: nfields dense DEVICE arrays of
+ * W*W floats each, the layout and the field_stride rules of the `prior_dev` of fluid_relax_spread (0: W*W; the floats in
+ * between are not read).  `crps_dev`: null, or nfields such arrays at the same stride: the per-cell CRPS as a float, written
+ * inside the box only -- cells outside it and the floats between fields are not touched.  `scores_dev`: device memory,
+ * 8-byte aligned, nfields rows of FLUID_VERIFY_ROW doubles.  `box`: host memory, {row_lo, row_hi, col_lo, col_hi}, half-open
+ * ranges inside [0, W] as fluid_transform_members_local takes them; null: the interior, [1, N+1) x [1, N+1); an empty box is
+ * legal.  `flags`: 0 or FLUID_VERIFY_FAIR.  At most two kernel launches per listed field whatever M and the box are; the
+ * per-block partial results pass through library-owned scratch outside the arena, which grows with the box (a growth the
+ * device refuses is FLUID_E_NOMEM and leaves the context usable).  `fields` and `box` belong to the caller again when the call
+ * returns, the device arrays when the stream has passed the launches.
+ *
+ * Per listed field, per cell of the box.  All arithmetic is IEEE double, every operation rounded once, none contracted.
+ *    1. x_k is what rule 1 of fluid_member_spread reads: the field is settled as a pack settles it, an fp16 value widened
+ *       exactly, a pressure scale divided back in float.  Nothing a later step or download sees is altered.  y is the float
+ *       of `truth_dev`.
+ *    2. mean_d, d_m and q are exactly the chains of fluid_ensemble_stats, in member order (rule 2 of fluid_member_spread).
+ *       var = q / (double)(M - 1);  e = mean_d - (double)y;  se = e * e.
+ *    3. For the CRPS only, every x_k and y is first replaced by v + 0.0f: -0 counts as +0.  s_1 <= .. <= s_M are the x_k
+ *       sorted ascending as floats -- after the replacement equal values are identical bits, so the sequence is unique.
+ *       a = |(double)s_1 - (double)y|, then a += |(double)s_i - (double)y| in increasing i;
+ *       g = (double)(1 - M) * (double)s_1, then g += (double)(2i - M - 1) * (double)s_i in increasing i (every product exact);
+ *       t1 = a / (double)M;  t2 = g / (double)(M*M), or g / (double)(M*(M-1)) with FLUID_VERIFY_FAIR (Ferro 2014);
+ *       crps = t1 - t2.  This is the energy form (1/M) sum |x_m - y| - (1/2M^2) sum sum |x_m - x_k|, the pair sum written over
+ *       the order statistics.
+ *    4. rank = the number of k with x_k < y, compared as floats, as rule 5 of "screening observations": 0 .. M.  A NaN on
+ *       either side counts as "not below".
+ *    5. If any x_k or y of the cell is not finite, crps is a NaN of unspecified sign and payload; e, se and var are what
+ *       their chains give.  The cell poisons the sums it enters and no other cell's map value.
+ *    6. crps_dev[i][j] = (float)crps.
+ * The score row of a field: [0] the number of cells in the box, as a double; [1] sum e; [2] sum se; [3] sum var; [4] sum
+ * crps; [5 + r], r = 0 .. M: the number of cells with rank r, as a double; beyond [5 + M]: +0.0.  The caller derives
+ * bias = [1] / [0], rmse = sqrt([2] / [0]), spread = sqrt([3] / [0]) and the mean CRPS = [4] / [0]; a calibrated ensemble has
+ * rmse^2 ~ (M + 1) / M * [3] / [0] and a flat histogram.
+ * Counts are integers until the end and exact.  Order of each of the four sums: the cells of the box are numbered row by
+ * row, t = (row - row_lo) * (col_hi - col_lo) + (col - col_lo); B = min(ceil(cells / 256), 2048) blocks of 256 lanes; lane L
+ * of the 256 * B chains the terms of the cells L, L + 256 * B, .. in increasing t, from -0.0 (a sum starts from its first
+ * term); the 64 lanes of a wave are added by a butterfly, lane j taking lane j ^ 32's, then ^ 16, 8, 4, 2, 1; a block's four
+ * waves in wave order; then lane j of 64 chains the blocks j, j + 64, .. from -0.0 and the same butterfly adds the 64.  So the
+ * order depends on (N, box, M, storage type, flags) and on nothing else -- not on the device, not on the call before: no
+ * floating-point atomics, the same bits call after call and process after process, and the exact sum whenever every
+ * partial sum is representable.  An empty box gives count 0, zero sums (of either sign) and zero bins.  No matrix instructions.
+ * Refusals, all FLUID_E_INVALID with a message that names the call, found before anything is launched or any state changes,
+ * null pointers before the context is looked at: a null `fields`, `truth_dev` or `scores_dev`, a null context; whatever
+ * fluid_member_spread refuses of its list, its stride and its device array, under this call's name (M < 2 among it);
+ * M > FLUID_TRANSFORM_MAX_MEMBERS (the message gives both numbers); a box entry outside [0, W] or a lo above its hi; unknown
+ * flag bits; a `scores_dev` that is not 8-byte aligned, or whose nfields * FLUID_VERIFY_ROW doubles do not lie inside one
+ * allocation of the context's device; a `crps_dev` whose extent, that of `truth_dev`, does not; row slabs.
+ * The launches belong to none of the fluid_timing categories. */
+#define FLUID_VERIFY_SUMS 5
+#define FLUID_VERIFY_ROW  (FLUID_VERIFY_SUMS + FLUID_TRANSFORM_MAX_MEMBERS + 1)   /* 70 doubles */
+#define FLUID_VERIFY_FAIR 1   /* flags: the CRPS's pair term over M(M-1) in place of M*M (Ferro 2014) */
+int fluid_verify_members(fluid_ctx *ctx, const int *fields, int nfields, const void *truth_dev, size_t field_stride, const int *box,
+                         int flags, void *crps_dev, void *scores_dev);
+
 int fluid_set_jacobi_variant(fluid_ctx *ctx, int variant);
 /* How FLUID_JACOBI_TB divides by `beta` in a solve with these coefficients (diagnostic; runs the on-device proof
  * if this beta has not been seen): 0 true division, 2 double-precision reciprocal, 3 two-term float reciprocal
