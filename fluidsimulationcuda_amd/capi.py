@@ -172,6 +172,9 @@ SIGNATURES = {
     "fluid_observation_qc": [_ctx, _MF],
     "fluid_observation_qc_result": [_ctx, C.POINTER(C.c_ubyte), C.POINTER(_i), C.POINTER(_i)],
     "fluid_verify_members": [_ctx, C.POINTER(_i), _i, C.c_void_p, C.c_size_t, C.POINTER(_i), _i, C.c_void_p, C.c_void_p],
+    "fluid_quantile_position": [_i, _f, C.POINTER(_i), C.POINTER(C.c_double)],
+    "fluid_member_quantiles": [_ctx, _i, _MF, _i, C.c_void_p, C.c_size_t],
+    "fluid_member_exceedance": [_ctx, _i, _MF, _i, _i, C.c_void_p, C.c_size_t],
     "fluid_set_jacobi_variant": [_ctx, _i],
     "fluid_division_mode": [_ctx, _f, _f, C.POINTER(_i)],
     "fluid_autotune_pending": [_ctx, C.POINTER(_i)],
@@ -211,6 +214,8 @@ WINDOW_MAX_SLOTS = 65536             # FLUID_WINDOW_MAX_SLOTS: slots of one flui
 VERIFY_SUMS = 5                      # FLUID_VERIFY_SUMS: count, then the sums of e, se, var and crps
 VERIFY_ROW = VERIFY_SUMS + TRANSFORM_MAX_MEMBERS + 1      # FLUID_VERIFY_ROW: doubles per field of a score row
 VERIFY_FAIR = 1                      # FLUID_VERIFY_FAIR
+QUANTILE_MAX_LEVELS = 16             # FLUID_QUANTILE_MAX_LEVELS: levels of one quantiles call, thresholds of one exceedance call
+EXCEED_ABOVE, EXCEED_BELOW = 0, 1
 
 _lib = None
 

@@ -21,6 +21,7 @@
 #include "fluid_etkf.h"
 #include "fluid_noise.h"
 #include "fluid_verify.h"
+#include "fluid_quantile.h"
 
 namespace fluid_detail {
 
@@ -3168,6 +3169,88 @@ int fluid_verify_members(fluid_ctx* c, const int* fields, int nfields, const voi
                                      static_cast<double*>(scores_dev) + (size_t)k * FLUID_VERIFY_ROW);
         HIP_TRY(hipGetLastError());
     }
+    return FLUID_OK;
+}
+
+// ---- ensemble products: fluid_quantile_position / fluid_member_quantiles / fluid_member_exceedance --------------------------
+// (include/fluid_amd.h "ensemble products".)  One field per call.  The null pointers, then the context, the count, the field,
+// the list's values, then the slabs, the stride and the device extent, as a spread's are checked.  The field is settled as
+// pack_range settles it, a scale KEPT: the products alter nothing.  ONE launch per call, no wait; the launches belong to
+// none of the timing categories.
+static_assert(FLUID_QUANTILE_MAX_LEVELS == fluid::kQuantileMaxLevels, "the header's level count is the kernels'");
+
+static int check_products(const fluid_ctx* c, const char* call, const char* name, const void* dev, int count, size_t* stride)
+{
+    TRY(refuse_slabs(c, call));
+    const size_t cells = member_cells(c);
+    if (*stride == 0) *stride = cells;
+    if (*stride < cells) return fail(FLUID_E_INVALID, "%s: level_stride %zu is below (N + 2)^2 = %zu", call, *stride, cells);
+    size_t bytes = 0;
+    if (!dense_span(cells, count, *stride, &bytes)) return fail(FLUID_E_INVALID, "%s: level_stride %zu is too large", call, *stride);
+    return check_device_span(c, call, name, dev, bytes);
+}
+
+int fluid_quantile_position(int members, float level, int* lo, double* frac)
+{
+    const char* call = "fluid_quantile_position";
+    if (!lo) return fail(FLUID_E_INVALID, "%s: null pointer `lo`", call);
+    if (!frac) return fail(FLUID_E_INVALID, "%s: null pointer `frac`", call);
+    if (members < 1 || members > FLUID_TRANSFORM_MAX_MEMBERS)
+        return fail(FLUID_E_INVALID, "%s: members %d outside [1, %d]", call, members, FLUID_TRANSFORM_MAX_MEMBERS);
+    if (!std::isfinite(level) || level < 0.0f || level > 1.0f)
+        return fail(FLUID_E_INVALID, "%s: level %g is not finite or lies outside [0, 1]", call, (double)level);
+    fluid::quantile_position(members, level, lo, frac);
+    return FLUID_OK;
+}
+
+int fluid_member_quantiles(fluid_ctx* c, int field, const float* levels, int nlevels, void* out_dev, size_t level_stride)
+{
+    const char* call = "fluid_member_quantiles";
+    if (!levels) return fail(FLUID_E_INVALID, "%s: null array `levels`", call);
+    if (!out_dev) return fail(FLUID_E_INVALID, "%s: null device pointer `out_dev`", call);
+    if (!c) return fail(FLUID_E_INVALID, "%s: null context", call);
+    if (nlevels < 1 || nlevels > FLUID_QUANTILE_MAX_LEVELS)
+        return fail(FLUID_E_INVALID, "%s: nlevels %d outside [1, %d]", call, nlevels, FLUID_QUANTILE_MAX_LEVELS);
+    if (!c->valid_field(field)) return fail(FLUID_E_INVALID, "%s: bad field id %d", call, field);
+    for (int l = 0; l < nlevels; ++l)
+        if (!std::isfinite(levels[l]) || levels[l] < 0.0f || levels[l] > 1.0f)
+            return fail(FLUID_E_INVALID, "%s: levels[%d] = %g is not finite or lies outside [0, 1]", call, l, (double)levels[l]);
+    if (c->members > FLUID_TRANSFORM_MAX_MEMBERS)
+        return fail(FLUID_E_INVALID, "%s: this context has %d members, above FLUID_TRANSFORM_MAX_MEMBERS = %d", call, c->members,
+                    FLUID_TRANSFORM_MAX_MEMBERS);
+    TRY(check_products(c, call, "out_dev", out_dev, nlevels, &level_stride));
+    fluid::QuantileLevels lv = {};
+    lv.count = nlevels;
+    for (int l = 0; l < nlevels; ++l) fluid::quantile_position(c->members, levels[l], &lv.lo[l], &lv.frac[l]);
+    const float inv = c->st != fluid::STORAGE_F32 ? 1.0f / c->field[field].fscale : 1.0f;      // as pack_range sees the field
+    TRY(materialize(c, field, /*keep_scale=*/inv != 1.0f));
+    fluid::launch_member_quantiles(c->stream, c->st, c->ptr(field), c->pitch, c->n, c->mb(), inv, lv, static_cast<float*>(out_dev), level_stride);
+    HIP_TRY(hipGetLastError());
+    return FLUID_OK;
+}
+
+int fluid_member_exceedance(fluid_ctx* c, int field, const float* thresholds, int nthresholds, int mode, void* out_dev, size_t level_stride)
+{
+    const char* call = "fluid_member_exceedance";
+    if (!thresholds) return fail(FLUID_E_INVALID, "%s: null array `thresholds`", call);
+    if (!out_dev) return fail(FLUID_E_INVALID, "%s: null device pointer `out_dev`", call);
+    if (!c) return fail(FLUID_E_INVALID, "%s: null context", call);
+    if (nthresholds < 1 || nthresholds > FLUID_QUANTILE_MAX_LEVELS)
+        return fail(FLUID_E_INVALID, "%s: nthresholds %d outside [1, %d]", call, nthresholds, FLUID_QUANTILE_MAX_LEVELS);
+    if (!c->valid_field(field)) return fail(FLUID_E_INVALID, "%s: bad field id %d", call, field);
+    for (int l = 0; l < nthresholds; ++l)
+        if (!std::isfinite(thresholds[l])) return fail(FLUID_E_INVALID, "%s: thresholds[%d] = %g is not finite", call, l, (double)thresholds[l]);
+    if (mode != FLUID_EXCEED_ABOVE && mode != FLUID_EXCEED_BELOW)
+        return fail(FLUID_E_INVALID, "%s: mode %d is neither FLUID_EXCEED_ABOVE nor FLUID_EXCEED_BELOW", call, mode);
+    TRY(check_products(c, call, "out_dev", out_dev, nthresholds, &level_stride));
+    fluid::ExceedLevels lv = {};
+    lv.count = nthresholds;
+    for (int l = 0; l < nthresholds; ++l) lv.threshold[l] = thresholds[l];
+    const float inv = c->st != fluid::STORAGE_F32 ? 1.0f / c->field[field].fscale : 1.0f;      // as pack_range sees the field
+    TRY(materialize(c, field, /*keep_scale=*/inv != 1.0f));
+    fluid::launch_member_exceedance(c->stream, c->st, c->ptr(field), c->pitch, c->n, c->mb(), inv, lv, mode == FLUID_EXCEED_BELOW,
+                                    static_cast<float*>(out_dev), level_stride);
+    HIP_TRY(hipGetLastError());
     return FLUID_OK;
 }
 

@@ -736,6 +736,48 @@ class FluidSolver:
                             "crps": float(r[4] / n), "rank_hist": r[s:s + self.members + 1].astype(np.int64)})
         return res
 
+    # -- ensemble products: order statistics and exceedance probabilities per cell across the members
+    def _levels(self, values, name):
+        a = np.ascontiguousarray(np.atleast_1d(np.asarray(values, dtype=np.float32)))
+        if a.ndim != 1 or not 1 <= a.size <= capi.QUANTILE_MAX_LEVELS:
+            raise ValueError("%s: expected 1 to %d values, got shape %s" % (name, capi.QUANTILE_MAX_LEVELS, a.shape))
+        return a
+
+    def quantiles(self, field="dens", levels=(0.5,), out=None, wait=True):
+        """Quantile fields of one field across the members, in one launch: an (nlevels, N+2, N+2) float32 device tensor, map l
+        the `levels[l]` quantile per cell (ghost ring included) of what pack would show, by numpy's default linear
+        interpolation between the order statistics -- 0 the minimum, 0.5 the median, 1 the maximum; -0 counts as +0; a
+        cell with a non-finite member is NaN.  Up to capi.QUANTILE_MAX_LEVELS levels in [0, 1], in any order; 1 <= members
+        <= capi.TRANSFORM_MAX_MEMBERS.  `out`: such a tensor to fill, None allocates one; `wait`: as for pack
+        (include/fluid_amd.h, "ensemble products")."""
+        lv = self._levels(levels, "levels")
+        if out is None:
+            import torch
+            out = torch.empty((lv.size, self.n + 2, self.n + 2), dtype=torch.float32, device="cuda")
+        address = self._spread_tensor(out, lv.size, "out")
+        self._handover(wait)
+        capi.check(capi.lib().fluid_member_quantiles(self._h, _fid(field), _mf(lv), lv.size, address, 0))
+        if wait:
+            self.synchronize()
+        return out
+
+    def exceedance(self, field, thresholds, below=False, out=None, wait=True):
+        """Exceedance probabilities of one field, in one launch: an (nthresholds, N+2, N+2) float32 device tensor, map l the
+        fraction of members whose value lies above `thresholds[l]` (`below`: beneath it) per cell of what pack would show.
+        A NaN member counts as neither.  Up to capi.QUANTILE_MAX_LEVELS finite thresholds; any members >= 1.  `out`, `wait`:
+        as for quantiles (include/fluid_amd.h, "ensemble products")."""
+        th = self._levels(thresholds, "thresholds")
+        if out is None:
+            import torch
+            out = torch.empty((th.size, self.n + 2, self.n + 2), dtype=torch.float32, device="cuda")
+        address = self._spread_tensor(out, th.size, "out")
+        self._handover(wait)
+        capi.check(capi.lib().fluid_member_exceedance(self._h, _fid(field), _mf(th), th.size,
+                                                      capi.EXCEED_BELOW if below else capi.EXCEED_ABOVE, address, 0))
+        if wait:
+            self.synchronize()
+        return out
+
     # -- ensemble noise: reproducible randomness on the device, the same bits for every members, launch shape and process
     def _amplitudes(self, amplitude):
         a = np.asarray(amplitude, dtype=np.float32)
@@ -1036,6 +1078,14 @@ def noise_value(seed, sequence, tag, member_id, c0, c1):
     z = C.c_double()
     capi.check(capi.lib().fluid_noise_value(int(seed), int(sequence), int(tag), int(member_id), int(c0), int(c1), C.byref(z)))
     return z.value
+
+
+def quantile_position(members, level):
+    """(lo, frac): where the `level` quantile of `members` sorted values lies -- between values lo and lo + 1, the fraction
+    frac of the way; numpy's default linear position (fluid_quantile_position: host logic, no device)."""
+    lo, frac = C.c_int(), C.c_double()
+    capi.check(capi.lib().fluid_quantile_position(int(members), float(level), C.byref(lo), C.byref(frac)))
+    return lo.value, frac.value
 
 
 def coefficients(n, dt, coef):

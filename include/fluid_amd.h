@@ -1163,6 +1163,61 @@ int fluid_observation_qc_result(fluid_ctx *ctx, unsigned char *flags, int *check
 int fluid_verify_members(fluid_ctx *ctx, const int *fields, int nfields, const void *truth_dev, size_t field_stride, const int *box,
                          int flags, void *crps_dev, void *scores_dev);
 
+/* ---- ensemble products: quantile fields and exceedance probabilities, per cell across the members, on the device -------------
+ * M = fluid_members(ctx), W = N + 2.  What an ensemble FORECAST hands to its user beside the mean and the variance
+ * (fluid_ensemble_stats, fluid_member_spread): order statistics per cell -- the median, the quartiles, the 5 % / 95 % envelope,
+ * minimum and maximum -- and exceedance probabilities, the fraction of members above or below a threshold per cell.  Both
+ * calls read the members once, in place: no M*W*W dense copy, no second pass.
+ *
+ * Common to both device calls.  Each call handles ONE field.  `out_dev`: nlevels (nthresholds) dense DEVICE arrays of W*W
+ * floats each, row-major with the ghost ring -- the layout of the `out_dev` of fluid_member_spread --, array l starting
+ * l * level_stride floats behind the pointer; level_stride = 0: W*W; any other value must be at least W*W (the floats in
+ * between are not touched).  Alignment: 4 bytes.  Every cell of the W x W array is computed; pad columns are neither read nor
+ * written.  ONE kernel launch per call whatever M and the level count are, enqueued on the context's stream, no wait; the host
+ * arrays belong to the caller again when the call returns, `out_dev` when the stream has passed the launch.  The field's
+ * lazy state is settled first, as fluid_member_spread settles it: x_k is the float the pack would show for member k right
+ * before the call -- with fp16 storage the stored value widened exactly, a pressure scale divided back in float.  Nothing a
+ * later step or download sees is altered.  No atomics, no LDS, no matrix instructions: the same bits for every launch shape.
+ *
+ * - fluid_quantile_position: host logic only, no context and no device, like fluid_coefficients and fluid_noise_value.
+ *   `members` in [1, FLUID_TRANSFORM_MAX_MEMBERS], `level` finite and in [0, 1].  In IEEE double: h = (double)level *
+ *   (double)(members - 1) -- the product is exact, 24 + 7 bits --; *lo = floor(h); *frac = h - *lo, also exact.  If *lo >=
+ *   members - 1: *lo = members - 1 and *frac = 0.  This is numpy's default ("linear", Hyndman & Fan 1996 type 7) position.
+ *   fluid_member_quantiles and this function share one body.
+ * - fluid_member_quantiles: 1 <= M <= FLUID_TRANSFORM_MAX_MEMBERS; M = 1 is legal.  `levels`: nlevels host floats, nlevels in
+ *   [1, FLUID_QUANTILE_MAX_LEVELS]; they may repeat and need not be ordered.  Per cell:
+ *    1. Every x_k is replaced by x_k + 0.0f: -0 counts as +0, as in rule 3 of fluid_verify_members.  s_0 <= .. <= s_{M-1} are
+ *       the values sorted ascending as floats -- after the replacement equal values are identical bits, so the sequence is
+ *       unique.
+ *    2. Per level l: (lo, frac) = fluid_quantile_position(M, levels[l]), computed once on the host.  frac == 0: out = s_lo, a
+ *       bit copy.  Otherwise d = (double)s_{lo+1} - (double)s_lo; t = frac * d; q = (double)s_lo + t -- each of the three
+ *       rounded once, none contracted --; out = (float)q.
+ *    3. If any x_k of the cell is not finite, every level's value in that cell is a NaN of unspecified sign and payload.  No
+ *       other cell is affected.
+ *    4. So level 0 is the minimum, 1 the maximum, 0.5 the median; with M even the median is the midpoint under rule 2.
+ * - fluid_member_exceedance: ANY M >= 1 the context has, NOT capped at FLUID_TRANSFORM_MAX_MEMBERS: the kernel walks the
+ *   members in a loop, as the spread does.  `thresholds`: nthresholds finite host floats t_l, nthresholds in [1,
+ *   FLUID_QUANTILE_MAX_LEVELS].  Per cell and per threshold l:
+ *    1. count = the number of k with x_k > t_l (FLUID_EXCEED_ABOVE) or with x_k < t_l (FLUID_EXCEED_BELOW), compared as
+ *       floats: -0 equals +0, a NaN member counts as neither, +-inf compare as they do.
+ *    2. out = (float)((double)count / (double)M).
+ *    3. The members are read once for all thresholds.
+ * Refusals, all FLUID_E_INVALID with a message that names the call and, where it applies, the list index, found before
+ * anything is launched or any state changes, null pointers before the context is looked at: a null `levels`, `thresholds`,
+ * `out_dev`, `lo` or `frac`, a null context; a count outside [1, FLUID_QUANTILE_MAX_LEVELS]; a bad field id; a level that is not
+ * finite or lies outside [0, 1]; a threshold that is not finite; a mode that is neither of the two; `members` outside [1,
+ * FLUID_TRANSFORM_MAX_MEMBERS] for the position; M > FLUID_TRANSFORM_MAX_MEMBERS for the quantiles (the message gives both
+ * numbers); a level_stride that is neither 0 nor at least W*W; an `out_dev` that is not device memory of the context's device,
+ * or whose whole extent, (count - 1) * level_stride + W*W floats, does not lie inside one allocation (asked of the runtime on
+ * the host, as for a pack); row slabs.
+ * The launches belong to none of the fluid_timing categories. */
+#define FLUID_QUANTILE_MAX_LEVELS 16
+enum { FLUID_EXCEED_ABOVE = 0, FLUID_EXCEED_BELOW = 1 };
+int fluid_quantile_position(int members, float level, int *lo, double *frac);
+int fluid_member_quantiles(fluid_ctx *ctx, int field, const float *levels, int nlevels, void *out_dev, size_t level_stride);
+int fluid_member_exceedance(fluid_ctx *ctx, int field, const float *thresholds, int nthresholds, int mode, void *out_dev,
+                            size_t level_stride);
+
 int fluid_set_jacobi_variant(fluid_ctx *ctx, int variant);
 /* How FLUID_JACOBI_TB divides by `beta` in a solve with these coefficients (diagnostic; runs the on-device proof
  * if this beta has not been seen): 0 true division, 2 double-precision reciprocal, 3 two-term float reciprocal
